@@ -16,7 +16,7 @@ shard of --batch aggregates that its key range owns, exactly what the
 reference's worker-side sliceKeyOrderedMsg delivers (message.h:89-123);
 per-GPU work is fixed ("scaling": "weak").
 
-The line also carries a "cfg5" block (BASELINE.json configs[4], the
+With --full the line also carries a "cfg5" block (BASELINE.json configs[4], the
 north star's 8-GPU target): ONE fixed global workload -- 256 worker pushes
 x 262,144 murmur-shuffled uniform keys over a 1e9-rank (1 B-key) space --
 range-partitioned over the N ranks (strong scaling), timed on all ranks
@@ -24,6 +24,21 @@ together, plus the same whole workload on ONE GPU (rank 0) in the same job,
 so "speedup_vs_1gpu" is measured, not inferred.
 
 --workload cfg3|cfg4|cfg5 runs a single-GPU side line of that config.
+
+A plain run (no --full) does only what the headline figure needs: it
+generates the inputs, builds the plan, warms up, times --steps steps, writes
+the outputs when --dump-outputs is given and prints the line (headline
+fields, config, and the roofline figures the timed region itself yields).
+--full adds everything else to the line: the partition's own time, the copy
+ceiling and PMC traffic of the roofline, the f64 and cfg5 blocks, the
+end-to-end host path, the SURVEY 8(f) rows, the CPU baseline and cfg4's
+server-API leg (each still switchable with its --no-* option).
+
+--dump-outputs DIR writes what the last timed step computed (the per-key sums
+a caller of the plan reads from its output arrays, and the matched count of
+every push) as DIR/sums.npy and DIR/matched.npy (DIR/<name>_rank<r>.npy per
+rank in a multi-GPU job).  Inputs are generated from fixed seeds, so two
+builds run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -79,6 +94,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: partition time, copy "
+                         "ceiling and PMC traffic of the roofline, the f64 and cfg5 blocks, "
+                         "end-to-end host path, 8(f) rows, CPU baseline, cfg4's server-API leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (per-key sums, "
+                         "matched counts) as DIR/<name>.npy; a fixed seeded sample of the sums "
+                         "when they exceed 48 MB")
     ap.add_argument("--prewarm-ms", type=float, default=100.0,
                     help="untimed steps for this long before each timed region's warm-up "
                          "steps (the GPU's clock ramp after host-side phases; 0 = off)")
@@ -207,13 +230,14 @@ def prewarm(step):
             return n
 
 
-def timed_steps(plan, K, W, stream, dist):
+def timed_steps(plan, K, W, stream, dist, partition=True):
     """W untimed warm-up steps (after the prewarm), then exactly K timed steps
     bracketed by a barrier + device synchronize on both sides.  Returns (wall
     s, mean partition ms, mean aggregate ms).  Inside the timed region two
     HIP events per step bracket the aggregate kernel on its launch stream
     (the roofline's kernel time); the partition's time comes from a second,
-    untimed pass of K steps with events around the partition.  A third event
+    untimed pass of K steps with events around the partition
+    (partition_pass; None with partition=False).  A third event
     per step between the stages cost ~6 us per step (1.6 %,
     profiles/r06_warm_probe.txt)."""
     import torch
@@ -238,15 +262,52 @@ def timed_steps(plan, K, W, stream, dist):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     agg = float(np.mean([ev[s][0].elapsed_time(ev[s][1]) for s in range(K)]))
-    # the partition, untimed: events around it in K more steps
+    return wall, partition_pass(plan, K, stream) if partition else None, agg
+
+
+def partition_pass(plan, K, stream):
+    """The partition's mean ms, untimed: events around it in K more steps."""
+    import torch
+    sh = stream.cuda_stream
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(2)] for _ in range(K)]
     for s in range(K):
         ev[s][0].record(stream)
         plan.run_stage(0, sh)
         ev[s][1].record(stream)
         plan.run_stage(1, sh)
     torch.cuda.synchronize()
-    part = float(np.mean([ev[s][0].elapsed_time(ev[s][1]) for s in range(K)]))
-    return wall, part, agg
+    return float(np.mean([ev[s][0].elapsed_time(ev[s][1]) for s in range(K)]))
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: most bytes of sums written, all ranks together
+
+
+def dump_outputs(path, plan, keep, jobs, rank, world):
+    """--dump-outputs: the output arrays of the plan as the last timed step
+    left them.  sums: every aggregate's per-key sums (its `out` array, f32 or
+    f64 as computed), aggregate after aggregate; when they exceed DUMP_BYTES,
+    a fixed sample instead: of each aggregate the same share of slots, drawn
+    without replacement by default_rng(0), in ascending slot order.  matched:
+    the matched-key count of every push (float64)."""
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    total = sum(int(jb["nslots"]) for jb in jobs)
+    budget = DUMP_BYTES // world // keep[0][3].element_size() if keep else 0
+    rng = np.random.default_rng(0)
+    parts = []
+    for (_, _, _, out), jb in zip(keep, jobs):
+        n = int(jb["nslots"])
+        if total <= budget:
+            parts.append(out[:n].cpu().numpy())
+        else:
+            idx = np.sort(rng.choice(n, n * budget // total, replace=False))
+            parts.append(out[torch.from_numpy(idx).to(out.device)].cpu().numpy())
+    sums = np.concatenate(parts) if parts else np.zeros(0, np.float32)
+    np.save(os.path.join(path, f"sums{sfx}.npy"), sums)
+    np.save(os.path.join(path, f"matched{sfx}.npy"), plan.matched().astype(np.float64))
+    log(f"rank {rank}: wrote {sums.size:,} of {total:,} sums ({sums.dtype}) to {path}")
 
 
 def main():
@@ -282,7 +343,7 @@ def main():
     # ---- synthetic inputs (each rank: its shard of `batch` aggregates) ----
     t0 = time.time()
     if wl != "cfg2" and world > 1:
-        raise SystemExit("--workload cfg3/cfg4/cfg5 are single-GPU side lines; the default "
+        raise SystemExit("--workload cfg3/cfg4/cfg5 are single-GPU side lines; the --full "
                          "line carries cfg5's multi-GPU strong-scaling block")
     vdt = np.float64 if args.dtype == "f64" else np.float32
     if args.dtype == "f64" and wl != "cfg2":
@@ -315,7 +376,11 @@ def main():
         "unmatched keys in the bench workload"
 
     K = args.steps
-    wall, part_ms, agg_ms = timed_steps(plan, K, args.warmup, stream, dist)
+    wall, _, agg_ms = timed_steps(plan, K, args.warmup, stream, dist, partition=False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan, keep, jobs, rank, world)
+    # the partition's own time takes K more steps: --full and profile runs
+    part_ms = partition_pass(plan, K, stream) if args.full or args.profile_steps else None
     wall_max, kv_all = reduce_over_ranks(wall, plan.kv_pairs, dist, dev)
     value = kv_all * K / wall_max
     ms_per_step = wall_max / K * 1e3
@@ -341,8 +406,10 @@ def main():
                    "(SURVEY 8d)")
     achieved = nbytes / (agg_ms * 1e-3) / 1e9
     step_gbps = nbytes / (ms_per_step * 1e-3) / 1e9
-    copy_gbps = copy_bandwidth(dev, stream)
-    traffic = load_traffic(nbytes, wl)
+    # beside the headline (--full): the copy ceiling (a run of its own) and
+    # the committed PMC traffic of this workload
+    copy_gbps = copy_bandwidth(dev, stream) if args.full else None
+    traffic = load_traffic(nbytes, wl) if args.full else None
 
     result = {
         "metric": METRIC,
@@ -352,6 +419,7 @@ def main():
         "steps": K,
         "warmup": args.warmup,
         "prewarm_ms": args.prewarm_ms,
+        "full": args.full,
         "ms_per_step": ms_per_step,
         "higher_is_better": True,
         "scaling": "weak",
@@ -387,6 +455,12 @@ def main():
             "frac_of_measured_copy": achieved / copy_gbps if copy_gbps else None,
         },
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     if wl == "cfg4" and rank == 0 and not args.no_server_api:
         del plan, keep
         torch.cuda.empty_cache()

@@ -10,6 +10,7 @@ import pytest
 import oracle_py as O
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "known_answers.json")))
+REF = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_vectors.json")))
 ALL = (0, (1 << 64) - 1)
 
 
@@ -62,8 +63,12 @@ def test_murmur_shuffle_known_and_reference():
     s = GOLD["shuffle"]
     got = O.shuffle_keys(s["ids"])
     assert [int(x) for x in got] == [int(x) for x in s["keys"]]
+    # the reference build's recorded outputs (tests/golden/reference_vectors.json),
+    # and oracle/_ref itself where the reference tree was there to build it
+    m = REF["murmur_shuffle"]
+    ids = np.arange(*m["ids"], dtype=np.uint64)
+    assert [int(x) for x in O.shuffle_keys(ids, m["seed"])] == [int(x) for x in m["keys"]]
     if O.ref_murmur_available():
-        ids = np.arange(0, 2000, 7, dtype=np.uint64)
         assert np.array_equal(O.shuffle_keys(ids), O.ref_shuffle_keys(ids))
     # the product's numpy generator restates the same hash
     from parameter_server_amd import synth

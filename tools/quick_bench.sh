@@ -9,6 +9,6 @@ if [ -z "$NOTEST" ]; then
 fi
 for w in ${WLS:-cfg2 cfg3 cfg4 cfg5}; do
   a="--workload $w"; [ $w = cfg2 ] && a="--no-cfg5"
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline $a $BARGS > $O/$w.json 2> $O/$w.err || { echo "bench $w failed"; tail -3 $O/$w.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $a $BARGS > $O/$w.json 2> $O/$w.err || { echo "bench $w failed"; tail -3 $O/$w.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/$w.json'));r=d['roofline'];print('$w','%.3e'%d['value'],'ms/step %.3f kern %.3f part %.3f frac %.3f step_frac %.3f copy %s'%(d['ms_per_step'],r['kernel_ms'],r['partition_ms'],r['frac'],r['step_frac'],r['measured_copy_GBps']))"
 done
