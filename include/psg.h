@@ -447,6 +447,70 @@ int psg_freq_query_dev(psg_ctx* ctx, int chl, const uint64_t* keys, size_t n,
 int psg_freq_table(psg_ctx* ctx, int chl, uint8_t* out, size_t n);
 
 /* ------------------------------------------------------------------ */
+/* Online server model: FTRLModel<uint64, double>                      */
+/* (src/linear_method/ftrl_model.h, driven by linear_method/ftrl.cc),  */
+/* a hash map from key to {uint64 pos, uint64 neg, double w, double z} */
+/* resident in the HBM of the context's device.                        */
+/* ------------------------------------------------------------------ */
+/* One model per context; it needs a PSG_F64 context (V = double,
+ * ftrl.h:26; PSG_ERR_ARG otherwise) and every call before psg_ftrl_init is
+ * PSG_ERR_ARG.  Every uint64 is a legal key.  Messages are applied one after
+ * another in call order, whatever streams the device forms are given.
+ * Defined deviations from the reference:
+ *  - a pull does not insert: getValue's operator[] (ftrl_model.h:76) adds a
+ *    default entry there, which nothing observes but the map's size; here
+ *    `entries` counts the keys touched by a push;
+ *  - norm1 / norm2 are not running sums (ftrl_model.h:104-105, a serial
+ *    chain in key order) but a fixed-order device reduction over the table,
+ *    computed by psg_ftrl_status: sum |w| and sum w^2, each within
+ *    entries * 2^-53 * (the exact sum) of it; nnz is exact;
+ *  - a pushed message must be strictly increasing (the reference's callers
+ *    send countUniqIndex's sorted unique keys, ftrl.cc:93-96,143, and the
+ *    model does not check).  One that is not is rejected whole by a device
+ *    check that runs ahead of the update, reported once as PSG_ERR_UNSORTED
+ *    by the next psg_ftrl_pull, psg_ftrl_status or psg_ftrl_export, and then
+ *    cleared; later messages apply normally.  psg_ftrl_lookup is a probe
+ *    for tests and checkpoints and neither reports nor clears it;
+ *  - psg_ftrl_export's order is unspecified (as writeToFile's is, the
+ *    reference's map order); the Python and C++ mirrors sort by key. */
+typedef struct psg_ftrl_param {
+  double alpha, beta;      /* setLearningRate, ftrl_model.h:15-18 */
+  double lambda1, lambda2; /* setPenalty, ftrl_model.h:19-22 */
+} psg_ftrl_param;
+/* A fresh, empty model (ftrl_model.h:47-68) sized for capacity_hint entries
+ * (0: a default; any value is legal, the table grows by rehash). */
+int psg_ftrl_init(psg_ctx* ctx, const psg_ftrl_param* p, size_t capacity_hint);
+/* Room for `entries` entries: pushes allocate nothing and read no device
+ * count until the keys pushed could number more than that. */
+int psg_ftrl_reserve(psg_ctx* ctx, size_t entries);
+/* setValue(msg) (ftrl_model.h:80-112): msg->key = keys[n], msg->value =
+ * {pos[n], neg[n], grad[n]}.  Host arrays, free on return; the update runs
+ * asynchronously on the context's stream (PSG_HOLD_BUFFERS as for psg_push).
+ * Thresholded weights are -0.0, as the reference's are. */
+int psg_ftrl_push(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint32_t* pos,
+                  const uint32_t* neg, const double* grad);
+/* The same with device arrays, enqueued on `stream`; allocates nothing and
+ * waits for nothing while the model has room (psg_ftrl_reserve). */
+int psg_ftrl_push_dev(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint32_t* pos,
+                      const uint32_t* neg, const double* grad, void* stream);
+/* getValue(msg) (ftrl_model.h:72-78): out[i] = w of keys[i], +0.0 for a key
+ * never pushed.  Keys in any order, repeats allowed. */
+int psg_ftrl_pull(psg_ctx* ctx, const uint64_t* keys, size_t n, double* out);
+int psg_ftrl_pull_dev(psg_ctx* ctx, const uint64_t* keys, size_t n, double* out, void* stream);
+/* nnz() (ftrl_model.h:32) and the terms of objv() (:31) = norm1 * lambda1 +
+ * .5 * lambda2 * sqrt(norm2); entries = model_.size().  Any output may be
+ * NULL.  Synchronises. */
+int psg_ftrl_status(psg_ctx* ctx, size_t* entries, size_t* nnz, double* norm1, double* norm2);
+/* writeToFile's content (ftrl_model.h:24-29): (key, w) of every entry with
+ * w != 0, order unspecified.  *n = their count; PSG_ERR_SIZE (nothing
+ * copied) if that exceeds cap. */
+int psg_ftrl_export(psg_ctx* ctx, uint64_t* keys, double* w, size_t cap, size_t* n);
+/* Whole entries (tests, checkpoints): found[i] = 1 and the entry of keys[i],
+ * or 0 and zeros.  Any output may be NULL. */
+int psg_ftrl_lookup(psg_ctx* ctx, const uint64_t* keys, size_t n, uint64_t* pos, uint64_t* neg,
+                    double* w, double* z, uint8_t* found);
+
+/* ------------------------------------------------------------------ */
 /* Wire ingress: key signatures of the key cache                       */
 /* ------------------------------------------------------------------ */
 /* CRC-32C of device-resident byte segments: out[i] = crc32c::Extend(

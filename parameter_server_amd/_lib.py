@@ -82,6 +82,13 @@ class MergeJob(C.Structure):
     ]
 
 
+class FtrlParam(C.Structure):
+    """psg_ftrl_param (include/psg.h)."""
+
+    _fields_ = [("alpha", C.c_double), ("beta", C.c_double),
+                ("lambda1", C.c_double), ("lambda2", C.c_double)]
+
+
 SIGNATURES = {
     "psg_abi_version": (C.c_int, []),
     "psg_status_string": (C.c_char_p, [C.c_int]),
@@ -163,6 +170,15 @@ SIGNATURES = {
     "psg_darling_reset_active": (C.c_int, [_p, C.c_int]),
     "psg_darling_update": (C.c_int, [_p, C.c_int, C.c_int, _p, C.POINTER(C.c_double)]),
     "psg_darling_state": (C.c_int, [_p, C.c_int, _sz, _sz, _p, _p, _psz]),
+    "psg_ftrl_init": (C.c_int, [_p, _p, _sz]),
+    "psg_ftrl_reserve": (C.c_int, [_p, _sz]),
+    "psg_ftrl_push": (C.c_int, [_p, _p, _sz, _p, _p, _p]),
+    "psg_ftrl_push_dev": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p]),
+    "psg_ftrl_pull": (C.c_int, [_p, _p, _sz, _p]),
+    "psg_ftrl_pull_dev": (C.c_int, [_p, _p, _sz, _p, _p]),
+    "psg_ftrl_status": (C.c_int, [_p, _psz, _psz, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "psg_ftrl_export": (C.c_int, [_p, _p, _p, _sz, _psz]),
+    "psg_ftrl_lookup": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _p]),
 }
 
 _LIB = None

@@ -223,6 +223,65 @@ hipError_t launch_cm_query(const uint64_t* keys, uint64_t nk, const uint8_t* tab
                            int k, int freq, uint64_t* out, unsigned long long* nout,
                            void* scratch, hipStream_t stream);
 
+// FTRLModel<uint64, double> (psg_ftrl.hip): the model is an open-addressing
+// hash table of 128-B buckets, three 40-B entries each, probed bucket to
+// bucket from a mixing hash of the key.  A slot is free while its key word
+// is 0; key 0 itself lives in the side entry of the head block, so every
+// uint64 is a legal key.  Entries are never deleted: the free slots of a
+// probe sequence are always its tail, and a search ends at the first one.
+struct FtrlEntry {
+  uint64_t key, pos, neg;
+  double w, z;
+};
+struct FtrlBucket {
+  FtrlEntry e[3];
+  uint64_t spare;
+};
+static_assert(sizeof(FtrlBucket) == 128, "one bucket = one 128-B line");
+struct FtrlParam {
+  double alpha, beta, lambda1, lambda2;
+};
+constexpr int kFtrlSlots = 256;      // counter slots of 64 B: [0] entries, [1] nnz
+constexpr int kFtrlPartials = 1024;  // norm partials, two doubles each
+// the model's small device block: head, counter slots, norm partials
+struct FtrlHead {
+  unsigned long long verdict;   // order violations of the message in flight
+  unsigned long long err;       // rejected messages not yet reported
+  unsigned long long overflow;  // keys that found no slot (never, by the load limit)
+  unsigned long long side_present;
+  FtrlEntry side;               // the entry of key 0
+  unsigned long long res[5];    // entries, nnz, norm1, norm2 (bits), export count
+  unsigned long long pad[2];
+  unsigned long long slots[kFtrlSlots * 8];
+  double partial[kFtrlPartials * 2];
+};
+struct FtrlTable {
+  FtrlBucket* b;
+  uint64_t mask;  // buckets - 1 (a power of two)
+  FtrlHead* head;
+};
+// one message: order check, then the update, which applies nothing unless
+// the check passed (a rejected message also counts in head->err)
+hipError_t launch_ftrl_push(const FtrlTable& T, const uint64_t* keys, const uint32_t* pos,
+                            const uint32_t* neg, const double* grad, uint64_t n,
+                            const FtrlParam& P, hipStream_t stream);
+hipError_t launch_ftrl_pull(const FtrlTable& T, const uint64_t* keys, uint64_t n, double* out,
+                            hipStream_t stream);
+// any output may be null
+hipError_t launch_ftrl_lookup(const FtrlTable& T, const uint64_t* keys, uint64_t n, uint64_t* pos,
+                              uint64_t* neg, double* w, double* z, uint8_t* found,
+                              hipStream_t stream);
+// every entry of `from` into `to` (zeroed, same head)
+hipError_t launch_ftrl_rehash(const FtrlTable& from, const FtrlTable& to, hipStream_t stream);
+// head->res[0..1] = entries, nnz (the sums of the counter slots)
+hipError_t launch_ftrl_count(const FtrlTable& T, hipStream_t stream);
+// ... and res[2..3] = sum |w|, sum w^2 in a fixed order for a given table
+hipError_t launch_ftrl_norm(const FtrlTable& T, hipStream_t stream);
+// (key, w) of every entry with w != 0, in no particular order, the first
+// cap of them; head->res[4] = their count
+hipError_t launch_ftrl_export(const FtrlTable& T, uint64_t* keys, double* w, uint64_t cap,
+                              hipStream_t stream);
+
 // snappy raw-format decompression (psg_snappy.hip), one wave per message:
 // part i -> dst + doff[i], of dcap[i] bytes (dcap NULL: doff[i+1] - doff[i]).
 // scratch (snappy_scratch_bytes(nmsg), device; NULL: no deferral) holds the
