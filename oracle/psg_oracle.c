@@ -574,8 +574,9 @@ void orc_darling_update_weight(double* value, double* delta, uint8_t* active,
 /* insertKeys / queryKeys (parameter/frequency_filter.h:27-43), restated   */
 /* on a caller-held table of n uint8 counters (n = max(n, 64) and          */
 /* k = min(30, max(1, k)) already applied by the caller, as resize() does).*/
-/* PARITY UNPINNED: src/test/countmin_test.cc is entirely commented out    */
-/* and countmin.h cannot be compiled here (glog via shared_array_inl.h).   */
+/* src/test/countmin_test.cc is entirely commented out; PINNED by          */
+/* countmin.h / frequency_filter.h compiled in place                       */
+/* (oracle/ref_countmin_shim.cc) and their recorded tables.                */
 /* ---------------------------------------------------------------------- */
 static uint32_t cm_hash(uint64_t key) {
   const uint32_t seed = 0xbc9f1d34u, m = 0xc6a4a793u, n = 8;

@@ -12,9 +12,14 @@
  *   - aggregate / gather / evenDivide / murmur key shuffle: the known-answer
  *     constants that SURVEY.md Appendix C records from the reference's own
  *     code; murmur additionally against oracle/_ref (the reference's
- *     src/util/MurmurHash3.cc compiled in place).
- *   The reference's message.h / kv_vector.h cannot be compiled here without
- *   glog/gflags/protobuf/Eigen, so there is no oracle/_ref build of them.
+ *     src/util/MurmurHash3.cc compiled in place);
+ *   - match / oldMatch / sliceKeyOrderedMsg / evenDivide, and through them
+ *     the folds and the gather: the reference's message.h and range.h
+ *     compiled in place (oracle/ref_match_shim.cc over the stand-in headers
+ *     of oracle/standin/) and its recorded outputs
+ *     (tests/golden/reference_pin/, tests/test_reference_pin.py).  The
+ *     per-push loops of kv_vector.h around them stay restated: kv_vector.h
+ *     needs the whole system and is not compiled.
  *
  * Reference quirks are given defined behaviour here:
  *   - a pushed key that is not among the server keys of the position range
@@ -144,7 +149,9 @@ void orc_darling_update_weight(double* value, double* delta, uint8_t* active,
                                double* violation);
 
 /* CountMin<uint64,uint8> insert/query and FreqencyFilter::queryKeys
- * (countmin.h:33-51, frequency_filter.h:27-34), parity unpinned. */
+ * (countmin.h:33-51, frequency_filter.h:27-34); pinned by the reference's
+ * own headers compiled in place (oracle/ref_countmin_shim.cc) and its
+ * recorded tables (tests/test_reference_pin.py). */
 void orc_cm_insert(uint8_t* data, uint32_t n, int k, const uint64_t* keys,
                    const uint32_t* counts, size_t nk);
 uint8_t orc_cm_query(const uint8_t* data, uint32_t n, int k, uint64_t key);

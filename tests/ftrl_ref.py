@@ -12,6 +12,13 @@ base/soft_thresholding.h:7-13):
 
 Both keep the reference's bookkeeping (nnz, the four kinds of weight
 transition) and neither checks its input, as the reference does not.
+
+PINNED: tests/test_reference_pin.py holds both classes, with ``pull``,
+``nonzero`` and ``dump_text``, bit for bit to what the reference's own
+ftrl_model.h (compiled in place, oracle/ref_ftrl_shim.cc) gave on the
+recorded case (tests/golden/reference_pin/ftrl_*.npz) and, where oracle/_ref
+is built, gives on seeded cases.  The norms are not restated here (a defined
+deviation of the product, include/psg.h).
 """
 import math
 

@@ -57,6 +57,10 @@ def orc() -> C.CDLL:
                                                            _p]),
             "orc_old_match_f32": (C.c_int, [_p, _sz, _p, _sz, _p, _u64, _u64, _p,
                                             _psz, _psz, _psz]),
+            "orc_old_match_f64": (C.c_int, [_p, _sz, _p, _sz, _p, _u64, _u64, _p,
+                                            _psz, _psz, _psz]),
+            "orc_match_f32": (None, [_sz, _sz, _p, _p, _p, _sz, _p, C.c_int, C.c_int, _psz]),
+            "orc_match_f64": (None, [_sz, _sz, _p, _p, _p, _sz, _p, C.c_int, C.c_int, _psz]),
             "orc_murmur3_x64_128": (None, [_p, C.c_int, C.c_uint32, _p]),
             "orc_shuffle_keys": (None, [_p, _sz, C.c_uint32, _p]),
             "orc_darling_update_weight": (None, [_p, _p, _p, _sz, _sz, _p, _p, C.c_double,
@@ -121,6 +125,30 @@ def slice_key_ordered(keys, rb, re, sep):
     orc().orc_slice_key_ordered(_a(keys), keys.size, int(rb), int(re), _a(sep),
                                 sep.size, _a(pos), _a(valid))
     return pos, valid[: sep.size - 1]
+
+
+def old_match(D, keys, vals, kb, ke, dtype=np.float32):
+    """oldMatch (message.h:229-267) over key range [kb, ke): (lo, hi, out, matched)."""
+    D, keys = u64(D), u64(keys)
+    vals = np.ascontiguousarray(vals, dtype)
+    out = np.zeros(max(1, D.size), dtype)
+    lo, hi, mt = C.c_size_t(), C.c_size_t(), C.c_size_t()
+    f = orc().orc_old_match_f32 if np.dtype(dtype) == np.float32 else orc().orc_old_match_f64
+    f(_a(D), D.size, _a(keys), keys.size, _a(vals), int(kb), int(ke), _a(out),
+      C.byref(lo), C.byref(hi), C.byref(mt))
+    return lo.value, hi.value, out[: hi.value - lo.value], mt.value
+
+
+def match(D, lo, hi, dst, keys, vals, add, nthreads, dtype=np.float32):
+    """match (message.h:134-226) over positions [lo, hi) of D onto a copy of
+    dst (hi - lo values): (dst, matched)."""
+    D, keys = u64(D), u64(keys)
+    dst = np.array(dst, dtype)
+    vals = np.ascontiguousarray(vals, dtype)
+    mt = C.c_size_t()
+    f = orc().orc_match_f32 if np.dtype(dtype) == np.float32 else orc().orc_match_f64
+    f(lo, hi, _a(D), _a(dst), _a(keys), keys.size, _a(vals), int(add), nthreads, C.byref(mt))
+    return dst, mt.value
 
 
 def aggregate(D, kb, ke, pushes, parallel=False, nthreads=1, dtype=np.float32):

@@ -3,11 +3,13 @@ CountMin<uint64, uint8> (src/parameter/frequency_filter.h:27-43,
 src/base/countmin.h:14-67), as SharedParameter::process drives it
 (shared_parameter.h:114-133).
 
-The oracle (oracle/psg_oracle.c orc_cm_*) is a restatement, PARITY
-UNPINNED: the reference's countmin_test.cc is entirely commented out and
-countmin.h cannot be compiled here (glog through shared_array_inl.h); it is
-checked against an independent pure-Python restatement.  The GPU table is
-compared byte for byte and the filtered keys in order.
+The oracle (oracle/psg_oracle.c orc_cm_*) and the pure-Python form below are
+restatements.  The reference's countmin_test.cc is entirely commented out;
+both are PINNED by the reference's own frequency_filter.h / countmin.h
+compiled in place (oracle/ref_countmin_shim.cc) and by its recorded tables
+and kept keys (tests/golden/reference_pin/countmin.npz,
+tests/test_reference_pin.py).  The GPU table is compared byte for byte and
+the filtered keys in order, against the oracle and against the recording.
 """
 import ctypes as C
 
@@ -301,4 +303,41 @@ def test_gpu_freq_query_binned_vs_oracle(k, nq):
                                            dn.data_ptr(), scratch.data_ptr(), None))
         got = dout[:int(dn.item())].cpu().numpy().view(np.uint64)
         assert np.array_equal(got, O.ff_query(t, nn, kk, q[:m], 3))
+    v.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,k", [(10, 3), (1000, 1), (777, 40), (65537, 4)])
+def test_gpu_freq_filter_against_the_recorded_tables(n, k):
+    """tests/golden/reference_pin/countmin.npz: the table bytes and the kept
+    keys the reference's own FreqencyFilter<uint64> (compiled in place,
+    oracle/ref_countmin_shim.cc) gave, written by tools/record_reference.py."""
+    import torch
+    assert torch.cuda.is_available()
+    import pin_cases as P
+    from parameter_server_amd import _lib
+    meta, fx = P.load_fixture("countmin")
+    tag = "n%d_k%d" % (n, k)
+    info = meta["cases"][tag]
+    c = P.cm_case(n, k)
+    assert info["input_sha256"] == c.digest()
+    v = _ctx()
+    e = C.c_int()
+    _lib.check(v._L.psg_freq_empty(v._h, 1, C.byref(e)))
+    assert bool(e.value) == info["empty_before_resize"]
+    _lib.check(v._L.psg_freq_resize(v._h, 1, n, k))
+    _lib.check(v._L.psg_freq_empty(v._h, 1, C.byref(e)))
+    assert bool(e.value) == info["empty_after_resize"]
+    for keys, counts in c.batches:
+        _lib.check(v._L.psg_freq_insert(v._h, 1, keys.ctypes.data, counts.ctypes.data, keys.size))
+    assert np.array_equal(_table(v, 1, info["n_"]), fx[tag + "_table"])
+    for freq in P.CM_FREQS:
+        mask = np.unpackbits(fx["%s_kept%d" % (tag, freq)])[: c.query.size].astype(bool)
+        want = c.query[mask]
+        assert want.size == info["kept"][str(freq)]["n"]
+        assert P.sha256([want]) == info["kept"][str(freq)]["sha256"]
+        assert np.array_equal(_query(v, 1, c.query, freq), want)
+    _lib.check(v._L.psg_freq_clear(v._h, 1))
+    _lib.check(v._L.psg_freq_empty(v._h, 1, C.byref(e)))
+    assert bool(e.value) == info["empty_after_clear"]
     v.close()

@@ -318,3 +318,130 @@ def test_arguments():
     ref.push(k, a, a, g)
     assert np.array_equal(R.bits(out), R.bits(R.pull(ref, k)))
     L.psg_destroy(h)
+
+
+# ------------------------------------------- against the reference's recording
+# tests/golden/reference_pin/ftrl_*.npz: what the reference's own FTRLModel
+# (compiled in place, oracle/ref_ftrl_shim.cc) held after each of six
+# messages, written by tools/record_reference.py.  The keys are chosen through
+# fmix64's inverse: 60 land in the last bucket of every table and 60 in bucket
+# 0, so chains longer than a bucket that wrap from the last bucket to the
+# first exist in every table the model passes through.
+@pytest.fixture(scope="module")
+def pinned_case():
+    import pin_cases as P
+    c = P.ftrl_case()
+    fixtures = {}
+    for pname in P.FTRL_PARAMS:
+        meta, fx = P.load_fixture("ftrl_" + pname)
+        assert meta["input_sha256"] == c.digest() and meta["param"] == P.FTRL_PARAMS[pname]
+        fixtures[pname] = (meta, fx)
+    return P, c, fixtures
+
+
+NO_REHASH_HINT = 4096  # 4,096 buckets hold 6,144 keys; the six messages push 3,418
+
+
+@pytest.mark.parametrize("mode", ["one_bucket", "no_rehash", "reserve_between", "device_forms"])
+@pytest.mark.parametrize("pname", ["parity", "steep"])
+def test_against_the_recorded_reference_model(pinned_case, tmp_path, pname, mode):
+    import torch
+    P, c, fixtures = pinned_case
+    meta, fx = fixtures[pname]
+    if mode == "no_rehash":
+        # the table's arithmetic (psg_runtime.hip buckets_for): the smallest
+        # power of two whose 3 * nb / 2 slots hold the hint, and no growth while
+        # every key pushed so far fits
+        nb = 1
+        while 3 * nb // 2 < NO_REHASH_HINT:
+            nb *= 2
+        assert sum(m[0].size for m in c.msgs) <= 3 * nb // 2
+        home = P.fmix64(c.keys) & np.uint64(nb - 1)
+        assert int((home == nb - 1).sum()) >= 60 and int((home == 0).sum()) >= 60
+        assert np.isin(c.last_bucket, c.msgs[0][0]).all()
+        # 60 keys of home nb - 1 at 3 per bucket: a chain of >= 20 buckets
+        # starting in the last bucket, so it wraps to bucket 0 and on
+        assert int((home == nb - 1).sum()) // 3 >= 20
+    m = new_model(hint={"one_bucket": 1, "no_rehash": NO_REHASH_HINT}.get(mode, 64),
+                  **P.FTRL_PARAMS[pname])
+    dev = torch.device("cuda:0")
+    side = torch.cuda.Stream()
+
+    def dt(a):
+        a = np.ascontiguousarray(a)
+        view = {8: np.int64, 4: np.int32}[a.dtype.itemsize] if a.dtype.kind == "u" else a.dtype
+        return torch.from_numpy(a.view(view)).to(dev)
+
+    for t, (msg, want) in enumerate(zip(c.msgs, meta["after"])):
+        if mode == "reserve_between":
+            m.reserve([700, 100, 1500, 1500, 5000, 20000][t])
+        if mode == "device_forms":
+            bufs = [dt(a) for a in msg]
+            torch.cuda.synchronize()
+            _lib.check(m._L.psg_ftrl_push_dev(m._h, bufs[0].data_ptr(), msg[0].size, bufs[1].data_ptr(),
+                                              bufs[2].data_ptr(), bufs[3].data_ptr(), side.cuda_stream))
+            side.synchronize()
+        else:
+            assert push(m, *msg) == _lib.PSG_OK
+        rc, e, nz, _, _ = status(m)
+        assert (rc, e, nz) == (_lib.PSG_OK, want["size"], want["nnz"])
+        assert P.entry_digest(*m.lookup(c.keys)) == want["entries_sha256"]
+    pos, neg, w, z, found = m.lookup(c.keys)
+    assert np.array_equal(pos, fx["pos"]) and np.array_equal(neg, fx["neg"])
+    assert np.array_equal(R.bits(w), fx["w"]) and np.array_equal(R.bits(z), fx["z"])
+    assert np.array_equal(found, fx["found"])
+    if mode == "device_forms":
+        tk = dt(c.request)
+        out = torch.full((c.request.size,), 7.0, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize()
+        _lib.check(m._L.psg_ftrl_pull_dev(m._h, tk.data_ptr(), c.request.size, out.data_ptr(),
+                                          side.cuda_stream))
+        side.synchronize()
+        pulled = out.cpu().numpy()
+    else:
+        req = Message(key=c.request)
+        m.getValue(req)
+        pulled = req.value[0]
+    assert np.array_equal(R.bits(pulled), fx["pull"])
+    keep = (fx["found"] == 1) & (fx["w"].view(np.float64) != 0)
+    k, wn = m.export()
+    assert np.array_equal(k, c.keys[keep]) and np.array_equal(R.bits(wn), fx["w"][keep])
+    path = tmp_path / "model.txt"
+    m.writeToFile(str(path))
+    assert path.read_text() == fx["dump_text"].tobytes().decode()
+    m.close()
+
+
+@pytest.mark.parametrize("pname", ["parity", "steep"])
+def test_norms_and_objv_within_the_stated_bound_on_the_recorded_case(pinned_case, pname):
+    """psg_ftrl_status's norms are a defined deviation (a reduction, not the
+    reference's running sums): each lies within entries * 2^-53 * (the exact
+    sum) of it, and objv with them inside the interval that also holds the
+    reference's recorded objv (tests/test_reference_pin.py).  On the recorded
+    messages without the two infinite-gradient keys, whose weights are
+    infinite; every other key's entry is what the reference recorded."""
+    from fractions import Fraction
+    P, c, fixtures = pinned_case
+    meta, fx = fixtures[pname]
+    param = P.FTRL_PARAMS[pname]
+    m = new_model(hint=1, **param)
+    for msg in c.finite_msgs():
+        assert push(m, *msg) == _lib.PSG_OK
+    rest = ~np.isin(c.keys, c.inf_keys)
+    pos, neg, w, z, found = m.lookup(c.keys[rest])
+    assert np.array_equal(R.bits(w), fx["w"][rest]) and np.array_equal(R.bits(z), fx["z"][rest])
+    assert np.array_equal(found, fx["found"][rest])
+    rc, entries, nnz, norm1, norm2 = status(m)
+    assert (rc, entries, nnz) == (_lib.PSG_OK, int(found.sum()), meta["finite_nnz"])
+    wl = w[found == 1].tolist()
+    assert all(math.isfinite(x) for x in wl)
+    s1 = sum(Fraction(abs(x)) for x in wl)
+    s2 = sum(Fraction(x) * Fraction(x) for x in wl)
+    eps = Fraction(entries, 1 << 53)
+    print("norm1 %r (exact %r), norm2 %r (exact %r)" % (norm1, float(s1), norm2, float(s2)))
+    assert abs(Fraction(norm1) - s1) <= eps * s1
+    assert abs(Fraction(norm2) - s2) <= eps * s2
+    lo, hi = P.objv_interval(wl, entries, param["lambda1"], param["lambda2"])
+    ref = float(np.array([int(meta["finite_objv_bits"], 16)], np.uint64).view(np.float64)[0])
+    assert lo <= m.objv() <= hi and lo <= ref <= hi
+    m.close()
