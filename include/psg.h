@@ -511,6 +511,118 @@ int psg_ftrl_lookup(psg_ctx* ctx, const uint64_t* keys, size_t n, uint64_t* pos,
                     double* w, double* z, uint8_t* found);
 
 /* ------------------------------------------------------------------ */
+/* Online worker step: FTRL::updateModel's minibatch loop              */
+/* (src/linear_method/ftrl.cc:88-151) on a minibatch resident in HBM:  */
+/* Localizer (src/base/localizer.h), FTRL::countKeys, Xw = Z * w,      */
+/* LogitLoss (src/linear_method/loss.h:73-85) and grad = Z' * (-y tau).*/
+/* ------------------------------------------------------------------ */
+/* A minibatch is a row-major CSR with global feature ids: offset[rows+1],
+ * index[nnz], value[nnz] (NULL: a binary matrix) and the labels y[rows].
+ * The calls follow ftrl.cc's order: psg_mb_load, psg_mb_uniq (:96),
+ * psg_mb_localize (:113-119), psg_mb_gradient (:128-138); a call ahead of
+ * the one it needs is PSG_ERR_ARG.  A minibatch's calls run in call order
+ * whatever streams they are given (each waits for the previous one's event);
+ * stream == NULL is the context's stream.  Device pointers handed out stay
+ * valid until the next psg_mb_load or psg_mb_destroy.  Buffers are reused
+ * and only grow: after the first minibatch of a given size (and dictionary
+ * of a given size) no call allocates.  The sums of psg_mb_times and
+ * psg_mb_trans_times are the reference's, one rounded multiply and one
+ * rounded add per entry in the reference's order (no float atomics, no
+ * tree), so Xw and a gradient from given coefficients are bit for bit the
+ * reference's.  Destroy a minibatch before its context.
+ * Defined deviations from the reference:
+ *  - a row with no surviving entry gets Xw = +0.0, so loss = log 2 and
+ *    tau = 1/2; the reference skips the row and leaves Xw[i] unwritten
+ *    (sparse_matrix.h:76 over the uninitialised SArray of ftrl.cc:128);
+ *  - ndict == 0 is legal: Z is empty, Xw is all +0.0, and grad / pos / neg
+ *    have length 0; the reference returns a null matrix (localizer.h:114)
+ *    and dereferences it (ftrl.cc:115);
+ *  - objv is a fixed-order device reduction of the per-row losses (a tree
+ *    over each 256 rows, then over those sums): the same bits on every run
+ *    of the same input, within rows * 2^-53 * objv of the exact sum; not
+ *    Eigen's .sum() (loss.h:74), whose order its packet code decides;
+ *  - a dictionary that is not strictly increasing is rejected by a device
+ *    check and reported as PSG_ERR_UNSORTED by psg_mb_gradient or
+ *    psg_mb_read, whichever synchronises next; psg_mb_localize must then be
+ *    called again.  The reference assumes the order without checking
+ *    (localizer.h:21);
+ *  - only LossConfig::LOGIT is built; any other loss id is PSG_ERR_ARG;
+ *  - exp and log are the device's (each within 1 ulp): tau is within 4 ulp
+ *    of the host's and loss within 4 * 2^-52 * max(1, loss). */
+typedef struct psg_minibatch psg_minibatch;
+/* Needs a PSG_F64 context (Real = double, ftrl.h:26; PSG_ERR_ARG otherwise). */
+int psg_mb_create(psg_ctx* ctx, psg_minibatch** mb);
+void psg_mb_destroy(psg_minibatch* mb);
+/* Host arrays, free on return; replaces the previous minibatch.  nnz =
+ * offset[rows] >= 2^32 - 1 is PSG_ERR_SIZE (the CHECK_LT of localizer.h:54),
+ * an offset array that does not start at 0 or decreases PSG_ERR_ARG. */
+int psg_mb_load(psg_minibatch* mb, const uint64_t* offset, size_t rows, const uint64_t* index,
+                const double* value, const double* y);
+/* countUniqIndex (localizer.h:50-87): the sorted unique ids and how often
+ * each occurs.  *n is written after a wait (the caller sizes its filter and
+ * pull by it, as ftrl.cc:102 waits for the filter's reply). */
+int psg_mb_uniq(psg_minibatch* mb, const uint64_t** keys_dev, const uint32_t** cnt_dev,
+                size_t* n);
+/* remapIndex (localizer.h:110-168) and countKeys (ftrl.cc:154-174) against
+ * dict_dev[ndict], the keys the server kept: strictly increasing, and read
+ * again by nothing after this call's kernels.  Enqueues only. */
+int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
+                    const uint32_t** pos_dev, const uint32_t** neg_dev, void* stream);
+/* xw[rows] = Z * x[ndict] (sparse_matrix.h:75-86) and g[ndict] = Z' * c[rows]
+ * (matrix.h:57-58 over sparse_matrix.h:88-104).  Enqueue only. */
+int psg_mb_times(psg_minibatch* mb, const double* x_dev, double* xw_dev, void* stream);
+int psg_mb_trans_times(psg_minibatch* mb, const double* c_dev, double* g_dev, void* stream);
+/* ftrl.cc:128-138: Xw = Z * w, objv = LogitLoss::evaluate (loss.h:74),
+ * grad = Z' * (-y * tau) (loss.h:81-84).  *objv on the host; synchronises. */
+#define PSG_LOSS_LOGIT 0
+int psg_mb_gradient(psg_minibatch* mb, int loss, const double* w_dev, const double** grad_dev,
+                    double* objv, void* stream);
+/* Tests and checkpoints: one internal array to the host, after a wait.  *n =
+ * its element count; PSG_ERR_SIZE (nothing copied) if cap_bytes is short. */
+#define PSG_MB_SORTED_KEY 0  /* uint64[nnz]: the sorted pairs' keys */
+#define PSG_MB_SORTED_POS 1  /* uint32[nnz]: ... and positions (Pair.i) */
+#define PSG_MB_UNIQ_KEY 2    /* uint64[n_uniq] */
+#define PSG_MB_KEY_CNT 3     /* uint32[n_uniq] */
+#define PSG_MB_NEW_OFFSET 4  /* uint64[rows + 1]: Z */
+#define PSG_MB_NEW_INDEX 5   /* uint32[matched] */
+#define PSG_MB_NEW_VALUE 6   /* double[matched], none for a binary matrix */
+#define PSG_MB_POS 7         /* uint32[ndict] */
+#define PSG_MB_NEG 8         /* uint32[ndict] */
+#define PSG_MB_XW 9          /* double[rows] */
+#define PSG_MB_TAU 10        /* double[rows] */
+#define PSG_MB_LOSS 11       /* double[rows] */
+#define PSG_MB_GRAD 12       /* double[ndict] */
+#define PSG_MB_RUN_START 13  /* uint32[n_uniq + 1]: each key's run of sorted pairs */
+#define PSG_MB_REMAPPED 14   /* uint32[nnz]: remapped_idx of localizer.h:123 */
+#define PSG_MB_ROW_OF 15     /* uint32[nnz]: the row of every position */
+#define PSG_MB_SCRATCH 16    /* + slot: uint64[bytes / 8] of psg_mb_scratch */
+int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t* n);
+/* Device blocks that live and grow with the minibatch, for what a worker
+ * keeps between these calls (the kept keys, the pulled weights, the
+ * filter's scratch): slot 0..3, at least `bytes` bytes. */
+int psg_mb_scratch(psg_minibatch* mb, int slot, size_t bytes, void** dev);
+/* Measurement aid (tools/bench_worker.py): with profiling on, a pair of HIP
+ * timing events is recorded around each stage's launches; psg_mb_stage_ms
+ * waits and writes the last run's time of each of the PSG_MB_STAGES stages
+ * in milliseconds (-1: the stage has not run since profiling went on). */
+#define PSG_MB_STAGE_SORT 0        /* (a) the radix passes */
+#define PSG_MB_STAGE_RUNS 1        /* (b) run heads: count, scan, emit */
+#define PSG_MB_STAGE_LOCALIZE 2    /* (c) order check, search, scatter, compaction */
+#define PSG_MB_STAGE_COUNT_KEYS 3  /* (d) */
+#define PSG_MB_STAGE_TIMES 4       /* (e) Xw = Z * w */
+#define PSG_MB_STAGE_LOGIT 5       /* (f) with the objv reduction */
+#define PSG_MB_STAGE_TRANS_TIMES 6 /* (e) grad */
+#define PSG_MB_STAGES 7
+int psg_mb_profile(psg_minibatch* mb, int on);
+int psg_mb_stage_ms(psg_minibatch* mb, double* ms);
+/* The context's stream, which stream == NULL above stands for: what a caller
+ * hands to the psg_ftrl_*_dev and psg_freq_*_dev forms (whose NULL is the
+ * device's default stream) to keep a whole worker step on one stream. */
+int psg_mb_stream(psg_minibatch* mb, void** stream);
+/* Pairs per workgroup of the sort (tests pick their sizes around it). */
+size_t psg_mb_sort_tile(void);
+
+/* ------------------------------------------------------------------ */
 /* Wire ingress: key signatures of the key cache                       */
 /* ------------------------------------------------------------------ */
 /* CRC-32C of device-resident byte segments: out[i] = crc32c::Extend(

@@ -7,4 +7,6 @@ mirror of KVVector for tests and tools, and synthetic workload generators.
 """
 from ._lib import PSGError, lib  # noqa: F401
 
-__all__ = ["PSGError", "lib"]
+from .worker import FTRLWorker, Minibatch  # noqa: F401,E402
+
+__all__ = ["PSGError", "lib", "FTRLWorker", "Minibatch"]

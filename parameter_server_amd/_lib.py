@@ -59,6 +59,13 @@ PSG_NO_CURSOR = 0x800000
 (PSG_KERNEL_TILE, PSG_KERNEL_TILE64, PSG_KERNEL_PACKED, PSG_KERNEL_DENSE, PSG_KERNEL_CURSOR,
  PSG_KERNEL_PACKED_CURSOR) = range(6)
 MAX_VALUE_ARRAYS = 4
+# psg_mb_stage_ms's stages, in order
+MB_STAGES = ("sort", "run_length", "localize", "count_keys", "times", "logit", "trans_times")
+# psg_mb_gradient's loss and psg_mb_read's arrays
+PSG_LOSS_LOGIT = 0
+(PSG_MB_SORTED_KEY, PSG_MB_SORTED_POS, PSG_MB_UNIQ_KEY, PSG_MB_KEY_CNT, PSG_MB_NEW_OFFSET,
+ PSG_MB_NEW_INDEX, PSG_MB_NEW_VALUE, PSG_MB_POS, PSG_MB_NEG, PSG_MB_XW, PSG_MB_TAU, PSG_MB_LOSS,
+ PSG_MB_GRAD, PSG_MB_RUN_START, PSG_MB_REMAPPED, PSG_MB_ROW_OF, PSG_MB_SCRATCH) = range(17)
 
 # Every symbol include/psg.h declares, with its ctypes signature.
 _u64 = C.c_uint64
@@ -179,6 +186,20 @@ SIGNATURES = {
     "psg_ftrl_status": (C.c_int, [_p, _psz, _psz, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "psg_ftrl_export": (C.c_int, [_p, _p, _p, _sz, _psz]),
     "psg_ftrl_lookup": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _p]),
+    "psg_mb_create": (C.c_int, [_p, C.POINTER(_p)]),
+    "psg_mb_destroy": (None, [_p]),
+    "psg_mb_load": (C.c_int, [_p, _p, _sz, _p, _p, _p]),
+    "psg_mb_uniq": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), _psz]),
+    "psg_mb_localize": (C.c_int, [_p, _p, _sz, C.POINTER(_p), C.POINTER(_p), _p]),
+    "psg_mb_times": (C.c_int, [_p, _p, _p, _p]),
+    "psg_mb_trans_times": (C.c_int, [_p, _p, _p, _p]),
+    "psg_mb_gradient": (C.c_int, [_p, C.c_int, _p, C.POINTER(_p), C.POINTER(C.c_double), _p]),
+    "psg_mb_read": (C.c_int, [_p, C.c_int, _p, _sz, _psz]),
+    "psg_mb_scratch": (C.c_int, [_p, C.c_int, _sz, C.POINTER(_p)]),
+    "psg_mb_profile": (C.c_int, [_p, C.c_int]),
+    "psg_mb_stage_ms": (C.c_int, [_p, C.POINTER(C.c_double)]),
+    "psg_mb_stream": (C.c_int, [_p, C.POINTER(_p)]),
+    "psg_mb_sort_tile": (_sz, []),
 }
 
 _LIB = None

@@ -9,6 +9,9 @@
 namespace psg {
 // Records the message for psg_last_error() and returns `code`.
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// The device, value type and stream of a context, for the translation units
+// that work in a context without owning it (psg_worker.hip).
+void ctx_info(psg_ctx* c, int* device, int* dtype, hipStream_t* stream);
 }  // namespace psg
 
 #define HIP_TRY(expr)                                                            \

@@ -1520,6 +1520,12 @@ int set_dev(int d) {
 
 }  // namespace
 
+void psg::ctx_info(psg_ctx* c, int* device, int* dtype, hipStream_t* stream) {
+  *device = c->device;
+  *dtype = c->dtype;
+  *stream = c->stream;
+}
+
 extern "C" {
 
 int psg_abi_version(void) { return PSG_ABI_VERSION; }

@@ -1,0 +1,1204 @@
+// psg_worker.hip -- the worker step of the reference's online solver,
+// FTRL::updateModel (src/linear_method/ftrl.cc:88-151), on one minibatch
+// resident in HBM: Localizer::countUniqIndex and remapIndex
+// (src/base/localizer.h:50-87, 110-168), FTRL::countKeys (ftrl.cc:154-174),
+// Xw = Z * w (src/base/sparse_matrix.h:73-86), LogitLoss::evaluate / compute
+// (src/linear_method/loss.h:73-85) and grad = Z' * (-y tau)
+// (base/matrix.h:57-58 over sparse_matrix.h:87-105).  Kernels first, the
+// psg_mb_* entry points of include/psg.h after them.
+//
+// (a) Sort.  countUniqIndex sorts (key, position) pairs by key
+// (parallelSort over pair_).  Here: a stable LSD radix sort of the 64-bit
+// keys, 8 bits per pass, the position as a 32-bit payload.  One OR / AND
+// reduction over the keys (at load) tells which of the eight digits differ
+// between any two keys; a digit that is the same in every key is not sorted
+// on.  A pass is three launches: per-tile digit counts (digit-major), one
+// workgroup per digit scanning its row of tile counts, and the scatter.  A
+// tile is 2048 consecutive pairs; wave w of the workgroup owns the w-th
+// quarter of it and walks it 64 pairs at a time, so "earlier in the input"
+// is "(wave, step, lane) smaller".  A pair's place among the equal digits of
+// its step comes from eight ballots (the lanes that agree on every bit of
+// the digit), its place among the wave's earlier steps from a per-wave LDS
+// counter that the last lane of each group of equal digits advances, and
+// the waves' counters are prefixed across the workgroup: no atomics, and
+// the order of equal keys is the input order.  Stability is what makes the
+// sorted positions the transpose (CSC) of the minibatch: inside a key's run
+// they ascend, that is row after row and in the row's own order.
+//
+// (b) Run heads of the sorted keys, counted per tile, scanned, then emitted:
+// uniq_key, run_start, and run_of (the run of every sorted pair).
+// (c) One binary search of the dictionary per run; every pair then takes its
+// run's rank + 1 (0: dropped) to its position; a second count / scan / emit
+// over the positions compacts the survivors into Z in row order.
+// (d) One lane per sorted pair; neighbours of one run fold their counts with
+// ballots and one lane adds them to the key's counters (integer atomics).
+// (e) times: one lane per row of Z.  trans_times: the term of every sorted
+// pair first (all the gathers, in parallel), then one lane per dictionary key
+// adds its run's terms in order; a run longer than kLongRun is taken by a
+// whole wave instead (the long runs are listed at localize): 64 terms per
+// load, several loads ahead, laid out in LDS and added one after the other
+// into one accumulator, so the add chain is the reference's and only the
+// loads are parallel.  No float atomics, no tree.
+// (f) tau, c = -y tau and loss per row as loss.h:74,81 writes them; objv by
+// a tree inside each workgroup of 256 rows and a second, single workgroup
+// over the partials: the order depends on `rows` alone.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "../../include/psg.h"
+#include "psg_host.h"
+#include "psg_internal.h"
+
+namespace psg {
+namespace {
+
+#ifndef PSG_SORT_KPT
+#define PSG_SORT_KPT 8  // A/B builds: 4, 16, 32
+#endif
+#ifndef PSG_LONG_RUN
+#define PSG_LONG_RUN 32  // A/B builds: 8, 256
+#endif
+constexpr int kSortKPT = PSG_SORT_KPT;           // pairs per lane per tile
+constexpr uint32_t kSortTile = 256 * kSortKPT;   // pairs per workgroup
+constexpr uint32_t kWaveSpan = 64 * kSortKPT;    // pairs per wave
+constexpr uint32_t kLongGrid = 1024;             // workgroups (of 4 waves) over the long runs
+constexpr uint32_t kFlagTile = 2048;             // elements per workgroup of the flag scans
+constexpr uint32_t kLongRun = PSG_LONG_RUN;      // runs longer than this go to the whole wave
+
+// XCD-contiguous runs of consecutive tiles (as psg_countmin.hip): tiles next
+// to each other write next to each other in every digit's output range, and
+// their partial lines meet in one XCD's L2
+__device__ __forceinline__ uint32_t xcd_index(uint32_t b, uint32_t n) {
+  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
+  return x * q + (x < r ? x : r) + j;
+}
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
+  for (uint32_t s = 1; s < 64; s <<= 1) {
+    const uint32_t u = __shfl_up(v, s, 64);
+    if (lane >= s) v += u;
+  }
+  return v;
+}
+
+// exclusive scan of v over the 256 lanes of the workgroup; ws: 4 LDS words
+__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* ws, uint32_t* total) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t inc = wave_incl_scan(v, lane);
+  __syncthreads();
+  if (lane == 63) ws[w] = inc;
+  __syncthreads();
+  uint32_t b = 0, t = 0;
+  for (uint32_t i = 0; i < 4; ++i) {
+    const uint32_t x = ws[i];
+    if (i < w) b += x;
+    t += x;
+  }
+  *total = t;
+  return b + inc - v;
+}
+
+// the valid lanes of the wave whose digit equals this lane's
+__device__ __forceinline__ uint64_t match_digit(uint32_t d, bool valid) {
+  uint64_t m = __ballot(valid);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const bool bit = (d >> b) & 1u;
+    const uint64_t bal = __ballot(bit);
+    m &= bit ? bal : ~bal;
+  }
+  return m;
+}
+
+// ---- (a) ------------------------------------------------------------------
+// orand[0] |= every key, orand[1] &= every key
+__global__ __launch_bounds__(256) void key_bits_kernel(const uint64_t* __restrict__ keys,
+                                                       uint32_t n,
+                                                       unsigned long long* __restrict__ orand) {
+  uint64_t o = 0, a = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n;
+       i += (uint64_t)gridDim.x * 256u) {
+    const uint64_t k = keys[i];
+    o |= k;
+    a &= k;
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    o |= __shfl_xor(o, s, 64);
+    a &= __shfl_xor(a, s, 64);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    atomicOr(orand, (unsigned long long)o);
+    atomicAnd(orand + 1, (unsigned long long)a);
+  }
+}
+
+// counts[d * ntiles + t] = pairs of tile t whose digit is d
+__global__ __launch_bounds__(256) void sort_count_kernel(const uint64_t* __restrict__ keys,
+                                                         uint32_t n, int shift,
+                                                         uint32_t* __restrict__ counts,
+                                                         uint32_t ntiles) {
+  __shared__ uint32_t h[256];
+  const uint32_t t = xcd_index(blockIdx.x, gridDim.x);
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)t * kSortTile + (uint64_t)w * kWaveSpan + lane;
+#pragma unroll 4
+  for (int j = 0; j < kSortKPT; ++j) {
+    const uint64_t i = base + (uint64_t)j * 64u;
+    const bool valid = i < n;
+    const uint32_t d = valid ? (uint32_t)(keys[i] >> shift) & 255u : 0u;
+    const uint64_t m = match_digit(d, valid);
+    if (valid && (m & ((1ull << lane) - 1)) == 0)  // first lane of its group
+      atomicAdd(&h[d], (uint32_t)__popcll(m));
+  }
+  __syncthreads();
+  counts[(size_t)threadIdx.x * ntiles + t] = h[threadIdx.x];
+}
+
+// workgroup r: c[r * n .. + n) becomes its exclusive scan, total[r] its sum
+__global__ __launch_bounds__(256) void row_scan_kernel(uint32_t* __restrict__ c, uint32_t n,
+                                                       uint32_t* __restrict__ total) {
+  __shared__ uint32_t ws[4];
+  uint32_t* row = c + (size_t)blockIdx.x * n;
+  uint32_t carry = 0;
+  for (uint32_t b = 0; b < n; b += 256) {
+    const uint32_t i = b + threadIdx.x;
+    const uint32_t v = i < n ? row[i] : 0u;
+    uint32_t tot;
+    const uint32_t ex = block_exscan(v, ws, &tot);
+    if (i < n) row[i] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) total[blockIdx.x] = carry;
+}
+
+// pin null: the positions are 0 .. n-1 (the first pass)
+__global__ __launch_bounds__(256) void sort_scatter_kernel(
+    const uint64_t* __restrict__ kin, const uint32_t* __restrict__ pin, uint64_t* __restrict__ kout,
+    uint32_t* __restrict__ pout, uint32_t n, int shift, const uint32_t* __restrict__ counts,
+    const uint32_t* __restrict__ dtotal, uint32_t ntiles) {
+  __shared__ uint32_t cnt[4][256];
+  __shared__ uint32_t dbase[256];
+  __shared__ uint32_t ws[4];
+  const uint32_t t = xcd_index(blockIdx.x, gridDim.x);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+  for (int i = 0; i < 4; ++i) cnt[i][tid] = 0;
+  {  // first output index of digit `tid` for this tile
+    uint32_t tot;
+    const uint32_t ex = block_exscan(dtotal[tid], ws, &tot);
+    dbase[tid] = ex + counts[(size_t)tid * ntiles + t];
+  }
+  __syncthreads();
+  // The wave's counters are read by every lane and then advanced by one lane
+  // per group.  LDS operations of one wave run in order, so a step reads
+  // what the step before wrote; volatile keeps the compiler from carrying a
+  // counter in a register across steps.
+  volatile uint32_t* mine = cnt[w];
+  const uint64_t base = (uint64_t)t * kSortTile + (uint64_t)w * kWaveSpan + lane;
+  uint64_t key[kSortKPT];
+  uint32_t off[kSortKPT];
+#pragma unroll
+  for (int j = 0; j < kSortKPT; ++j) {
+    const uint64_t i = base + (uint64_t)j * 64u;
+    const bool valid = i < n;
+    key[j] = valid ? kin[i] : 0;
+    const uint32_t d = (uint32_t)(key[j] >> shift) & 255u;
+    const uint64_t m = match_digit(d, valid);
+    const uint32_t before = mine[d];  // the wave's earlier steps
+    const uint32_t below = (uint32_t)__popcll(m & ((1ull << lane) - 1));
+    const uint32_t group = (uint32_t)__popcll(m);
+    __builtin_amdgcn_wave_barrier();
+    if (valid && below + 1 == group) mine[d] = before + group;  // last lane of the group
+    __builtin_amdgcn_wave_barrier();
+    off[j] = before + below;
+  }
+  __syncthreads();
+  {  // the waves' totals of digit `tid` become their exclusive prefix
+    uint32_t run = 0;
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t x = cnt[i][tid];
+      cnt[i][tid] = run;
+      run += x;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < kSortKPT; ++j) {
+    const uint64_t i = base + (uint64_t)j * 64u;
+    if (i < n) {
+      const uint32_t d = (uint32_t)(key[j] >> shift) & 255u;
+      const uint32_t dst = dbase[d] + cnt[w][d] + off[j];
+      if (dst < n) {  // always, by the counts; keeps a bad count in bounds
+        kout[dst] = key[j];
+        pout[dst] = pin ? pin[i] : (uint32_t)i;
+      }
+    }
+  }
+}
+
+// no digit differs: the input order is the sorted order
+__global__ __launch_bounds__(256) void sort_identity_kernel(const uint64_t* __restrict__ kin,
+                                                            uint64_t* __restrict__ kout,
+                                                            uint32_t* __restrict__ pout,
+                                                            uint32_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i < n) {
+    kout[i] = kin[i];
+    pout[i] = (uint32_t)i;
+  }
+}
+
+// ---- flag scans: (b) and the compaction of (c) -----------------------------
+// A lane owns 8 consecutive elements of a 2048-element tile.
+struct HeadFlag {  // element i starts a run of the sorted keys
+  const uint64_t* k;
+  __device__ bool operator()(uint32_t i) const { return i == 0 || k[i] != k[i - 1]; }
+};
+struct KeptFlag {  // position i survives the dictionary
+  const uint32_t* remapped;
+  __device__ bool operator()(uint32_t i) const { return remapped[i] != 0; }
+};
+
+template <class Flag>
+__global__ __launch_bounds__(256) void flag_count_kernel(Flag f, uint32_t n,
+                                                         uint32_t* __restrict__ tile_sum) {
+  __shared__ uint32_t ws[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * kFlagTile + threadIdx.x * 8u;
+  uint32_t c = 0;
+  for (uint32_t j = 0; j < 8; ++j)
+    if (i0 + j < n) c += f((uint32_t)(i0 + j)) ? 1u : 0u;
+  uint32_t tot;
+  (void)block_exscan(c, ws, &tot);
+  if (threadIdx.x == 0) tile_sum[blockIdx.x] = tot;
+}
+
+struct HeadEmit {  // ex: run heads before element i
+  const uint64_t* k;
+  uint64_t* uniq_key;
+  uint32_t* run_start;  // [n_uniq + 1]
+  uint32_t* run_of;     // [n]
+  __device__ void operator()(uint32_t i, uint32_t ex, bool head, uint32_t n) const {
+    if (head) {
+      uniq_key[ex] = k[i];
+      run_start[ex] = i;
+    }
+    const uint32_t after = ex + (head ? 1u : 0u);
+    run_of[i] = after - 1;  // i == 0 is a head: after >= 1
+    if (i == n - 1) run_start[after] = n;
+  }
+};
+struct KeptEmit {  // ex: survivors before position i
+  const uint32_t* remapped;
+  const double* value;  // null: binary
+  uint32_t* before;     // [n + 1]
+  uint32_t* new_index;
+  double* new_value;
+  __device__ void operator()(uint32_t i, uint32_t ex, bool kept, uint32_t n) const {
+    before[i] = ex;
+    if (kept) {
+      new_index[ex] = remapped[i] - 1;
+      if (value) new_value[ex] = value[i];
+    }
+    if (i == n - 1) before[n] = ex + (kept ? 1u : 0u);
+  }
+};
+
+template <class Flag, class Emit>
+__global__ __launch_bounds__(256) void flag_emit_kernel(Flag f, Emit e, uint32_t n,
+                                                        const uint32_t* __restrict__ tile_base) {
+  __shared__ uint32_t ws[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * kFlagTile + threadIdx.x * 8u;
+  bool fl[8];
+  uint32_t c = 0;
+  for (uint32_t j = 0; j < 8; ++j) {
+    fl[j] = i0 + j < n && f((uint32_t)(i0 + j));
+    c += fl[j] ? 1u : 0u;
+  }
+  uint32_t tot;
+  uint32_t ex = tile_base[blockIdx.x] + block_exscan(c, ws, &tot);
+  for (uint32_t j = 0; j < 8; ++j)
+    if (i0 + j < n) {
+      e((uint32_t)(i0 + j), ex, fl[j], n);
+      ex += fl[j] ? 1u : 0u;
+    }
+}
+
+__global__ __launch_bounds__(256) void key_cnt_kernel(const uint32_t* __restrict__ run_start,
+                                                      uint32_t n_uniq,
+                                                      uint32_t* __restrict__ key_cnt) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (r < n_uniq) key_cnt[r] = run_start[r + 1] - run_start[r];
+}
+
+// the row of every position: offset[row] <= i < offset[row + 1]
+__global__ __launch_bounds__(256) void row_of_kernel(const uint64_t* __restrict__ offset,
+                                                     uint32_t rows, uint32_t n,
+                                                     uint32_t* __restrict__ row_of) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t lo = 0, hi = rows;  // the last row in [lo, hi) with offset[row] <= i
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (offset[mid] <= i) {
+      lo = mid;
+    } else {
+      hi = mid;
+    }
+  }
+  row_of[i] = lo;
+}
+
+// ---- (c) --------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dict_check_kernel(const uint64_t* __restrict__ dict,
+                                                         uint32_t ndict,
+                                                         unsigned long long* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x + 1;
+  if (i < ndict && dict[i - 1] >= dict[i]) atomicAdd(bad, 1ull);
+}
+
+// run r: rank + 1 of its key in the dictionary (0: absent), and the run of
+// every dictionary key that has one (dict_run preset to all ones: none)
+__global__ __launch_bounds__(256) void run_search_kernel(const uint64_t* __restrict__ uniq_key,
+                                                         uint32_t n_uniq,
+                                                         const uint64_t* __restrict__ dict,
+                                                         uint32_t ndict,
+                                                         uint32_t* __restrict__ run_rank,
+                                                         uint32_t* __restrict__ dict_run) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (r >= n_uniq) return;
+  const uint64_t key = uniq_key[r];
+  uint32_t lo = 0, hi = ndict;  // first index with dict[index] >= key
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (dict[mid] < key) {
+      lo = mid + 1;
+    } else {
+      hi = mid;
+    }
+  }
+  const bool found = lo < ndict && dict[lo] == key;
+  run_rank[r] = found ? lo + 1 : 0u;
+  if (found) dict_run[lo] = (uint32_t)r;
+}
+
+// remapped[position] = rank + 1 of the pair's run (localizer.h:123-136)
+__global__ __launch_bounds__(256) void remap_kernel(const uint32_t* __restrict__ spos,
+                                                    const uint32_t* __restrict__ run_of,
+                                                    const uint32_t* __restrict__ run_rank,
+                                                    uint32_t n, uint32_t n_uniq,
+                                                    uint32_t* __restrict__ remapped) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t r = run_of[i], p = spos[i];
+  if (r < n_uniq && p < n) remapped[p] = run_rank[r];
+}
+
+__global__ __launch_bounds__(256) void new_offset_kernel(const uint64_t* __restrict__ offset,
+                                                         const uint32_t* __restrict__ before,
+                                                         uint32_t rows,
+                                                         uint64_t* __restrict__ new_offset) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (r <= rows) new_offset[r] = before[offset[r]];
+}
+
+// ---- (d), (e) -----------------------------------------------------------------
+// the run [*b, *e) of sorted pairs of dictionary key k (empty: none)
+__device__ __forceinline__ void run_of_key(uint64_t k, uint32_t ndict,
+                                           const uint32_t* __restrict__ dict_run,
+                                           const uint32_t* __restrict__ run_start,
+                                           uint32_t n_uniq, uint32_t n, uint32_t* b,
+                                           uint32_t* e) {
+  *b = *e = 0;
+  if (k < ndict) {
+    const uint32_t r = dict_run[k];
+    if (r < n_uniq) {  // all ones (no run) fails this
+      const uint32_t hi = run_start[r + 1] < n ? run_start[r + 1] : n;
+      *e = hi;
+      *b = run_start[r] < hi ? run_start[r] : hi;
+    }
+  }
+}
+
+// the row of sorted pair i (a position past the minibatch, which a correct
+// sort never yields, reads row 0 instead of memory it does not own)
+__device__ __forceinline__ uint32_t pair_row(const uint32_t* __restrict__ spos,
+                                             const uint32_t* __restrict__ row_of, uint64_t i,
+                                             uint32_t n, uint32_t* p) {
+  *p = spos[i];
+  if (*p >= n) *p = 0;
+  return row_of[*p];
+}
+
+// countKeys (ftrl.cc:164-173): y > 0 is positive, everything else negative.
+// One lane per sorted pair; the lanes of a wave that share a run (they are
+// neighbours: the pairs are sorted) fold their two counts with ballots, and
+// the first lane of each such group adds them to its key's counters (integer
+// atomics: exact in any order).  pos / neg zeroed before.
+__global__ __launch_bounds__(256) void count_keys_kernel(
+    const uint32_t* __restrict__ spos, const uint32_t* __restrict__ row_of,
+    const double* __restrict__ y, const uint32_t* __restrict__ run_of,
+    const uint32_t* __restrict__ run_rank, uint32_t n, uint32_t n_uniq, uint32_t ndict,
+    uint32_t* __restrict__ pos, uint32_t* __restrict__ neg) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  const bool valid = i < n;
+  const uint32_t r = valid ? run_of[i] : 0xffffffffu;
+  bool positive = false;
+  if (valid) {
+    uint32_t at;
+    positive = y[pair_row(spos, row_of, i, n, &at)] > 0;
+  }
+  const uint32_t rprev = __shfl_up(r, 1, 64);
+  const bool head = valid && (lane == 0 || r != rprev);
+  const uint64_t heads = __ballot(head), posb = __ballot(positive), val = __ballot(valid);
+  if (head) {
+    const uint64_t above = heads & ~((2ull << lane) - 1);  // the groups after this one
+    const int end = above ? __ffsll((unsigned long long)above) - 1 : 64;
+    const uint64_t upto = end == 64 ? ~0ull : (1ull << end) - 1;
+    const uint64_t seg = upto & ~((1ull << lane) - 1) & val;
+    const uint32_t cp = (uint32_t)__popcll(seg & posb), cn = (uint32_t)__popcll(seg) - cp;
+    const uint32_t rank = r < n_uniq ? run_rank[r] : 0u;
+    if (rank != 0 && rank <= ndict) {
+      if (cp) atomicAdd(&pos[rank - 1], cp);
+      if (cn) atomicAdd(&neg[rank - 1], cn);
+    }
+  }
+}
+
+// the dictionary keys whose runs are longer than kLongRun, in no particular
+// order (what each gives does not depend on it): one wave each in (e)
+__global__ __launch_bounds__(256) void long_runs_kernel(
+    const uint32_t* __restrict__ dict_run, uint32_t ndict, const uint32_t* __restrict__ run_start,
+    uint32_t n_uniq, uint32_t n, uint32_t* __restrict__ long_list, uint32_t* __restrict__ count) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  uint32_t b, e;
+  run_of_key(k, ndict, dict_run, run_start, n_uniq, n, &b, &e);
+  if (e - b > kLongRun) {
+    const uint32_t at = atomicAdd(count, 1u);
+    if (at < ndict) long_list[at] = (uint32_t)k;
+  }
+}
+
+// times, row-major (sparse_matrix.h:75-86): one lane per row of Z
+__global__ __launch_bounds__(256) void times_kernel(const uint64_t* __restrict__ new_offset,
+                                                    const uint32_t* __restrict__ new_index,
+                                                    const double* __restrict__ new_value,
+                                                    uint32_t rows, const double* __restrict__ x,
+                                                    double* __restrict__ xw) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= rows) return;
+  const uint64_t b = new_offset[i], e = new_offset[i + 1];
+  double acc = 0.0;
+  if (new_value) {
+    for (uint64_t j = b; j < e; ++j) acc = acc + x[new_index[j]] * new_value[j];
+  } else {
+    for (uint64_t j = b; j < e; ++j) acc = acc + x[new_index[j]];
+  }
+  xw[i] = acc;  // an empty row: +0.0 (the reference leaves it unwritten, :76)
+}
+
+// transTimes (sparse_matrix.h:88-104 on the transpose): g[k] over key k's run
+// in ascending position.  Three launches: the term of every sorted pair (all
+// the gathers, fully parallel), then the ordered sums over the terms, which
+// now lie in run order: one lane per key for runs up to kLongRun, one wave
+// per key for the longer ones.
+__global__ __launch_bounds__(256) void terms_kernel(const uint32_t* __restrict__ spos,
+                                                    const uint32_t* __restrict__ row_of,
+                                                    const double* __restrict__ value,
+                                                    const double* __restrict__ c, uint32_t n,
+                                                    double* __restrict__ term) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t p;
+  const uint32_t row = pair_row(spos, row_of, i, n, &p);
+  term[i] = value ? c[row] * value[p] : c[row];
+}
+
+__global__ __launch_bounds__(256) void trans_times_short_kernel(
+    const uint32_t* __restrict__ dict_run, uint32_t ndict, const uint32_t* __restrict__ run_start,
+    uint32_t n_uniq, uint32_t n, const double* __restrict__ term, double* __restrict__ g) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (k >= ndict) return;
+  uint32_t b, e;
+  run_of_key(k, ndict, dict_run, run_start, n_uniq, n, &b, &e);
+  if (e - b > kLongRun) return;  // trans_times_long_kernel's
+  double acc = 0.0;
+  for (uint32_t i = b; i < e; ++i) acc = acc + term[i];
+  g[k] = acc;
+}
+
+// ((0 + t[lb]) + t[lb + 1]) + ... + t[le - 1], the same in every lane: the
+// wave loads kChainAhead x 64 terms ahead of the ones it is adding, lays the
+// current ones out in its LDS block `stage` and adds them from there one
+// after the other into one accumulator (every lane reads the same word: a
+// broadcast).  Reading them out of the lanes' registers instead costs twice
+// the time.  LDS operations of one wave run in order; the
+// fences keep the compiler from moving the reads across the writes.
+#ifndef PSG_CHAIN_AHEAD
+#define PSG_CHAIN_AHEAD 8  // A/B builds: 1, 4
+#endif
+constexpr int kChainAhead = PSG_CHAIN_AHEAD;
+__device__ __forceinline__ double chain_sum(const double* __restrict__ term, uint32_t lb,
+                                            uint32_t le, uint32_t lane,
+                                            double* stage) {
+  double a = 0.0, cur[kChainAhead], nxt[kChainAhead];
+#pragma unroll
+  for (int u = 0; u < kChainAhead; ++u) {
+    const uint64_t i = (uint64_t)lb + (uint64_t)u * 64u + lane;
+    cur[u] = i < le ? term[i] : 0.0;
+    nxt[u] = 0.0;
+  }
+  for (uint64_t base = lb; base < le; base += 64u * kChainAhead) {
+    const uint64_t ahead = base + 64u * kChainAhead;
+    if (ahead < le) {
+#pragma unroll
+      for (int u = 0; u < kChainAhead; ++u) {
+        const uint64_t i = ahead + (uint64_t)u * 64u + lane;
+        nxt[u] = i < le ? term[i] : 0.0;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int u = 0; u < kChainAhead; ++u) stage[u * 64 + lane] = cur[u];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (le - base >= 64u * kChainAhead) {
+#pragma unroll 64
+      for (int j = 0; j < 64 * kChainAhead; ++j) a = a + stage[j];
+    } else {
+      const int cnt = (int)(le - base);
+      for (int j = 0; j < cnt; ++j) a = a + stage[j];
+    }
+#pragma unroll
+    for (int u = 0; u < kChainAhead; ++u) cur[u] = nxt[u];
+  }
+  return a;
+}
+
+// wave w of the launch takes long_list[w], [w + waves], ...
+__global__ __launch_bounds__(256) void trans_times_long_kernel(
+    const uint32_t* __restrict__ long_list, const uint32_t* __restrict__ count,
+    const uint32_t* __restrict__ dict_run, uint32_t ndict, const uint32_t* __restrict__ run_start,
+    uint32_t n_uniq, uint32_t n, const double* __restrict__ term, double* __restrict__ g) {
+  __shared__ double stage[4][64 * kChainAhead];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
+  const uint32_t nl = *count < ndict ? *count : ndict;
+  for (uint32_t j = wave; j < nl; j += waves) {
+    const uint32_t k = long_list[j];
+    uint32_t b, e;
+    run_of_key(k, ndict, dict_run, run_start, n_uniq, n, &b, &e);
+    b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+    e = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);
+    const double a = chain_sum(term, b, e, lane, stage[threadIdx.x >> 6]);
+    if (lane == 0 && k < ndict) g[k] = a;
+  }
+}
+
+// ---- (f) ------------------------------------------------------------------------
+// loss.h:74,81 as written; partial[workgroup] = the tree sum of its 256 losses
+__global__ __launch_bounds__(256) void logit_kernel(const double* __restrict__ y,
+                                                    const double* __restrict__ xw, uint32_t rows,
+                                                    double* __restrict__ tau,
+                                                    double* __restrict__ c,
+                                                    double* __restrict__ loss,
+                                                    double* __restrict__ partial) {
+  __shared__ double s[256];
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  double l = 0.0;
+  if (i < rows) {
+    const double yi = y[i], x = xw[i];
+    const double t = 1 / (1 + exp(yi * x));
+    l = log(1 + exp(-yi * x));
+    tau[i] = t;
+    c[i] = -yi * t;
+    loss[i] = l;
+  }
+  s[threadIdx.x] = l;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
+}
+
+// lane t adds partials t, t + 256, ... one after the other; then the tree
+__global__ __launch_bounds__(256) void objv_kernel(const double* __restrict__ partial,
+                                                   uint32_t nparts, double* __restrict__ objv) {
+  __shared__ double s[256];
+  double a = 0.0;
+  for (uint32_t p = threadIdx.x; p < nparts; p += 256) a += partial[p];
+  s[threadIdx.x] = a;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *objv = s[0];
+}
+
+inline uint32_t blocks_of(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
+
+}  // namespace
+}  // namespace psg
+
+// ------------------------------------------------------------------- host --
+using psg::fail;
+
+namespace {
+
+enum BufId {
+  B_OFFSET, B_INDEX, B_VALUE, B_Y, B_KEY_A, B_KEY_B, B_POS_A, B_POS_B, B_COUNTS, B_TILE_SUM,
+  B_UNIQ_KEY, B_KEY_CNT, B_RUN_START, B_RUN_OF, B_ROW_OF, B_RUN_RANK, B_REMAPPED, B_BEFORE,
+  B_NEW_OFFSET, B_NEW_INDEX, B_NEW_VALUE, B_DICT_RUN, B_CNT_POS, B_CNT_NEG, B_XW, B_TAU, B_C,
+  B_LOSS, B_PARTIAL, B_GRAD, B_TERM, B_LONG_LIST, B_SCRATCH0, B_SCRATCH1, B_SCRATCH2, B_SCRATCH3, B_COUNT
+};
+
+// device words: [0] OR of the keys, [1] AND, [2] dictionary order violations,
+// [3] objv, [4] as two u32: n_uniq, survivors, [5] as u32: long runs; then
+// the 256 digit totals
+constexpr size_t kSmallBytes = 6 * 8 + 256 * 4;
+
+enum State { S_NEW = 0, S_LOADED, S_UNIQ, S_LOCAL, S_GRAD };
+
+}  // namespace
+
+struct psg_minibatch {
+  psg_ctx* ctx = nullptr;
+  int device = 0;
+  hipStream_t stream = nullptr;  // the context's
+  hipEvent_t ev = nullptr;       // the last enqueue, for calls on another stream
+  hipStream_t last_s = nullptr;
+  int state = S_NEW;
+  size_t rows = 0, nnz = 0, n_uniq = 0, ndict = 0;
+  bool binary = false;
+  uint64_t differ = 0;  // the key bits that differ between some two keys
+  const uint64_t* skey = nullptr;  // the sorted pairs (one side of the ping-pong)
+  const uint32_t* spos = nullptr;
+  struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;
+  } b[B_COUNT];
+  size_t scratch_len[4] = {0, 0, 0, 0};
+  unsigned long long* d_small = nullptr;
+  unsigned long long* h_small = nullptr;  // pinned, 8 words
+  // psg_mb_profile: a pair of timing events around each stage's launches
+  bool prof = false;
+  hipEvent_t tev[2 * PSG_MB_STAGES] = {};
+  bool tset[2 * PSG_MB_STAGES] = {};
+  void tick(int stage, int end, hipStream_t s) {
+    const int i = 2 * stage + end;
+    if (prof && tev[i] && hipEventRecord(tev[i], s) == hipSuccess) tset[i] = true;
+  }
+
+  template <class T>
+  T* at(int id) const {
+    return (T*)b[id].p;
+  }
+  uint32_t* d_u32(int word) const { return (uint32_t*)(d_small + 4) + word; }
+  uint32_t* d_dtotal() const { return (uint32_t*)(d_small + 6); }
+
+  // Buffers only grow.  Growing one frees the old block, which waits for the
+  // device, so nothing in flight can still use it.
+  int need(int id, size_t bytes) {
+    if (bytes <= b[id].cap) return PSG_OK;
+    if (b[id].p) HIP_TRY(hipFree(b[id].p));
+    b[id].p = nullptr;
+    b[id].cap = 0;
+    const size_t cap = (bytes + 4095) / 4096 * 4096;
+    HIP_TRY(hipMalloc(&b[id].p, cap));
+    b[id].cap = cap;
+    return PSG_OK;
+  }
+  int order(hipStream_t s) {
+    if (last_s && last_s != s) HIP_TRY(hipStreamWaitEvent(s, ev, 0));
+    return PSG_OK;
+  }
+  int mark(hipStream_t s) {
+    HIP_TRY(hipEventRecord(ev, s));
+    last_s = s;
+    return PSG_OK;
+  }
+  // everything enqueued for this minibatch, on whatever stream, has run
+  int settle() {
+    if (last_s && last_s != stream) HIP_TRY(hipStreamSynchronize(last_s));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PSG_OK;
+  }
+  hipStream_t pick(void* s) const { return s ? (hipStream_t)s : stream; }
+};
+
+namespace {
+
+using namespace psg;
+
+#define LAUNCH(kernel, grid, s, ...) \
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, __VA_ARGS__)
+
+int launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(PSG_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+  return PSG_OK;
+}
+
+// (a): the sorted pairs end in mb->skey / mb->spos
+int enqueue_sort(psg_minibatch* mb, hipStream_t s) {
+  const uint32_t n = (uint32_t)mb->nnz, ntiles = blocks_of(n, kSortTile);
+  const uint64_t* kin = mb->at<uint64_t>(B_INDEX);
+  const uint32_t* pin = nullptr;
+  uint64_t* kout = mb->at<uint64_t>(B_KEY_A);
+  uint32_t* pout = mb->at<uint32_t>(B_POS_A);
+  uint32_t* counts = mb->at<uint32_t>(B_COUNTS);
+  bool any = false;
+  for (int d = 0; d < 8; ++d) {
+    if (((mb->differ >> (8 * d)) & 255u) == 0) continue;  // the same digit in every key
+    LAUNCH(sort_count_kernel, ntiles, s, kin, n, 8 * d, counts, ntiles);
+    LAUNCH(row_scan_kernel, 256, s, counts, ntiles, mb->d_dtotal());
+    LAUNCH(sort_scatter_kernel, ntiles, s, kin, pin, kout, pout, n, 8 * d, counts,
+           mb->d_dtotal(), ntiles);
+    kin = kout;
+    pin = pout;
+    const bool to_b = kout == mb->at<uint64_t>(B_KEY_A);
+    kout = mb->at<uint64_t>(to_b ? B_KEY_B : B_KEY_A);
+    pout = mb->at<uint32_t>(to_b ? B_POS_B : B_POS_A);
+    any = true;
+  }
+  if (!any) {
+    LAUNCH(sort_identity_kernel, blocks_of(n, 256), s, kin, kout, pout, n);
+    pin = pout;
+    kin = kout;
+  }
+  mb->skey = kin;
+  mb->spos = pin;
+  return launched("sort");
+}
+
+size_t elem_size(int what) {
+  switch (what) {
+    case PSG_MB_SORTED_POS:
+    case PSG_MB_KEY_CNT:
+    case PSG_MB_NEW_INDEX:
+    case PSG_MB_POS:
+    case PSG_MB_NEG:
+    case PSG_MB_RUN_START:
+    case PSG_MB_REMAPPED:
+    case PSG_MB_ROW_OF:
+      return 4;
+    default:
+      return 8;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t psg_mb_sort_tile(void) { return kSortTile; }
+
+int psg_mb_create(psg_ctx* ctx, psg_minibatch** out) {
+  if (!ctx || !out) return fail(PSG_ERR_ARG, "null argument");
+  *out = nullptr;
+  int device, dtype;
+  hipStream_t stream;
+  psg::ctx_info(ctx, &device, &dtype, &stream);
+  if (dtype != PSG_F64) return fail(PSG_ERR_ARG, "a minibatch needs a PSG_F64 context");
+  HIP_TRY(hipSetDevice(device));
+  psg_minibatch* mb = new (std::nothrow) psg_minibatch();
+  if (!mb) return fail(PSG_ERR_OOM, "host allocation");
+  mb->ctx = ctx;
+  mb->device = device;
+  mb->stream = stream;
+  if (hipMalloc((void**)&mb->d_small, kSmallBytes) != hipSuccess ||
+      hipHostMalloc((void**)&mb->h_small, 64) != hipSuccess ||
+      hipEventCreateWithFlags(&mb->ev, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    psg_mb_destroy(mb);
+    return fail(PSG_ERR_OOM, "minibatch control blocks");
+  }
+  *out = mb;
+  return PSG_OK;
+}
+
+void psg_mb_destroy(psg_minibatch* mb) {
+  if (!mb) return;
+  (void)hipSetDevice(mb->device);
+  if (mb->last_s && mb->last_s != mb->stream) (void)hipStreamSynchronize(mb->last_s);
+  (void)hipStreamSynchronize(mb->stream);
+  for (auto& x : mb->b)
+    if (x.p) (void)hipFree(x.p);
+  if (mb->d_small) (void)hipFree(mb->d_small);
+  if (mb->h_small) (void)hipHostFree(mb->h_small);
+  if (mb->ev) (void)hipEventDestroy(mb->ev);
+  for (hipEvent_t e : mb->tev)
+    if (e) (void)hipEventDestroy(e);
+  delete mb;
+}
+
+int psg_mb_load(psg_minibatch* mb, const uint64_t* offset, size_t rows, const uint64_t* index,
+                const double* value, const double* y) {
+  if (!mb || !offset || (rows && !y)) return fail(PSG_ERR_ARG, "null argument");
+  if (rows >= 0xffffffffull) return fail(PSG_ERR_SIZE, "%zu rows >= 2^32 - 1", rows);
+  const uint64_t nnz = offset[rows];
+  if (nnz >= 0xffffffffull)  // CHECK_LT(idx.size(), kuint32max), localizer.h:54
+    return fail(PSG_ERR_SIZE, "%llu entries >= 2^32 - 1: positions are uint32",
+                (unsigned long long)nnz);
+  if (offset[0] != 0) return fail(PSG_ERR_ARG, "offset[0] = %llu", (unsigned long long)offset[0]);
+  for (size_t i = 0; i < rows; ++i)
+    if (offset[i] > offset[i + 1]) return fail(PSG_ERR_ARG, "offset decreases at row %zu", i);
+  if (nnz && !index) return fail(PSG_ERR_ARG, "null index");
+  HIP_TRY(hipSetDevice(mb->device));
+  if (int rc = mb->settle()) return rc;  // the previous minibatch's work
+  mb->state = S_NEW;
+  const size_t n = (size_t)nnz, ntiles = blocks_of(n, kSortTile);
+  struct {
+    int id;
+    size_t bytes;
+  } const want[] = {
+      {B_OFFSET, 8 * (rows + 1)}, {B_Y, 8 * rows}, {B_INDEX, 8 * n},
+      {B_VALUE, value ? 8 * n : 0}, {B_KEY_A, 8 * n}, {B_KEY_B, 8 * n}, {B_POS_A, 4 * n},
+      {B_POS_B, 4 * n}, {B_COUNTS, 4 * 256 * ntiles},
+      {B_TILE_SUM, 4 * (size_t)blocks_of(n, kFlagTile) + 4}, {B_UNIQ_KEY, 8 * n},
+      {B_KEY_CNT, 4 * n}, {B_RUN_START, 4 * (n + 1)}, {B_RUN_OF, 4 * n}, {B_ROW_OF, 4 * n},
+      {B_RUN_RANK, 4 * n}, {B_REMAPPED, 4 * n}, {B_BEFORE, 4 * (n + 1)},
+      {B_NEW_OFFSET, 8 * (rows + 1)}, {B_NEW_INDEX, 4 * n}, {B_NEW_VALUE, value ? 8 * n : 0},
+      {B_TERM, 8 * n}, {B_XW, 8 * rows}, {B_TAU, 8 * rows}, {B_C, 8 * rows}, {B_LOSS, 8 * rows},
+      {B_PARTIAL, 8 * (size_t)blocks_of(rows, 256) + 8}};
+  for (const auto& w : want)
+    if (int rc = mb->need(w.id, w.bytes)) return rc;
+  hipStream_t s = mb->stream;
+  HIP_TRY(hipMemcpyAsync(mb->b[B_OFFSET].p, offset, 8 * (rows + 1), hipMemcpyHostToDevice, s));
+  if (rows) HIP_TRY(hipMemcpyAsync(mb->b[B_Y].p, y, 8 * rows, hipMemcpyHostToDevice, s));
+  mb->h_small[0] = 0;
+  mb->h_small[1] = ~0ull;
+  mb->h_small[2] = 0;
+  HIP_TRY(hipMemcpyAsync(mb->d_small, mb->h_small, 24, hipMemcpyHostToDevice, s));
+  if (n) {
+    HIP_TRY(hipMemcpyAsync(mb->b[B_INDEX].p, index, 8 * n, hipMemcpyHostToDevice, s));
+    if (value)
+      HIP_TRY(hipMemcpyAsync(mb->b[B_VALUE].p, value, 8 * n, hipMemcpyHostToDevice, s));
+    LAUNCH(row_of_kernel, blocks_of(n, 256), s, mb->at<uint64_t>(B_OFFSET), (uint32_t)rows,
+           (uint32_t)n, mb->at<uint32_t>(B_ROW_OF));
+    const uint32_t grid = std::min<uint32_t>(blocks_of(n, 256), 2048u);
+    LAUNCH(key_bits_kernel, grid, s, mb->at<uint64_t>(B_INDEX), (uint32_t)n, mb->d_small);
+    if (int rc = launched("minibatch load")) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(mb->h_small, mb->d_small, 16, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));  // the host arrays are free on return
+  mb->differ = n ? mb->h_small[0] ^ mb->h_small[1] : 0;
+  mb->rows = rows;
+  mb->nnz = n;
+  mb->binary = value == nullptr;
+  mb->n_uniq = mb->ndict = 0;
+  mb->last_s = nullptr;
+  mb->state = S_LOADED;
+  return PSG_OK;
+}
+
+int psg_mb_uniq(psg_minibatch* mb, const uint64_t** keys_dev, const uint32_t** cnt_dev,
+                size_t* n_out) {
+  if (!mb || !n_out) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_LOADED) return fail(PSG_ERR_ARG, "psg_mb_uniq before psg_mb_load");
+  HIP_TRY(hipSetDevice(mb->device));
+  if (mb->state == S_LOADED) {
+    hipStream_t s = mb->stream;
+    const uint32_t n = (uint32_t)mb->nnz;
+    mb->n_uniq = 0;
+    if (n) {
+      mb->tick(PSG_MB_STAGE_SORT, 0, s);
+      if (int rc = enqueue_sort(mb, s)) return rc;
+      mb->tick(PSG_MB_STAGE_SORT, 1, s);
+      mb->tick(PSG_MB_STAGE_RUNS, 0, s);
+      const uint32_t nt = blocks_of(n, kFlagTile);
+      uint32_t* ts = mb->at<uint32_t>(B_TILE_SUM);
+      const HeadFlag f{mb->skey};
+      const HeadEmit e{mb->skey, mb->at<uint64_t>(B_UNIQ_KEY), mb->at<uint32_t>(B_RUN_START),
+                       mb->at<uint32_t>(B_RUN_OF)};
+      LAUNCH(flag_count_kernel<HeadFlag>, nt, s, f, n, ts);
+      LAUNCH(row_scan_kernel, 1, s, ts, nt, mb->d_u32(0));
+      LAUNCH((flag_emit_kernel<HeadFlag, HeadEmit>), nt, s, f, e, n, ts);
+      mb->tick(PSG_MB_STAGE_RUNS, 1, s);
+      if (int rc = launched("run heads")) return rc;
+      HIP_TRY(hipMemcpyAsync(mb->h_small + 4, mb->d_small + 4, 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      mb->n_uniq = (uint32_t)(mb->h_small[4] & 0xffffffffu);
+      if (mb->n_uniq == 0 || mb->n_uniq > n)
+        return fail(PSG_ERR_DEVICE, "run count %zu of %u pairs", mb->n_uniq, n);
+      LAUNCH(key_cnt_kernel, blocks_of(mb->n_uniq, 256), s, mb->at<uint32_t>(B_RUN_START),
+             (uint32_t)mb->n_uniq, mb->at<uint32_t>(B_KEY_CNT));
+      if (int rc = launched("key counts")) return rc;
+      if (int rc = mb->mark(s)) return rc;
+    }
+    mb->state = S_UNIQ;
+  }
+  if (keys_dev) *keys_dev = mb->at<uint64_t>(B_UNIQ_KEY);
+  if (cnt_dev) *cnt_dev = mb->at<uint32_t>(B_KEY_CNT);
+  *n_out = mb->n_uniq;
+  return PSG_OK;
+}
+
+int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
+                    const uint32_t** pos_dev, const uint32_t** neg_dev, void* stream) {
+  if (!mb || (ndict && !dict_dev)) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_UNIQ) return fail(PSG_ERR_ARG, "psg_mb_localize before psg_mb_uniq");
+  if (ndict >= 0xffffffffull)  // CHECK_LT(idx_dict.size(), kuint32max), localizer.h:115
+    return fail(PSG_ERR_SIZE, "dictionary of %zu keys >= 2^32 - 1", ndict);
+  HIP_TRY(hipSetDevice(mb->device));
+  if (int rc = mb->need(B_DICT_RUN, 4 * ndict)) return rc;
+  if (int rc = mb->need(B_CNT_POS, 4 * ndict)) return rc;
+  if (int rc = mb->need(B_CNT_NEG, 4 * ndict)) return rc;
+  if (int rc = mb->need(B_GRAD, 8 * ndict)) return rc;
+  if (int rc = mb->need(B_LONG_LIST, 4 * ndict)) return rc;
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  mb->state = S_UNIQ;
+  const uint32_t n = (uint32_t)mb->nnz, nu = (uint32_t)mb->n_uniq, nd = (uint32_t)ndict;
+  const uint32_t rows = (uint32_t)mb->rows;
+  uint32_t* before = mb->at<uint32_t>(B_BEFORE);
+  mb->tick(PSG_MB_STAGE_LOCALIZE, 0, s);
+  HIP_TRY(hipMemsetAsync(mb->d_small + 2, 0, 8, s));
+  HIP_TRY(hipMemsetAsync(mb->d_u32(1), 0, 4, s));
+  if (nd > 1) LAUNCH(dict_check_kernel, blocks_of(nd - 1, 256), s, dict_dev, nd, mb->d_small + 2);
+  if (nd) HIP_TRY(hipMemsetAsync(mb->b[B_DICT_RUN].p, 0xff, 4 * (size_t)nd, s));
+  if (n) {
+    LAUNCH(run_search_kernel, blocks_of(nu, 256), s, mb->at<uint64_t>(B_UNIQ_KEY), nu, dict_dev,
+           nd, mb->at<uint32_t>(B_RUN_RANK), mb->at<uint32_t>(B_DICT_RUN));
+    HIP_TRY(hipMemsetAsync(mb->b[B_REMAPPED].p, 0, 4 * (size_t)n, s));
+    LAUNCH(remap_kernel, blocks_of(n, 256), s, mb->spos, mb->at<uint32_t>(B_RUN_OF),
+           mb->at<uint32_t>(B_RUN_RANK), n, nu, mb->at<uint32_t>(B_REMAPPED));
+    const uint32_t nt = blocks_of(n, kFlagTile);
+    uint32_t* ts = mb->at<uint32_t>(B_TILE_SUM);
+    const KeptFlag f{mb->at<uint32_t>(B_REMAPPED)};
+    const KeptEmit e{mb->at<uint32_t>(B_REMAPPED), mb->binary ? nullptr : mb->at<double>(B_VALUE),
+                     before, mb->at<uint32_t>(B_NEW_INDEX), mb->at<double>(B_NEW_VALUE)};
+    LAUNCH(flag_count_kernel<KeptFlag>, nt, s, f, n, ts);
+    LAUNCH(row_scan_kernel, 1, s, ts, nt, mb->d_u32(1));
+    LAUNCH((flag_emit_kernel<KeptFlag, KeptEmit>), nt, s, f, e, n, ts);
+  } else {
+    HIP_TRY(hipMemsetAsync(before, 0, 4, s));
+  }
+  LAUNCH(new_offset_kernel, blocks_of((uint64_t)rows + 1, 256), s, mb->at<uint64_t>(B_OFFSET),
+         before, rows, mb->at<uint64_t>(B_NEW_OFFSET));
+  mb->tick(PSG_MB_STAGE_LOCALIZE, 1, s);
+  mb->tick(PSG_MB_STAGE_COUNT_KEYS, 0, s);
+  HIP_TRY(hipMemsetAsync(mb->d_small + 5, 0, 8, s));
+  if (nd) {
+    HIP_TRY(hipMemsetAsync(mb->b[B_CNT_POS].p, 0, 4 * (size_t)nd, s));
+    HIP_TRY(hipMemsetAsync(mb->b[B_CNT_NEG].p, 0, 4 * (size_t)nd, s));
+    if (n) {
+      LAUNCH(count_keys_kernel, blocks_of(n, 256), s, mb->spos, mb->at<uint32_t>(B_ROW_OF),
+             mb->at<double>(B_Y), mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK), n, nu,
+             nd, mb->at<uint32_t>(B_CNT_POS), mb->at<uint32_t>(B_CNT_NEG));
+      LAUNCH(long_runs_kernel, blocks_of(nd, 256), s, mb->at<uint32_t>(B_DICT_RUN), nd,
+             mb->at<uint32_t>(B_RUN_START), nu, n, mb->at<uint32_t>(B_LONG_LIST),
+             (uint32_t*)(mb->d_small + 5));
+    }
+  }
+  mb->tick(PSG_MB_STAGE_COUNT_KEYS, 1, s);
+  if (int rc = launched("localize")) return rc;
+  if (int rc = mb->mark(s)) return rc;
+  mb->ndict = ndict;
+  mb->state = S_LOCAL;
+  if (pos_dev) *pos_dev = mb->at<uint32_t>(B_CNT_POS);
+  if (neg_dev) *neg_dev = mb->at<uint32_t>(B_CNT_NEG);
+  return PSG_OK;
+}
+
+namespace {
+
+int enqueue_times(psg_minibatch* mb, const double* x, double* xw, hipStream_t s) {
+  if (mb->rows)
+    LAUNCH(times_kernel, blocks_of(mb->rows, 256), s, mb->at<uint64_t>(B_NEW_OFFSET),
+           mb->at<uint32_t>(B_NEW_INDEX), mb->binary ? nullptr : mb->at<double>(B_NEW_VALUE),
+           (uint32_t)mb->rows, x, xw);
+  return launched("times");
+}
+
+int enqueue_trans_times(psg_minibatch* mb, const double* c, double* g, hipStream_t s) {
+  const uint32_t n = (uint32_t)mb->nnz, nd = (uint32_t)mb->ndict, nu = (uint32_t)mb->n_uniq;
+  if (nd) {
+    if (n)
+      LAUNCH(terms_kernel, blocks_of(n, 256), s, mb->spos, mb->at<uint32_t>(B_ROW_OF),
+             mb->binary ? nullptr : mb->at<double>(B_VALUE), c, n, mb->at<double>(B_TERM));
+    LAUNCH(trans_times_short_kernel, blocks_of(nd, 256), s, mb->at<uint32_t>(B_DICT_RUN), nd,
+           mb->at<uint32_t>(B_RUN_START), nu, n, mb->at<double>(B_TERM), g);
+    if (n)
+      LAUNCH(trans_times_long_kernel, std::min<uint32_t>(blocks_of(nd, 4), kLongGrid), s,
+             mb->at<uint32_t>(B_LONG_LIST), (const uint32_t*)(mb->d_small + 5),
+             mb->at<uint32_t>(B_DICT_RUN), nd, mb->at<uint32_t>(B_RUN_START), nu, n,
+             mb->at<double>(B_TERM), g);
+  }
+  return launched("trans_times");
+}
+
+// A dictionary that was not strictly increasing: reported once, and the
+// minibatch is back to where psg_mb_localize can be called again.
+int report_dict(psg_minibatch* mb, unsigned long long bad) {
+  if (!bad) return PSG_OK;
+  mb->state = S_UNIQ;
+  return fail(PSG_ERR_UNSORTED, "%llu key pairs of the dictionary not strictly increasing", bad);
+}
+
+}  // namespace
+
+int psg_mb_times(psg_minibatch* mb, const double* x_dev, double* xw_dev, void* stream) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_LOCAL) return fail(PSG_ERR_ARG, "psg_mb_times before psg_mb_localize");
+  if ((mb->ndict && !x_dev) || (mb->rows && !xw_dev)) return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(mb->device));
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  if (int rc = enqueue_times(mb, x_dev, xw_dev, s)) return rc;
+  return mb->mark(s);
+}
+
+int psg_mb_trans_times(psg_minibatch* mb, const double* c_dev, double* g_dev, void* stream) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_LOCAL) return fail(PSG_ERR_ARG, "psg_mb_trans_times before psg_mb_localize");
+  if ((mb->rows && !c_dev) || (mb->ndict && !g_dev)) return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(mb->device));
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  if (int rc = enqueue_trans_times(mb, c_dev, g_dev, s)) return rc;
+  return mb->mark(s);
+}
+
+int psg_mb_gradient(psg_minibatch* mb, int loss, const double* w_dev, const double** grad_dev,
+                    double* objv, void* stream) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (loss != PSG_LOSS_LOGIT) return fail(PSG_ERR_ARG, "loss %d: only PSG_LOSS_LOGIT is built", loss);
+  if (mb->state < S_LOCAL) return fail(PSG_ERR_ARG, "psg_mb_gradient before psg_mb_localize");
+  if (mb->ndict && !w_dev) return fail(PSG_ERR_ARG, "null weights");
+  HIP_TRY(hipSetDevice(mb->device));
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  const uint32_t rows = (uint32_t)mb->rows, nparts = blocks_of(rows, 256);
+  mb->tick(PSG_MB_STAGE_TIMES, 0, s);
+  if (int rc = enqueue_times(mb, w_dev, mb->at<double>(B_XW), s)) return rc;
+  mb->tick(PSG_MB_STAGE_TIMES, 1, s);
+  mb->tick(PSG_MB_STAGE_LOGIT, 0, s);
+  if (rows)
+    LAUNCH(logit_kernel, nparts, s, mb->at<double>(B_Y), mb->at<double>(B_XW), rows,
+           mb->at<double>(B_TAU), mb->at<double>(B_C), mb->at<double>(B_LOSS),
+           mb->at<double>(B_PARTIAL));
+  LAUNCH(objv_kernel, 1, s, mb->at<double>(B_PARTIAL), nparts, (double*)(mb->d_small + 3));
+  mb->tick(PSG_MB_STAGE_LOGIT, 1, s);
+  if (int rc = launched("logit")) return rc;
+  mb->tick(PSG_MB_STAGE_TRANS_TIMES, 0, s);
+  if (int rc = enqueue_trans_times(mb, mb->at<double>(B_C), mb->at<double>(B_GRAD), s)) return rc;
+  mb->tick(PSG_MB_STAGE_TRANS_TIMES, 1, s);
+  if (int rc = mb->mark(s)) return rc;
+  HIP_TRY(hipMemcpyAsync(mb->h_small + 2, mb->d_small + 2, 16, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (int rc = report_dict(mb, mb->h_small[2])) return rc;
+  if (objv) memcpy(objv, mb->h_small + 3, 8);
+  if (grad_dev) *grad_dev = mb->at<double>(B_GRAD);
+  mb->state = S_GRAD;
+  return PSG_OK;
+}
+
+int psg_mb_scratch(psg_minibatch* mb, int slot, size_t bytes, void** dev) {
+  if (!mb || !dev || slot < 0 || slot > 3) return fail(PSG_ERR_ARG, "bad scratch slot");
+  HIP_TRY(hipSetDevice(mb->device));
+  if (int rc = mb->need(B_SCRATCH0 + slot, bytes ? bytes : 1)) return rc;
+  mb->scratch_len[slot] = bytes;
+  *dev = mb->b[B_SCRATCH0 + slot].p;
+  return PSG_OK;
+}
+
+int psg_mb_profile(psg_minibatch* mb, int on) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(mb->device));
+  if (on)
+    for (hipEvent_t& e : mb->tev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+  for (bool& b : mb->tset) b = false;
+  mb->prof = on != 0;
+  return PSG_OK;
+}
+
+int psg_mb_stage_ms(psg_minibatch* mb, double* ms) {
+  if (!mb || !ms) return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(mb->device));
+  if (int rc = mb->settle()) return rc;
+  for (int st = 0; st < PSG_MB_STAGES; ++st) {
+    ms[st] = -1.0;
+    if (!mb->tset[2 * st] || !mb->tset[2 * st + 1]) continue;
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, mb->tev[2 * st], mb->tev[2 * st + 1]));
+    ms[st] = t;
+  }
+  return PSG_OK;
+}
+
+int psg_mb_stream(psg_minibatch* mb, void** stream) {
+  if (!mb || !stream) return fail(PSG_ERR_ARG, "null argument");
+  *stream = (void*)mb->stream;
+  return PSG_OK;
+}
+
+int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t* n_out) {
+  if (!mb || !n_out) return fail(PSG_ERR_ARG, "null argument");
+  *n_out = 0;
+  int need_state, id;
+  size_t n;
+  const size_t kept_unknown = ~(size_t)0;
+  switch (what) {
+    case PSG_MB_SORTED_KEY: need_state = S_UNIQ; id = -1; n = mb->nnz; break;
+    case PSG_MB_SORTED_POS: need_state = S_UNIQ; id = -2; n = mb->nnz; break;
+    case PSG_MB_UNIQ_KEY: need_state = S_UNIQ; id = B_UNIQ_KEY; n = mb->n_uniq; break;
+    case PSG_MB_KEY_CNT: need_state = S_UNIQ; id = B_KEY_CNT; n = mb->n_uniq; break;
+    case PSG_MB_RUN_START: need_state = S_UNIQ; id = B_RUN_START; n = mb->nnz ? mb->n_uniq + 1 : 0; break;
+    case PSG_MB_ROW_OF: need_state = S_LOADED; id = B_ROW_OF; n = mb->nnz; break;
+    case PSG_MB_REMAPPED: need_state = S_LOCAL; id = B_REMAPPED; n = mb->nnz; break;
+    case PSG_MB_NEW_OFFSET: need_state = S_LOCAL; id = B_NEW_OFFSET; n = mb->rows + 1; break;
+    case PSG_MB_NEW_INDEX: need_state = S_LOCAL; id = B_NEW_INDEX; n = kept_unknown; break;
+    case PSG_MB_NEW_VALUE: need_state = S_LOCAL; id = B_NEW_VALUE; n = kept_unknown; break;
+    case PSG_MB_POS: need_state = S_LOCAL; id = B_CNT_POS; n = mb->ndict; break;
+    case PSG_MB_NEG: need_state = S_LOCAL; id = B_CNT_NEG; n = mb->ndict; break;
+    case PSG_MB_XW: need_state = S_GRAD; id = B_XW; n = mb->rows; break;
+    case PSG_MB_TAU: need_state = S_GRAD; id = B_TAU; n = mb->rows; break;
+    case PSG_MB_LOSS: need_state = S_GRAD; id = B_LOSS; n = mb->rows; break;
+    case PSG_MB_GRAD: need_state = S_GRAD; id = B_GRAD; n = mb->ndict; break;
+    case PSG_MB_SCRATCH + 0: case PSG_MB_SCRATCH + 1: case PSG_MB_SCRATCH + 2:
+    case PSG_MB_SCRATCH + 3:
+      need_state = S_NEW; id = B_SCRATCH0 + (what - PSG_MB_SCRATCH);
+      n = mb->scratch_len[what - PSG_MB_SCRATCH] / 8; break;
+    default: return fail(PSG_ERR_ARG, "psg_mb_read: array %d", what);
+  }
+  if (mb->state < need_state)
+    return fail(PSG_ERR_ARG, "psg_mb_read: array %d is not computed yet", what);
+  HIP_TRY(hipSetDevice(mb->device));
+  if (int rc = mb->settle()) return rc;
+  if (mb->state >= S_LOCAL) {
+    HIP_TRY(hipMemcpy(mb->h_small + 2, mb->d_small + 2, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mb->h_small + 4, mb->d_small + 4, 8, hipMemcpyDeviceToHost));
+    if (need_state >= S_LOCAL)
+      if (int rc = report_dict(mb, mb->h_small[2])) return rc;
+    if (n == kept_unknown) {
+      n = (size_t)(mb->h_small[4] >> 32);
+      if (n > mb->nnz) return fail(PSG_ERR_DEVICE, "%zu survivors of %zu entries", n, mb->nnz);
+      if (what == PSG_MB_NEW_VALUE && mb->binary) n = 0;
+    }
+  }
+  *n_out = n;
+  const size_t bytes = n * elem_size(what);
+  if (bytes > cap_bytes)
+    return fail(PSG_ERR_SIZE, "psg_mb_read: array %d holds %zu bytes, room for %zu", what, bytes,
+                cap_bytes);
+  if (bytes == 0) return PSG_OK;
+  if (!out) return fail(PSG_ERR_ARG, "null output");
+  const void* src = id == -1 ? (const void*)mb->skey
+                             : id == -2 ? (const void*)mb->spos : (const void*)mb->b[id].p;
+  HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  return PSG_OK;
+}
+
+}  // extern "C"

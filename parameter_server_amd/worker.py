@@ -1,0 +1,227 @@
+"""Python mirror of the reference's online worker step over the C ABI.
+
+``Minibatch`` is a thin class over ``psg_mb_*`` (include/psg.h): one worker
+minibatch resident in HBM, with ``Localizer::countUniqIndex`` / ``remapIndex``
+(reference src/base/localizer.h:50-168), ``FTRL::countKeys``
+(src/linear_method/ftrl.cc:154-174), ``Xw = Z * w``, ``LogitLoss``
+(src/linear_method/loss.h:73-85) and the gradient as device kernels.
+
+``FTRLWorker.step`` is the body of ``FTRL::updateModel``'s loop
+(ftrl.cc:88-151) against an ``FTRLModel`` in the same context: unique keys,
+tail filter, pull, localize, gradient, push.  Every array stays on the
+device between those calls; the host reads ``n_uniq``, the filter's kept
+count and ``objv``, the three points at which the reference worker waits
+(ftrl.cc:102,122,130).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Tuple
+
+import numpy as np
+
+from . import _lib
+from .ftrl import FTRLModel
+from .kv_vector import _ptr
+
+# psg_mb_read's arrays: name -> (id, dtype)
+ARRAYS = {
+    "sorted_key": (_lib.PSG_MB_SORTED_KEY, np.uint64),
+    "sorted_pos": (_lib.PSG_MB_SORTED_POS, np.uint32),
+    "uniq_key": (_lib.PSG_MB_UNIQ_KEY, np.uint64),
+    "key_cnt": (_lib.PSG_MB_KEY_CNT, np.uint32),
+    "new_offset": (_lib.PSG_MB_NEW_OFFSET, np.uint64),
+    "new_index": (_lib.PSG_MB_NEW_INDEX, np.uint32),
+    "new_value": (_lib.PSG_MB_NEW_VALUE, np.float64),
+    "pos": (_lib.PSG_MB_POS, np.uint32),
+    "neg": (_lib.PSG_MB_NEG, np.uint32),
+    "xw": (_lib.PSG_MB_XW, np.float64),
+    "tau": (_lib.PSG_MB_TAU, np.float64),
+    "loss": (_lib.PSG_MB_LOSS, np.float64),
+    "grad": (_lib.PSG_MB_GRAD, np.float64),
+    "run_start": (_lib.PSG_MB_RUN_START, np.uint32),
+    "remapped": (_lib.PSG_MB_REMAPPED, np.uint32),
+    "row_of": (_lib.PSG_MB_ROW_OF, np.uint32),
+}
+
+
+def sort_tile() -> int:
+    """Pairs per workgroup of the device sort (psg_mb_sort_tile)."""
+    return int(_lib.lib().psg_mb_sort_tile())
+
+
+class Minibatch:
+    """One worker minibatch (row-major CSR with global ids) on the device of
+    context ``ctx`` (a ``psg_ctx`` handle of a PSG_F64 context)."""
+
+    def __init__(self, ctx):
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(self._L.psg_mb_create(ctx, C.byref(h)))
+        self._h = h
+        self.rows = self.nnz = self.n_uniq = self.ndict = 0
+        s = C.c_void_p()
+        _lib.check(self._L.psg_mb_stream(h, C.byref(s)))
+        self.stream = s.value  # the context's
+        self.uniq_key_dev = self.key_cnt_dev = None
+        self.pos_dev = self.neg_dev = self.grad_dev = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psg_mb_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, offset, index, value, y) -> None:
+        """psg_mb_load; ``value`` None: a binary matrix."""
+        offset = np.ascontiguousarray(offset, dtype=np.uint64)
+        index = np.ascontiguousarray(index, dtype=np.uint64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if offset.size < 1 or y.size != offset.size - 1:
+            raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"{y.size} labels for {offset.size} offsets")
+        if value is not None:
+            value = np.ascontiguousarray(value, dtype=np.float64)
+            if value.size != index.size:  # CHECK_EQ(value.size(), index.size()) localizer.h:119
+                raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"{value.size} values, {index.size} ids")
+        if int(offset[-1]) < (1 << 32) - 1 and int(offset[-1]) != index.size:
+            raise _lib.PSGError(_lib.PSG_ERR_SIZE,  # CHECK_EQ(offset.back(), index.size()) :116
+                                f"offset ends at {int(offset[-1])}, {index.size} ids")
+        _lib.check(self._L.psg_mb_load(self._h, _ptr(offset), offset.size - 1, _ptr(index),
+                                       _ptr(value) if value is not None else None, _ptr(y)))
+        self.rows, self.nnz = offset.size - 1, index.size
+        self.n_uniq = self.ndict = 0
+
+    def uniq(self) -> int:
+        """psg_mb_uniq: n_uniq; the device arrays are uniq_key_dev, key_cnt_dev."""
+        k, c, n = C.c_void_p(), C.c_void_p(), C.c_size_t()
+        _lib.check(self._L.psg_mb_uniq(self._h, C.byref(k), C.byref(c), C.byref(n)))
+        self.uniq_key_dev, self.key_cnt_dev, self.n_uniq = k.value, c.value, n.value
+        return n.value
+
+    def localize(self, dict_dev, ndict: int, stream=None) -> None:
+        """psg_mb_localize against ndict device keys; pos_dev / neg_dev."""
+        p, q = C.c_void_p(), C.c_void_p()
+        _lib.check(self._L.psg_mb_localize(self._h, dict_dev, ndict, C.byref(p), C.byref(q),
+                                           stream))
+        self.pos_dev, self.neg_dev, self.ndict = p.value, q.value, ndict
+
+    def times(self, x_dev, xw_dev, stream=None) -> None:
+        _lib.check(self._L.psg_mb_times(self._h, x_dev, xw_dev, stream))
+
+    def trans_times(self, c_dev, g_dev, stream=None) -> None:
+        _lib.check(self._L.psg_mb_trans_times(self._h, c_dev, g_dev, stream))
+
+    def gradient(self, w_dev, loss: int = _lib.PSG_LOSS_LOGIT, stream=None) -> float:
+        """psg_mb_gradient: objv; the device gradient is grad_dev."""
+        g, objv = C.c_void_p(), C.c_double()
+        _lib.check(self._L.psg_mb_gradient(self._h, loss, w_dev, C.byref(g), C.byref(objv),
+                                           stream))
+        self.grad_dev = g.value
+        return objv.value
+
+    def scratch(self, slot: int, nbytes: int) -> int:
+        """A device block of the minibatch's (psg_mb_scratch)."""
+        p = C.c_void_p()
+        _lib.check(self._L.psg_mb_scratch(self._h, slot, nbytes, C.byref(p)))
+        return p.value
+
+    def profile(self, on: bool = True) -> None:
+        """Stage timing on or off (psg_mb_profile)."""
+        _lib.check(self._L.psg_mb_profile(self._h, 1 if on else 0))
+
+    def stage_ms(self) -> dict:
+        """The last run's time of each stage in ms (psg_mb_stage_ms); waits."""
+        ms = (C.c_double * len(_lib.MB_STAGES))()
+        _lib.check(self._L.psg_mb_stage_ms(self._h, ms))
+        return dict(zip(_lib.MB_STAGES, list(ms)))
+
+    def _read(self, what: int, dtype) -> np.ndarray:
+        n = C.c_size_t()
+        rc = self._L.psg_mb_read(self._h, what, None, 0, C.byref(n))
+        if rc not in (_lib.PSG_OK, _lib.PSG_ERR_SIZE):
+            _lib.check(rc)
+        out = np.empty(n.value, dtype)
+        if n.value:
+            _lib.check(self._L.psg_mb_read(self._h, what, _ptr(out), out.nbytes, C.byref(n)))
+        return out
+
+    def read(self, name: str) -> np.ndarray:
+        """A host copy of one internal array (ARRAYS)."""
+        what, dtype = ARRAYS[name]
+        return self._read(what, dtype)
+
+    def read_scratch(self, slot: int, dtype, count: int) -> np.ndarray:
+        """The first `count` items of a scratch block, as `dtype` (8 bytes wide)."""
+        a = self._read(_lib.PSG_MB_SCRATCH + slot, np.uint64)
+        return a[:count].view(dtype)
+
+
+class FTRLWorker:
+    """The worker of the online solver (ftrl.cc:88-151) for one model.
+
+    ``tail_feature_freq`` > 0 turns the tail filter on: a minibatch's keys
+    are inserted with their counts and only those whose estimate exceeds it
+    are kept (shared_parameter.h:114-133), in a CountMin of ``countmin_n``
+    counters and ``countmin_k`` probes on channel ``chl`` of the context."""
+
+    _DICT, _W, _FILTER, _WORD = 0, 1, 2, 3  # scratch slots
+
+    def __init__(self, model: FTRLModel, tail_feature_freq: int = 0, countmin_n: int = 1 << 20,
+                 countmin_k: int = 2, chl: int = 0):
+        self._L = _lib.lib()
+        self.model = model
+        self._ctx = model._model()
+        self.freq = int(tail_feature_freq)
+        self.chl = chl
+        if self.freq > 0:
+            _lib.check(self._L.psg_freq_resize(self._ctx, chl, countmin_n, countmin_k))
+        self.mb = Minibatch(self._ctx)
+        self.objv = 0.0   # status_.objv
+        self.num_ex = 0   # status_.num_ex
+        self.ndict = 0
+        self.dict_dev = self.w_dev = None
+
+    def close(self):
+        self.mb.close()
+
+    def step(self, offset, index, value, y) -> Tuple[float, int]:
+        """One minibatch: (its objv, its number of examples)."""
+        L, mb = self._L, self.mb
+        st = mb.stream  # every enqueue of the step, in order
+        mb.load(offset, index, value, y)
+        n = mb.uniq()                                                      # ftrl.cc:96
+        if self.freq > 0 and n:                                            # :99-106
+            keys = mb.scratch(self._DICT, 8 * n)
+            word = mb.scratch(self._WORD, 8)
+            fs = mb.scratch(self._FILTER, L.psg_freq_query_scratch_bytes(n))
+            _lib.check(L.psg_freq_insert_dev(self._ctx, self.chl, mb.uniq_key_dev,
+                                             mb.key_cnt_dev, n, st))
+            _lib.check(L.psg_freq_query_dev(self._ctx, self.chl, mb.uniq_key_dev, n, self.freq,
+                                            keys, word, fs, st))
+            ndict = int(mb.read_scratch(self._WORD, np.uint64, 1)[0])
+        else:
+            keys, ndict = mb.uniq_key_dev, n
+        w = mb.scratch(self._W, 8 * ndict)
+        _lib.check(L.psg_ftrl_pull_dev(self._ctx, keys, ndict, w, st))   # :108-111
+        mb.localize(keys, ndict)                                           # :113-119
+        objv = mb.gradient(w)                                              # :128-138
+        _lib.check(L.psg_ftrl_push_dev(self._ctx, keys, ndict, mb.pos_dev, mb.neg_dev,
+                                       mb.grad_dev, st))                 # :141-148
+        self.dict_dev, self.w_dev, self.ndict = keys, w, ndict
+        self.objv += objv                                                  # :131-135
+        self.num_ex += mb.rows
+        return objv, mb.rows
+
+    # -- what the last step used, for tests and checkpoints ------------------
+    def last_dict(self) -> np.ndarray:
+        if self.freq > 0 and self.mb.n_uniq:
+            return self.mb.read_scratch(self._DICT, np.uint64, self.ndict).copy()
+        return self.mb.read("uniq_key")
+
+    def last_w(self) -> np.ndarray:
+        return self.mb.read_scratch(self._W, np.float64, self.ndict).copy()
