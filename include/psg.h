@@ -623,6 +623,74 @@ int psg_mb_stream(psg_minibatch* mb, void** stream);
 size_t psg_mb_sort_tile(void);
 
 /* ------------------------------------------------------------------ */
+/* Batch worker step: the worker half of Darling::updateModel          */
+/* (src/linear_method/darling.cc:196-250) on a localized minibatch:    */
+/* computeGradients (:306-356), updateDual (:358-435), the worker's    */
+/* lines of preprocessData (:110-117) and evaluateProgress (:506).     */
+/* ------------------------------------------------------------------ */
+/* The minibatch is the worker's data of one feature group, the dictionary of
+ * psg_mb_localize is w_->key(grp), and the dictionary positions [cb, ce) are
+ * what seg_pos / col_range are in the reference: column k of the column-major
+ * matrix Darling reads (SparseMatrix::alterStorage, sparse_matrix.h:186-241,
+ * fills each column in row-major scan order) is key k's entries in ascending
+ * position.  Every call needs psg_mb_darling_init after psg_mb_localize;
+ * psg_mb_load and psg_mb_localize invalidate the state; a call ahead of the
+ * one it needs, cb > ce or ce > ndict is PSG_ERR_ARG.  Streams and buffers as
+ * for the calls above.  Every operator of darling.cc:342-350,375-376,432 is
+ * one rounded operation in the order written, std::min is b < a ? b : a (a
+ * NaN first argument stays), and every sum and product runs in the
+ * reference's order (no float atomics, no tree): G, cur_w, delta, delta_w and
+ * the active set are bit for bit the reference's from the same state.
+ * Defined deviations from the reference:
+ *  - exp and log are the device's (each within 1 ulp), so U, dual and objv
+ *    are within the bounds derived in tests/test_darling_worker_gpu.py of the
+ *    host's;
+ *  - objv is the fixed-order device reduction of psg_mb_gradient (a tree over
+ *    each 256 rows, then over those sums): the same bits on every run, within
+ *    rows * 2^-53 * objv of the exact sum; not Eigen's .sum() (darling.cc:506);
+ *  - a dictionary key absent from the data is a column with no entry (G = U =
+ *    +0.0), and a row with no surviving entry has dual = exp(y * +0.0) = 1;
+ *  - the active set is kept as one byte per key, not a Bitmap. */
+/* preprocessData (:110-117): dual[rows] = exp(y .* (Z * w)), the worker's
+ * copy cur_w[ndict] = w (w_dev NULL: zero, and every dual exactly 1.0),
+ * delta[ndict] = delta_init, active all true.  Also builds the rows' lists
+ * that psg_mb_darling_update_dual walks (a stable sort of the surviving
+ * sorted pairs by row) and reads each column's range of sorted pairs to the
+ * host: synchronises, and reports an unsorted dictionary as psg_mb_gradient
+ * does. */
+int psg_mb_darling_init(psg_minibatch* mb, double delta_init, const double* w_dev, void* stream);
+/* kkt_filter_reset: active_set.fill(true) (:167-169).  Enqueues only. */
+int psg_mb_darling_reset_active(psg_minibatch* mb, void* stream);
+/* computeGradients (:306-356) over columns [cb, ce): g_dev[j], u_dev[j] are
+ * column cb + j's.  An inactive column gets the all-ones NaN in both
+ * (kInactiveValue_, :15,334); both branches (binary, valued) are built.
+ * Enqueues only. */
+int psg_mb_darling_gradients(psg_minibatch* mb, size_t cb, size_t ce, double* g_dev,
+                             double* u_dev, void* stream);
+/* updateDual (:358-435): new_w_dev[j] is column cb + j's pulled weight.  The
+ * columns' state first (:364-378; delta_max = conf_.darling().
+ * delta_max_value() of newDelta, darling.h:31-33), then every row's dual
+ * (:420-434), its factors multiplied in ascending column and, within a
+ * column, ascending position.  A row that only columns with delta_w == 0 or
+ * a cleared active bit touch is not written.  Enqueues only. */
+int psg_mb_darling_update_dual(psg_minibatch* mb, size_t cb, size_t ce, const double* new_w_dev,
+                               double delta_max, void* stream);
+/* evaluateProgress (:506): *objv = sum log(1 + 1 / dual), on the host;
+ * synchronises. */
+int psg_mb_darling_objv(psg_minibatch* mb, double* objv, void* stream);
+/* Tests and checkpoints: host arrays dual[rows], cur_w[ndict], delta[ndict],
+ * active[ndict] (bytes 0 / 1; anything else PSG_ERR_ARG); any may be NULL.
+ * Waits for the minibatch's work first. */
+int psg_mb_darling_set_state(psg_minibatch* mb, const double* dual, const double* cur_w,
+                             const double* delta, const uint8_t* active);
+/* psg_mb_read ids of the state (PSG_ERR_ARG before psg_mb_darling_init) */
+#define PSG_MB_DARLING_DUAL 32     /* double[rows] */
+#define PSG_MB_DARLING_CUR_W 33    /* double[ndict] */
+#define PSG_MB_DARLING_DELTA 34    /* double[ndict] */
+#define PSG_MB_DARLING_ACTIVE 35   /* uint8[ndict], 0 / 1 */
+#define PSG_MB_DARLING_DELTA_W 36  /* double[ce - cb] of the last psg_mb_darling_update_dual */
+
+/* ------------------------------------------------------------------ */
 /* Wire ingress: key signatures of the key cache                       */
 /* ------------------------------------------------------------------ */
 /* CRC-32C of device-resident byte segments: out[i] = crc32c::Extend(

@@ -8,5 +8,6 @@ mirror of KVVector for tests and tools, and synthetic workload generators.
 from ._lib import PSGError, lib  # noqa: F401
 
 from .worker import FTRLWorker, Minibatch  # noqa: F401,E402
+from .darling import DarlingWorker  # noqa: F401,E402
 
-__all__ = ["PSGError", "lib", "FTRLWorker", "Minibatch"]
+__all__ = ["PSGError", "lib", "FTRLWorker", "Minibatch", "DarlingWorker"]

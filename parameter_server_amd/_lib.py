@@ -66,6 +66,9 @@ PSG_LOSS_LOGIT = 0
 (PSG_MB_SORTED_KEY, PSG_MB_SORTED_POS, PSG_MB_UNIQ_KEY, PSG_MB_KEY_CNT, PSG_MB_NEW_OFFSET,
  PSG_MB_NEW_INDEX, PSG_MB_NEW_VALUE, PSG_MB_POS, PSG_MB_NEG, PSG_MB_XW, PSG_MB_TAU, PSG_MB_LOSS,
  PSG_MB_GRAD, PSG_MB_RUN_START, PSG_MB_REMAPPED, PSG_MB_ROW_OF, PSG_MB_SCRATCH) = range(17)
+# ... and the Darling worker's state (psg_mb_darling_*)
+(PSG_MB_DARLING_DUAL, PSG_MB_DARLING_CUR_W, PSG_MB_DARLING_DELTA, PSG_MB_DARLING_ACTIVE,
+ PSG_MB_DARLING_DELTA_W) = range(32, 37)
 
 # Every symbol include/psg.h declares, with its ctypes signature.
 _u64 = C.c_uint64
@@ -94,6 +97,13 @@ class FtrlParam(C.Structure):
 
     _fields_ = [("alpha", C.c_double), ("beta", C.c_double),
                 ("lambda1", C.c_double), ("lambda2", C.c_double)]
+
+
+class DarlingParam(C.Structure):
+    """psg_darling_param (include/psg.h)."""
+
+    _fields_ = [("eta", C.c_double), ("lambda_", C.c_double),
+                ("kkt_filter_threshold", C.c_double), ("delta_max", C.c_double)]
 
 
 SIGNATURES = {
@@ -200,6 +210,12 @@ SIGNATURES = {
     "psg_mb_stage_ms": (C.c_int, [_p, C.POINTER(C.c_double)]),
     "psg_mb_stream": (C.c_int, [_p, C.POINTER(_p)]),
     "psg_mb_sort_tile": (_sz, []),
+    "psg_mb_darling_init": (C.c_int, [_p, C.c_double, _p, _p]),
+    "psg_mb_darling_reset_active": (C.c_int, [_p, _p]),
+    "psg_mb_darling_gradients": (C.c_int, [_p, _sz, _sz, _p, _p, _p]),
+    "psg_mb_darling_update_dual": (C.c_int, [_p, _sz, _sz, _p, C.c_double, _p]),
+    "psg_mb_darling_objv": (C.c_int, [_p, C.POINTER(C.c_double), _p]),
+    "psg_mb_darling_set_state": (C.c_int, [_p, _p, _p, _p, _p]),
 }
 
 _LIB = None

@@ -42,6 +42,19 @@
 // (f) tau, c = -y tau and loss per row as loss.h:74,81 writes them; objv by
 // a tree inside each workgroup of 256 rows and a second, single workgroup
 // over the partials: the order depends on `rows` alone.
+//
+// (g) The worker half of the batch solver, Darling::updateModel
+// (src/linear_method/darling.cc:196-250), on the same localized minibatch:
+// column k of the column-major matrix Darling reads is dictionary key k's
+// run of sorted pairs.  computeGradients (:306-356): the two terms of every
+// sorted pair of the block (one contiguous range of the pairs), then the
+// ordered sums as in (e), both accumulators on one chain.  updateDual
+// (:358-435): the per-column state, the factor of every sorted pair of the
+// block (all the exp calls, fully parallel), then one lane per row, which
+// multiplies its factors in ascending sorted-pair index: a row's entries
+// ordered by (column, position) are ordered by sorted-pair index.  The rows'
+// lists are built once, at psg_mb_darling_init: the surviving sorted pairs
+// stably sorted by row with the passes of (a).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -49,6 +62,7 @@
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "../../include/psg.h"
 #include "psg_host.h"
@@ -645,6 +659,326 @@ __global__ __launch_bounds__(256) void objv_kernel(const double* __restrict__ pa
   if (threadIdx.x == 0) *objv = s[0];
 }
 
+// ---- (g) ------------------------------------------------------------------------
+// std::min(a, b) as <algorithm> defines it: b < a ? b : a.  Not fmin: a NaN
+// first argument stays a NaN, as in the reference.
+__device__ __forceinline__ double std_min(double a, double b) { return b < a ? b : a; }
+
+__device__ __forceinline__ double inactive_value() {  // kInactiveValue_, darling.cc:13-15
+  return __longlong_as_double(-1ll);
+}
+
+// the dictionary key (column) of sorted pair i; false: dropped by the dictionary
+__device__ __forceinline__ bool pair_key(const uint32_t* __restrict__ run_of,
+                                         const uint32_t* __restrict__ run_rank, uint64_t i,
+                                         uint32_t n_uniq, uint32_t ndict, uint32_t* k) {
+  const uint32_t r = run_of[i];
+  const uint32_t rank = r < n_uniq ? run_rank[r] : 0u;
+  *k = rank - 1;
+  return rank != 0 && rank <= ndict;
+}
+
+__global__ __launch_bounds__(256) void fill_kernel(double* __restrict__ p, uint32_t n, double v) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// dual = exp(y .* Xw), darling.cc:110; dual holds Xw on entry
+__global__ __launch_bounds__(256) void dual_init_kernel(const double* __restrict__ y,
+                                                        uint32_t rows, double* __restrict__ dual) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i < rows) dual[i] = exp(y[i] * dual[i]);
+}
+
+// the sort key of sorted pair i for the rows' lists: its row, or `rows` (past
+// every row) for a pair the dictionary dropped
+__global__ __launch_bounds__(256) void row_key_kernel(
+    const uint32_t* __restrict__ spos, const uint32_t* __restrict__ row_of,
+    const uint32_t* __restrict__ run_of, const uint32_t* __restrict__ run_rank, uint32_t n,
+    uint32_t n_uniq, uint32_t ndict, uint32_t rows, uint64_t* __restrict__ rkey) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t k, p;
+  const uint32_t row = pair_row(spos, row_of, i, n, &p);
+  rkey[i] = pair_key(run_of, run_rank, i, n_uniq, ndict, &k) && row < rows ? row : rows;
+}
+
+// row_start[r] = the first place of the sorted row keys that holds r or more,
+// r = 0 .. rows: row r's list is [row_start[r], row_start[r + 1])
+__global__ __launch_bounds__(256) void row_start_kernel(const uint64_t* __restrict__ rkey,
+                                                        uint32_t n, uint32_t rows,
+                                                        uint32_t* __restrict__ row_start) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (r > rows) return;
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (rkey[mid] < r) {
+      lo = mid + 1;
+    } else {
+      hi = mid;
+    }
+  }
+  row_start[r] = lo;
+}
+
+// range[2k], range[2k + 1] = key k's run of sorted pairs (0, 0: none)
+__global__ __launch_bounds__(256) void col_range_kernel(
+    const uint32_t* __restrict__ dict_run, uint32_t ndict, const uint32_t* __restrict__ run_start,
+    uint32_t n_uniq, uint32_t n, uint32_t* __restrict__ range) {
+  const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (k >= ndict) return;
+  uint32_t b, e;
+  run_of_key(k, ndict, dict_run, run_start, n_uniq, n, &b, &e);
+  range[2 * k] = b;
+  range[2 * k + 1] = e;
+}
+
+// binary matrix: d = exp(delta[k]) once per column (darling.cc:338)
+__global__ __launch_bounds__(256) void exp_delta_kernel(const double* __restrict__ delta,
+                                                        const uint8_t* __restrict__ active,
+                                                        uint32_t cb, uint32_t ce,
+                                                        double* __restrict__ expd) {
+  const uint64_t k = (uint64_t)cb + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (k < ce && active[k]) expd[k] = exp(delta[k]);
+}
+
+// darling.cc:341-351 for the sorted pairs [lo, hi): term[i] = (-(y tau [v]),
+// the term of u): g -= t is g += -t, bit for bit, and the two terms of a pair
+// lie side by side so that the sums load them as one.  d: exp(delta) for a
+// binary matrix, delta otherwise.  A dropped pair or one of an inactive
+// column writes nothing, and nothing reads its terms.
+template <bool kBinary>
+__global__ __launch_bounds__(256) void darling_terms_kernel(
+    const uint32_t* __restrict__ spos, const uint32_t* __restrict__ row_of,
+    const uint32_t* __restrict__ run_of, const uint32_t* __restrict__ run_rank,
+    const double* __restrict__ value, const double* __restrict__ y,
+    const double* __restrict__ dual, const double* __restrict__ d,
+    const uint8_t* __restrict__ active, uint32_t lo, uint32_t hi, uint32_t n, uint32_t n_uniq,
+    uint32_t ndict, double2* __restrict__ term) {
+  const uint64_t i = (uint64_t)lo + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= hi || i >= n) return;
+  uint32_t k, p;
+  if (!pair_key(run_of, run_rank, i, n_uniq, ndict, &k) || !active[k]) return;
+  const uint32_t row = pair_row(spos, row_of, i, n, &p);
+  const double tau = 1 / (1 + dual[row]);
+  if (kBinary) {
+    term[i] = make_double2(-(y[row] * tau), std_min(tau * (1 - tau) * d[k], .25));
+  } else {
+    const double v = value[p];
+    term[i] = make_double2(-(y[row] * tau * v),
+                           std_min(tau * (1 - tau) * exp(fabs(v) * d[k]), .25) * v * v);
+  }
+}
+
+// columns [cb, ce): G and U of a run up to kLongRun, of an empty or absent
+// column (+0.0) and of an inactive one (darling.cc:331-336)
+__global__ __launch_bounds__(256) void darling_sum_short_kernel(
+    const uint32_t* __restrict__ dict_run, uint32_t ndict, const uint32_t* __restrict__ run_start,
+    uint32_t n_uniq, uint32_t n, const uint8_t* __restrict__ active, uint32_t cb, uint32_t ce,
+    const double2* __restrict__ term, double* __restrict__ g, double* __restrict__ u) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const uint64_t k = (uint64_t)cb + j;
+  if (k >= ce || k >= ndict) return;
+  if (!active[k]) {
+    g[j] = u[j] = inactive_value();
+    return;
+  }
+  uint32_t b, e;
+  run_of_key(k, ndict, dict_run, run_start, n_uniq, n, &b, &e);
+  if (e - b > kLongRun) return;  // darling_sum_long_kernel's
+  double ag = 0.0, au = 0.0;
+  for (uint32_t i = b; i < e; ++i) {
+    const double2 t = term[i];
+    ag = ag + t.x;
+    au = au + t.y;
+  }
+  g[j] = ag;
+  u[j] = au;
+}
+
+// chain_sum over pairs of terms: one load and one LDS read bring both terms
+// of a sorted pair, and each has its own accumulator, so the two add chains
+// overlap.  A load is 16 B per lane here, so half as many are kept ahead.
+// stage: 64 x kChainAhead2 double2 of the wave.
+#ifndef PSG_CHAIN_AHEAD2
+#define PSG_CHAIN_AHEAD2 4
+#endif
+constexpr int kChainAhead2 = PSG_CHAIN_AHEAD2;
+__device__ __forceinline__ double2 chain_sum2(const double2* __restrict__ term, uint32_t lb,
+                                              uint32_t le, uint32_t lane, double2* stage) {
+  constexpr int kSpan = 64 * kChainAhead2;
+  const double2 zero = make_double2(0.0, 0.0);
+  double a0 = 0.0, a1 = 0.0;
+  double c0[kChainAhead2], c1[kChainAhead2], n0[kChainAhead2], n1[kChainAhead2];
+#pragma unroll
+  for (int u = 0; u < kChainAhead2; ++u) {
+    const uint64_t i = (uint64_t)lb + (uint64_t)u * 64u + lane;
+    const double2 t = i < le ? term[i] : zero;
+    c0[u] = t.x;
+    c1[u] = t.y;
+    n0[u] = n1[u] = 0.0;
+  }
+  for (uint64_t base = lb; base < le; base += kSpan) {
+    const uint64_t ahead = base + kSpan;
+    if (ahead < le) {
+#pragma unroll
+      for (int u = 0; u < kChainAhead2; ++u) {
+        const uint64_t i = ahead + (uint64_t)u * 64u + lane;
+        const double2 t = i < le ? term[i] : zero;
+        n0[u] = t.x;
+        n1[u] = t.y;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int u = 0; u < kChainAhead2; ++u) stage[u * 64 + lane] = make_double2(c0[u], c1[u]);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (le - base >= (uint64_t)kSpan) {
+#pragma unroll 32
+      for (int j = 0; j < kSpan; ++j) {
+        const double2 t = stage[j];
+        a0 = a0 + t.x;
+        a1 = a1 + t.y;
+      }
+    } else {
+      const int cnt = (int)(le - base);
+      for (int j = 0; j < cnt; ++j) {
+        const double2 t = stage[j];
+        a0 = a0 + t.x;
+        a1 = a1 + t.y;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kChainAhead2; ++u) {
+      c0[u] = n0[u];
+      c1[u] = n1[u];
+    }
+  }
+  return make_double2(a0, a1);
+}
+
+// wave w of the launch takes long_list[w], [w + waves], ... and keeps the
+// active keys of [cb, ce): the list is the dictionary's, in no order, so
+// every block's launch walks all of it (the host sizes the grid by its
+// length: a few entries per wave)
+__global__ __launch_bounds__(256) void darling_sum_long_kernel(
+    const uint32_t* __restrict__ long_list, const uint32_t* __restrict__ count,
+    const uint32_t* __restrict__ dict_run, uint32_t ndict, const uint32_t* __restrict__ run_start,
+    uint32_t n_uniq, uint32_t n, const uint8_t* __restrict__ active, uint32_t cb, uint32_t ce,
+    const double2* __restrict__ term, double* __restrict__ g, double* __restrict__ u) {
+  __shared__ double2 stage[4][64 * kChainAhead2];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6), waves = gridDim.x * 4u;
+  const uint32_t nl = *count < ndict ? *count : ndict;
+  for (uint32_t j = wave; j < nl; j += waves) {
+    const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)long_list[j]);
+    if (k < cb || k >= ce || k >= ndict || !active[k]) continue;
+    uint32_t b, e;
+    run_of_key(k, ndict, dict_run, run_start, n_uniq, n, &b, &e);
+    b = (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+    e = (uint32_t)__builtin_amdgcn_readfirstlane((int)e);
+    const double2 a = chain_sum2(term, b, e, lane, stage[threadIdx.x >> 6]);
+    if (lane == 0) {
+      g[k - cb] = a.x;
+      u[k - cb] = a.y;
+    }
+  }
+}
+
+// darling.cc:364-378 for columns [cb, ce); new_w[j] is column cb + j's
+__global__ __launch_bounds__(256) void darling_state_kernel(
+    const double* __restrict__ new_w, uint32_t cb, uint32_t ce, double delta_max,
+    double* __restrict__ cur_w, double* __restrict__ delta, uint8_t* __restrict__ active,
+    double* __restrict__ delta_w) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const uint64_t k = (uint64_t)cb + j;
+  if (k >= ce) return;
+  const double nw = new_w[j];
+  if (nw != nw) {  // inactive(nw), darling.h:35
+    active[k] = 0;
+    cur_w[k] = 0;
+    delta_w[k] = 0;
+    return;
+  }
+  const double dw = nw - cur_w[k];
+  delta_w[k] = dw;
+  delta[k] = std_min(delta_max, 2 * fabs(dw) + .1);  // newDelta, darling.h:31-33
+  cur_w[k] = nw;
+}
+
+// the factor of every sorted pair in [lo, hi) (darling.cc:432); -1.0, which
+// exp never gives, for a pair of a column that contributes nothing (:424)
+template <bool kBinary>
+__global__ __launch_bounds__(256) void darling_factor_kernel(
+    const uint32_t* __restrict__ spos, const uint32_t* __restrict__ row_of,
+    const uint32_t* __restrict__ run_of, const uint32_t* __restrict__ run_rank,
+    const double* __restrict__ value, const double* __restrict__ y,
+    const double* __restrict__ delta_w, const uint8_t* __restrict__ active, uint32_t lo,
+    uint32_t hi, uint32_t n, uint32_t n_uniq, uint32_t ndict, double* __restrict__ factor) {
+  const uint64_t i = (uint64_t)lo + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (i >= hi || i >= n) return;
+  uint32_t k, p;
+  if (!pair_key(run_of, run_rank, i, n_uniq, ndict, &k)) return;  // in no row's list
+  const double wd = delta_w[k];
+  if (wd == 0 || !active[k]) {
+    factor[i] = -1.0;
+    return;
+  }
+  const uint32_t row = pair_row(spos, row_of, i, n, &p);
+  factor[i] = kBinary ? exp(y[row] * wd) : exp(y[row] * wd * value[p]);
+}
+
+// one lane per row: the row's list holds its sorted pairs in ascending
+// index; those in [lo, hi) are the block's, and their factors multiply into
+// dual[row] in that order.  A row no factor touches is not written.
+__global__ __launch_bounds__(256) void darling_rows_kernel(
+    const uint32_t* __restrict__ row_start, const uint32_t* __restrict__ row_pair, uint32_t rows,
+    uint32_t lo, uint32_t hi, uint32_t n, const double* __restrict__ factor,
+    double* __restrict__ dual) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (r >= rows) return;
+  const uint32_t e = row_start[r + 1] < n ? row_start[r + 1] : n;
+  uint32_t a = row_start[r] < e ? row_start[r] : e, z = e;
+  while (a < z) {  // the first entry at or past lo
+    const uint32_t mid = a + (z - a) / 2;
+    if (row_pair[mid] < lo) {
+      a = mid + 1;
+    } else {
+      z = mid;
+    }
+  }
+  double d = 0.0;
+  bool touched = false;
+  for (uint32_t j = a; j < e; ++j) {
+    const uint32_t i = row_pair[j];
+    if (i >= hi || i >= n) break;
+    const double f = factor[i];
+    if (f == -1.0) continue;
+    if (!touched) d = dual[r];
+    touched = true;
+    d = d * f;
+  }
+  if (touched) dual[r] = d;
+}
+
+// log(1 + 1 / dual) per row (darling.cc:506); partial as in logit_kernel
+__global__ __launch_bounds__(256) void darling_objv_kernel(const double* __restrict__ dual,
+                                                           uint32_t rows,
+                                                           double* __restrict__ partial) {
+  __shared__ double s[256];
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  s[threadIdx.x] = i < rows ? log(1 + 1 / dual[i]) : 0.0;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
+}
+
 inline uint32_t blocks_of(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
 
 }  // namespace
@@ -659,7 +993,10 @@ enum BufId {
   B_OFFSET, B_INDEX, B_VALUE, B_Y, B_KEY_A, B_KEY_B, B_POS_A, B_POS_B, B_COUNTS, B_TILE_SUM,
   B_UNIQ_KEY, B_KEY_CNT, B_RUN_START, B_RUN_OF, B_ROW_OF, B_RUN_RANK, B_REMAPPED, B_BEFORE,
   B_NEW_OFFSET, B_NEW_INDEX, B_NEW_VALUE, B_DICT_RUN, B_CNT_POS, B_CNT_NEG, B_XW, B_TAU, B_C,
-  B_LOSS, B_PARTIAL, B_GRAD, B_TERM, B_LONG_LIST, B_SCRATCH0, B_SCRATCH1, B_SCRATCH2, B_SCRATCH3, B_COUNT
+  B_LOSS, B_PARTIAL, B_GRAD, B_TERM, B_LONG_LIST, B_SCRATCH0, B_SCRATCH1, B_SCRATCH2, B_SCRATCH3,
+  // (g): the Darling worker's state, its second term array and the rows' lists
+  B_DUAL, B_CUR_W, B_DELTA, B_ACTIVE, B_DELTA_W, B_EXP_DELTA, B_TERM2, B_RKEY_A, B_RKEY_B,
+  B_RPOS_A, B_RPOS_B, B_ROW_START, B_COL_RANGE, B_COUNT
 };
 
 // device words: [0] OR of the keys, [1] AND, [2] dictionary order violations,
@@ -683,6 +1020,15 @@ struct psg_minibatch {
   uint64_t differ = 0;  // the key bits that differ between some two keys
   const uint64_t* skey = nullptr;  // the sorted pairs (one side of the ping-pong)
   const uint32_t* spos = nullptr;
+  // (g): set by psg_mb_darling_init, cleared by psg_mb_load and psg_mb_localize
+  bool darling = false;
+  const uint32_t* row_pair = nullptr;  // the rows' lists (one side of their ping-pong)
+  // host: pair_lo[k] = the first sorted pair of the first of keys k, k + 1, ...
+  // that has a run (nnz: none); pair_hi[k] = the end of the last run among
+  // keys 0 .. k - 1 (0: none).  Block [cb, ce) is pairs [pair_lo[cb], pair_hi[ce]).
+  std::vector<uint32_t> pair_lo, pair_hi;
+  size_t n_long = 0;  // the length of the long-run list, read at psg_mb_darling_init
+  size_t last_cb = 0, last_ce = 0;  // the columns of the last psg_mb_darling_update_dual
   struct Buf {
     void* p = nullptr;
     size_t cap = 0;
@@ -749,26 +1095,28 @@ int launched(const char* what) {
   return PSG_OK;
 }
 
-// (a): the sorted pairs end in mb->skey / mb->spos
-int enqueue_sort(psg_minibatch* mb, hipStream_t s) {
+// the nnz keys `kin` (which may be the key_b block) stably sorted on the
+// digits that `differ` names, through the blocks key_a / key_b / pos_a / pos_b
+int enqueue_sort_keys(psg_minibatch* mb, const uint64_t* kin, uint64_t differ, int key_a,
+                      int key_b, int pos_a, int pos_b, const uint64_t** skey,
+                      const uint32_t** spos, hipStream_t s) {
   const uint32_t n = (uint32_t)mb->nnz, ntiles = blocks_of(n, kSortTile);
-  const uint64_t* kin = mb->at<uint64_t>(B_INDEX);
   const uint32_t* pin = nullptr;
-  uint64_t* kout = mb->at<uint64_t>(B_KEY_A);
-  uint32_t* pout = mb->at<uint32_t>(B_POS_A);
+  uint64_t* kout = mb->at<uint64_t>(key_a);
+  uint32_t* pout = mb->at<uint32_t>(pos_a);
   uint32_t* counts = mb->at<uint32_t>(B_COUNTS);
   bool any = false;
   for (int d = 0; d < 8; ++d) {
-    if (((mb->differ >> (8 * d)) & 255u) == 0) continue;  // the same digit in every key
+    if (((differ >> (8 * d)) & 255u) == 0) continue;  // the same digit in every key
     LAUNCH(sort_count_kernel, ntiles, s, kin, n, 8 * d, counts, ntiles);
     LAUNCH(row_scan_kernel, 256, s, counts, ntiles, mb->d_dtotal());
     LAUNCH(sort_scatter_kernel, ntiles, s, kin, pin, kout, pout, n, 8 * d, counts,
            mb->d_dtotal(), ntiles);
     kin = kout;
     pin = pout;
-    const bool to_b = kout == mb->at<uint64_t>(B_KEY_A);
-    kout = mb->at<uint64_t>(to_b ? B_KEY_B : B_KEY_A);
-    pout = mb->at<uint32_t>(to_b ? B_POS_B : B_POS_A);
+    const bool to_b = kout == mb->at<uint64_t>(key_a);
+    kout = mb->at<uint64_t>(to_b ? key_b : key_a);
+    pout = mb->at<uint32_t>(to_b ? pos_b : pos_a);
     any = true;
   }
   if (!any) {
@@ -776,9 +1124,15 @@ int enqueue_sort(psg_minibatch* mb, hipStream_t s) {
     pin = pout;
     kin = kout;
   }
-  mb->skey = kin;
-  mb->spos = pin;
+  *skey = kin;
+  *spos = pin;
   return launched("sort");
+}
+
+// (a): the sorted pairs end in mb->skey / mb->spos
+int enqueue_sort(psg_minibatch* mb, hipStream_t s) {
+  return enqueue_sort_keys(mb, mb->at<uint64_t>(B_INDEX), mb->differ, B_KEY_A, B_KEY_B, B_POS_A,
+                           B_POS_B, &mb->skey, &mb->spos, s);
 }
 
 size_t elem_size(int what) {
@@ -792,6 +1146,8 @@ size_t elem_size(int what) {
     case PSG_MB_REMAPPED:
     case PSG_MB_ROW_OF:
       return 4;
+    case PSG_MB_DARLING_ACTIVE:
+      return 1;
     default:
       return 8;
   }
@@ -857,6 +1213,7 @@ int psg_mb_load(psg_minibatch* mb, const uint64_t* offset, size_t rows, const ui
   HIP_TRY(hipSetDevice(mb->device));
   if (int rc = mb->settle()) return rc;  // the previous minibatch's work
   mb->state = S_NEW;
+  mb->darling = false;
   const size_t n = (size_t)nnz, ntiles = blocks_of(n, kSortTile);
   struct {
     int id;
@@ -959,6 +1316,7 @@ int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
   hipStream_t s = mb->pick(stream);
   if (int rc = mb->order(s)) return rc;
   mb->state = S_UNIQ;
+  mb->darling = false;
   const uint32_t n = (uint32_t)mb->nnz, nu = (uint32_t)mb->n_uniq, nd = (uint32_t)ndict;
   const uint32_t rows = (uint32_t)mb->rows;
   uint32_t* before = mb->at<uint32_t>(B_BEFORE);
@@ -1148,7 +1506,7 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
   if (!mb || !n_out) return fail(PSG_ERR_ARG, "null argument");
   *n_out = 0;
   int need_state, id;
-  size_t n;
+  size_t n, first = 0;  // first: the element the array starts at in its block
   const size_t kept_unknown = ~(size_t)0;
   switch (what) {
     case PSG_MB_SORTED_KEY: need_state = S_UNIQ; id = -1; n = mb->nnz; break;
@@ -1171,8 +1529,17 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
     case PSG_MB_SCRATCH + 3:
       need_state = S_NEW; id = B_SCRATCH0 + (what - PSG_MB_SCRATCH);
       n = mb->scratch_len[what - PSG_MB_SCRATCH] / 8; break;
+    case PSG_MB_DARLING_DUAL: need_state = S_LOCAL; id = B_DUAL; n = mb->rows; break;
+    case PSG_MB_DARLING_CUR_W: need_state = S_LOCAL; id = B_CUR_W; n = mb->ndict; break;
+    case PSG_MB_DARLING_DELTA: need_state = S_LOCAL; id = B_DELTA; n = mb->ndict; break;
+    case PSG_MB_DARLING_ACTIVE: need_state = S_LOCAL; id = B_ACTIVE; n = mb->ndict; break;
+    case PSG_MB_DARLING_DELTA_W:
+      need_state = S_LOCAL; id = B_DELTA_W; n = mb->last_ce - mb->last_cb; first = mb->last_cb;
+      break;
     default: return fail(PSG_ERR_ARG, "psg_mb_read: array %d", what);
   }
+  if (what >= PSG_MB_DARLING_DUAL && !mb->darling)
+    return fail(PSG_ERR_ARG, "psg_mb_read: array %d before psg_mb_darling_init", what);
   if (mb->state < need_state)
     return fail(PSG_ERR_ARG, "psg_mb_read: array %d is not computed yet", what);
   HIP_TRY(hipSetDevice(mb->device));
@@ -1197,7 +1564,245 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
   if (!out) return fail(PSG_ERR_ARG, "null output");
   const void* src = id == -1 ? (const void*)mb->skey
                              : id == -2 ? (const void*)mb->spos : (const void*)mb->b[id].p;
-  HIP_TRY(hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, (const char*)src + first * elem_size(what), bytes,
+                    hipMemcpyDeviceToHost));
+  return PSG_OK;
+}
+
+// ---- (g): the Darling worker ------------------------------------------------
+namespace {
+
+int darling_ready(psg_minibatch* mb, const char* who) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_LOCAL || !mb->darling)
+    return fail(PSG_ERR_ARG, "%s before psg_mb_darling_init", who);
+  return PSG_OK;
+}
+
+int darling_block(psg_minibatch* mb, size_t cb, size_t ce, const char* who, uint32_t* lo,
+                  uint32_t* hi) {
+  if (cb > ce || ce > mb->ndict)
+    return fail(PSG_ERR_ARG, "%s: columns [%zu, %zu) of %zu", who, cb, ce, mb->ndict);
+  *lo = *hi = 0;
+  if (cb < ce) {
+    *lo = mb->pair_lo[cb];
+    *hi = std::max(mb->pair_hi[ce], *lo);
+  }
+  return PSG_OK;
+}
+
+}  // namespace
+
+int psg_mb_darling_init(psg_minibatch* mb, double delta_init, const double* w_dev,
+                        void* stream) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_LOCAL) return fail(PSG_ERR_ARG, "psg_mb_darling_init before psg_mb_localize");
+  HIP_TRY(hipSetDevice(mb->device));
+  mb->darling = false;
+  const size_t rows_z = mb->rows, n_z = mb->nnz, nd_z = mb->ndict;
+  struct {
+    int id;
+    size_t bytes;
+  } const want[] = {
+      {B_DUAL, 8 * rows_z}, {B_CUR_W, 8 * nd_z}, {B_DELTA, 8 * nd_z}, {B_ACTIVE, nd_z},
+      {B_DELTA_W, 8 * nd_z}, {B_EXP_DELTA, mb->binary ? 8 * nd_z : 0}, {B_TERM2, 16 * n_z},
+      {B_RKEY_A, 8 * n_z}, {B_RKEY_B, 8 * n_z}, {B_RPOS_A, 4 * n_z}, {B_RPOS_B, 4 * n_z},
+      {B_ROW_START, 4 * (rows_z + 1)}, {B_COL_RANGE, 8 * nd_z}};
+  for (const auto& w : want)
+    if (int rc = mb->need(w.id, w.bytes)) return rc;
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  const uint32_t n = (uint32_t)n_z, nd = (uint32_t)nd_z, nu = (uint32_t)mb->n_uniq;
+  const uint32_t rows = (uint32_t)rows_z;
+  double* dual = mb->at<double>(B_DUAL);
+  // dual_ = exp(y .* (X w)), darling.cc:110; the worker's copy of w
+  if (rows) {
+    if (w_dev) {
+      if (int rc = enqueue_times(mb, w_dev, dual, s)) return rc;
+      LAUNCH(dual_init_kernel, blocks_of(rows, 256), s, mb->at<double>(B_Y), rows, dual);
+    } else {
+      LAUNCH(fill_kernel, blocks_of(rows, 256), s, dual, rows, 1.0);
+    }
+  }
+  if (nd) {
+    if (w_dev)
+      HIP_TRY(hipMemcpyAsync(mb->b[B_CUR_W].p, w_dev, 8 * nd_z, hipMemcpyDeviceToDevice, s));
+    else
+      HIP_TRY(hipMemsetAsync(mb->b[B_CUR_W].p, 0, 8 * nd_z, s));
+    HIP_TRY(hipMemsetAsync(mb->b[B_DELTA_W].p, 0, 8 * nd_z, s));
+    HIP_TRY(hipMemsetAsync(mb->b[B_ACTIVE].p, 1, nd_z, s));  // :114
+    LAUNCH(fill_kernel, blocks_of(nd, 256), s, mb->at<double>(B_DELTA), nd, delta_init);  // :116
+    LAUNCH(col_range_kernel, blocks_of(nd, 256), s, mb->at<uint32_t>(B_DICT_RUN), nd,
+           mb->at<uint32_t>(B_RUN_START), nu, n, mb->at<uint32_t>(B_COL_RANGE));
+  }
+  // the rows' lists: the sorted pairs, stably sorted by row
+  mb->row_pair = nullptr;
+  if (n) {
+    uint64_t* rkey = mb->at<uint64_t>(B_RKEY_B);
+    LAUNCH(row_key_kernel, blocks_of(n, 256), s, mb->spos, mb->at<uint32_t>(B_ROW_OF),
+           mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK), n, nu, nd, rows, rkey);
+    uint64_t differ = 1;  // the keys are 0 .. rows: the bits up to rows' highest
+    while (differ <= rows) differ <<= 1;
+    const uint64_t* sorted_row = nullptr;
+    if (int rc = enqueue_sort_keys(mb, rkey, differ - 1, B_RKEY_A, B_RKEY_B, B_RPOS_A, B_RPOS_B,
+                                   &sorted_row, &mb->row_pair, s))
+      return rc;
+    LAUNCH(row_start_kernel, blocks_of((uint64_t)rows + 1, 256), s, sorted_row, n, rows,
+           mb->at<uint32_t>(B_ROW_START));
+  } else {
+    HIP_TRY(hipMemsetAsync(mb->b[B_ROW_START].p, 0, 4 * (rows_z + 1), s));
+  }
+  if (int rc = launched("darling init")) return rc;
+  if (int rc = mb->mark(s)) return rc;
+  // every block's range of sorted pairs, kept on the host: a block's launches
+  // are sized by it
+  std::vector<uint32_t> range;
+  try {
+    range.resize(2 * nd_z);
+    mb->pair_lo.resize(nd_z + 1);
+    mb->pair_hi.resize(nd_z + 1);
+  } catch (const std::bad_alloc&) {
+    return fail(PSG_ERR_OOM, "host allocation");
+  }
+  HIP_TRY(hipMemcpyAsync(mb->h_small + 2, mb->d_small + 2, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(mb->h_small + 5, mb->d_small + 5, 8, hipMemcpyDeviceToHost, s));
+  if (nd)
+    HIP_TRY(hipMemcpyAsync(range.data(), mb->b[B_COL_RANGE].p, 8 * nd_z, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (int rc = report_dict(mb, mb->h_small[2])) return rc;
+  mb->pair_lo[nd_z] = n;
+  for (size_t k = nd_z; k-- > 0;)
+    mb->pair_lo[k] = range[2 * k] < range[2 * k + 1] ? range[2 * k] : mb->pair_lo[k + 1];
+  mb->pair_hi[0] = 0;
+  for (size_t k = 0; k < nd_z; ++k)
+    mb->pair_hi[k + 1] = range[2 * k] < range[2 * k + 1] ? range[2 * k + 1] : mb->pair_hi[k];
+  mb->n_long = std::min<size_t>((uint32_t)(mb->h_small[5] & 0xffffffffu), nd_z);
+  mb->last_cb = mb->last_ce = 0;
+  mb->darling = true;
+  return PSG_OK;
+}
+
+int psg_mb_darling_reset_active(psg_minibatch* mb, void* stream) {
+  if (int rc = darling_ready(mb, "psg_mb_darling_reset_active")) return rc;
+  HIP_TRY(hipSetDevice(mb->device));
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  if (mb->ndict) HIP_TRY(hipMemsetAsync(mb->b[B_ACTIVE].p, 1, mb->ndict, s));
+  return mb->mark(s);
+}
+
+int psg_mb_darling_gradients(psg_minibatch* mb, size_t cb, size_t ce, double* g_dev,
+                             double* u_dev, void* stream) {
+  if (int rc = darling_ready(mb, "psg_mb_darling_gradients")) return rc;
+  uint32_t lo, hi;
+  if (int rc = darling_block(mb, cb, ce, "psg_mb_darling_gradients", &lo, &hi)) return rc;
+  if (cb < ce && (!g_dev || !u_dev)) return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(mb->device));
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  if (cb == ce) return mb->mark(s);
+  const uint32_t n = (uint32_t)mb->nnz, nd = (uint32_t)mb->ndict, nu = (uint32_t)mb->n_uniq;
+  const uint32_t b = (uint32_t)cb, e = (uint32_t)ce;
+  const uint8_t* active = mb->at<uint8_t>(B_ACTIVE);
+  double2* term = mb->at<double2>(B_TERM2);
+  if (mb->binary)
+    LAUNCH(exp_delta_kernel, blocks_of(e - b, 256), s, mb->at<double>(B_DELTA), active, b, e,
+           mb->at<double>(B_EXP_DELTA));
+  if (hi > lo) {
+    if (mb->binary)
+      LAUNCH(darling_terms_kernel<true>, blocks_of(hi - lo, 256), s, mb->spos,
+             mb->at<uint32_t>(B_ROW_OF), mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK),
+             (const double*)nullptr, mb->at<double>(B_Y), mb->at<double>(B_DUAL),
+             mb->at<double>(B_EXP_DELTA), active, lo, hi, n, nu, nd, term);
+    else
+      LAUNCH(darling_terms_kernel<false>, blocks_of(hi - lo, 256), s, mb->spos,
+             mb->at<uint32_t>(B_ROW_OF), mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK),
+             mb->at<double>(B_VALUE), mb->at<double>(B_Y), mb->at<double>(B_DUAL),
+             mb->at<double>(B_DELTA), active, lo, hi, n, nu, nd, term);
+  }
+  LAUNCH(darling_sum_short_kernel, blocks_of(e - b, 256), s, mb->at<uint32_t>(B_DICT_RUN), nd,
+         mb->at<uint32_t>(B_RUN_START), nu, n, active, b, e, term, g_dev, u_dev);
+  if (hi - lo > kLongRun && mb->n_long)
+    LAUNCH(darling_sum_long_kernel, std::min<uint32_t>(blocks_of(mb->n_long, 4), kLongGrid), s,
+           mb->at<uint32_t>(B_LONG_LIST), (const uint32_t*)(mb->d_small + 5),
+           mb->at<uint32_t>(B_DICT_RUN), nd, mb->at<uint32_t>(B_RUN_START), nu, n, active, b, e,
+           term, g_dev, u_dev);
+  if (int rc = launched("darling gradients")) return rc;
+  return mb->mark(s);
+}
+
+int psg_mb_darling_update_dual(psg_minibatch* mb, size_t cb, size_t ce, const double* new_w_dev,
+                               double delta_max, void* stream) {
+  if (int rc = darling_ready(mb, "psg_mb_darling_update_dual")) return rc;
+  uint32_t lo, hi;
+  if (int rc = darling_block(mb, cb, ce, "psg_mb_darling_update_dual", &lo, &hi)) return rc;
+  if (cb < ce && !new_w_dev) return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(mb->device));
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  mb->last_cb = cb;
+  mb->last_ce = ce;
+  if (cb == ce) return mb->mark(s);
+  const uint32_t n = (uint32_t)mb->nnz, nd = (uint32_t)mb->ndict, nu = (uint32_t)mb->n_uniq;
+  const uint32_t rows = (uint32_t)mb->rows;
+  uint8_t* active = mb->at<uint8_t>(B_ACTIVE);
+  double* factor = mb->at<double>(B_TERM);
+  LAUNCH(darling_state_kernel, blocks_of(ce - cb, 256), s, new_w_dev, (uint32_t)cb, (uint32_t)ce,
+         delta_max, mb->at<double>(B_CUR_W), mb->at<double>(B_DELTA), active,
+         mb->at<double>(B_DELTA_W));
+  if (hi > lo && rows) {
+    if (mb->binary)
+      LAUNCH(darling_factor_kernel<true>, blocks_of(hi - lo, 256), s, mb->spos,
+             mb->at<uint32_t>(B_ROW_OF), mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK),
+             (const double*)nullptr, mb->at<double>(B_Y), mb->at<double>(B_DELTA_W), active, lo,
+             hi, n, nu, nd, factor);
+    else
+      LAUNCH(darling_factor_kernel<false>, blocks_of(hi - lo, 256), s, mb->spos,
+             mb->at<uint32_t>(B_ROW_OF), mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK),
+             mb->at<double>(B_VALUE), mb->at<double>(B_Y), mb->at<double>(B_DELTA_W), active, lo,
+             hi, n, nu, nd, factor);
+    LAUNCH(darling_rows_kernel, blocks_of(rows, 256), s, mb->at<uint32_t>(B_ROW_START),
+           mb->row_pair, rows, lo, hi, n, factor, mb->at<double>(B_DUAL));
+  }
+  if (int rc = launched("darling update_dual")) return rc;
+  return mb->mark(s);
+}
+
+int psg_mb_darling_objv(psg_minibatch* mb, double* objv, void* stream) {
+  if (int rc = darling_ready(mb, "psg_mb_darling_objv")) return rc;
+  if (!objv) return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(hipSetDevice(mb->device));
+  hipStream_t s = mb->pick(stream);
+  if (int rc = mb->order(s)) return rc;
+  const uint32_t rows = (uint32_t)mb->rows, nparts = blocks_of(rows, 256);
+  if (rows)
+    LAUNCH(darling_objv_kernel, nparts, s, mb->at<double>(B_DUAL), rows,
+           mb->at<double>(B_PARTIAL));
+  LAUNCH(objv_kernel, 1, s, mb->at<double>(B_PARTIAL), nparts, (double*)(mb->d_small + 3));
+  if (int rc = launched("darling objv")) return rc;
+  if (int rc = mb->mark(s)) return rc;
+  HIP_TRY(hipMemcpyAsync(mb->h_small + 3, mb->d_small + 3, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  memcpy(objv, mb->h_small + 3, 8);
+  return PSG_OK;
+}
+
+int psg_mb_darling_set_state(psg_minibatch* mb, const double* dual, const double* cur_w,
+                             const double* delta, const uint8_t* active) {
+  if (int rc = darling_ready(mb, "psg_mb_darling_set_state")) return rc;
+  HIP_TRY(hipSetDevice(mb->device));
+  if (int rc = mb->settle()) return rc;
+  if (dual && mb->rows)
+    HIP_TRY(hipMemcpy(mb->b[B_DUAL].p, dual, 8 * mb->rows, hipMemcpyHostToDevice));
+  if (cur_w && mb->ndict)
+    HIP_TRY(hipMemcpy(mb->b[B_CUR_W].p, cur_w, 8 * mb->ndict, hipMemcpyHostToDevice));
+  if (delta && mb->ndict)
+    HIP_TRY(hipMemcpy(mb->b[B_DELTA].p, delta, 8 * mb->ndict, hipMemcpyHostToDevice));
+  if (active && mb->ndict) {
+    for (size_t k = 0; k < mb->ndict; ++k)
+      if (active[k] > 1) return fail(PSG_ERR_ARG, "active[%zu] = %u, not 0 or 1", k, active[k]);
+    HIP_TRY(hipMemcpy(mb->b[B_ACTIVE].p, active, mb->ndict, hipMemcpyHostToDevice));
+  }
   return PSG_OK;
 }
 
