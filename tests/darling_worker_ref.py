@@ -187,7 +187,8 @@ def vector_gradients(new_offset, new_index, new_value, p, y, dual, delta, active
 
 
 def vector_update_dual(new_offset, new_index, new_value, p, y, dual, cur_w, delta, active, cb, ce,
-                       new_w, delta_max):
+                       new_w, delta_max, reverse=False):
+    """reverse: each row's factors backwards (the order-sensitivity guard)."""
     row, val, start, col = _csc(new_offset, new_index, new_value, p)
     y, dual = np.asarray(y, np.float64), np.array(dual, np.float64)
     cur_w, delta = np.array(cur_w, np.float64), np.array(delta, np.float64)
@@ -214,7 +215,8 @@ def vector_update_dual(new_offset, new_index, new_value, p, y, dual, cur_w, delt
     f = f[by_row]
     with np.errstate(all="ignore"):
         for i in np.nonzero(np.diff(rs))[0]:
-            dual[i] = np.multiply.accumulate(np.concatenate([[dual[i]], f[rs[i]:rs[i + 1]]]))[-1]
+            fi = f[rs[i]:rs[i + 1]][::-1] if reverse else f[rs[i]:rs[i + 1]]
+            dual[i] = np.multiply.accumulate(np.concatenate([[dual[i]], fi]))[-1]
     return dual, cur_w, delta, active, delta_w, np.diff(rs)
 
 
@@ -306,12 +308,56 @@ def case(binary, emax=20, seed=1):
         index.append(ids[rng.permutation(ids.size)] if r % 2 else np.sort(ids))
     offset = np.concatenate([[0], np.cumsum([a.size for a in index])]).astype(np.uint64)
     index = np.concatenate(index).astype(np.uint64)
-    value = None
-    if not binary:
-        value = (rng.choice([-1.0, 1.0], size=index.size) * (0.5 + rng.random(index.size))
-                 * np.exp2(rng.integers(-4, emax + 1, size=index.size).astype(np.float64)))
+    value = None if binary else values(rng, index.size, emax)
     y = rng.choice([-1.0, 1.0], size=ROWS)
     return offset, index, value, y, dic
+
+
+def values(rng, n, emax):
+    """+-[0.5, 1.5) 2^e, e in -4 .. emax."""
+    return (rng.choice([-1.0, 1.0], size=n) * (0.5 + rng.random(n))
+            * np.exp2(rng.integers(-4, emax + 1, size=n).astype(np.float64)))
+
+
+SEAM_SEED, SEAM_EMAX = 29, 2
+
+
+def seam_case(tile):
+    """(offset, index, value, y, dic): worker_ref.seam_case's structure (its
+    docstring says what it reaches) with this module's values, e in -4 ..
+    SEAM_EMAX so that G and U stay finite, against worker_ref.seam_dict."""
+    import worker_ref as R
+    offset, index, value, y = R.seam_case(
+        tile, SEAM_SEED, values=lambda rng, n: values(rng, n, SEAM_EMAX))
+    return offset, index, value, y, R.seam_dict(index)
+
+
+ROW_COUNTS = (255, 256, 65535, 65536)  # 1, 2, 2 and 3 digit passes of the sort by row
+
+
+def row_case(rows, seed=37):
+    """(offset, index, value, y, dic): some hundred pairs over 40 keys in
+    `rows` rows, most of them empty; the first row, the last and one in the
+    middle hold 12 factors each, 60 others 1 .. 5."""
+    rng = np.random.default_rng(seed + rows)
+    dic = np.sort(rng.choice(np.arange(1, 1 << 20, dtype=np.uint64), size=40, replace=False)
+                  ) * np.uint64(0x000003FFFF000001) + np.uint64(1 << 40)
+    lens = np.zeros(rows, np.int64)
+    lens[rng.choice(np.arange(1, rows - 1), size=60, replace=False)] = rng.integers(1, 6, size=60)
+    lens[[0, rows // 2, rows - 1]] = 12
+    index = dic[rng.integers(0, dic.size, size=int(lens.sum()))]
+    offset = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    return offset, index, values(rng, index.size, 1), rng.choice([-1.0, 1.0], size=rows), dic
+
+
+def row_case_update(rows):
+    """(dual, cur_w, delta, active, new_w) for one update_dual over all the
+    columns of row_case(rows): steps of some tenths, so that the factors'
+    mantissas are arbitrary and their order shows in the product."""
+    rng = np.random.default_rng(1000 + rows)
+    cur_w = rng.standard_normal(40)
+    return (spread_dual(rng, rows), cur_w, rng.uniform(0.1, 3.0, 40), np.ones(40, np.uint8),
+            cur_w + rng.standard_normal(40) * 0.3)
 
 
 def localized(offset, index, value, dic):

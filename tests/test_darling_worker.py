@@ -111,6 +111,32 @@ def test_forms_agree_on_init_and_objv():
     assert D.scalar_objv(np.ones(4)) == 4 * np.log(2.0)
 
 
+@pytest.mark.parametrize("rows", D.ROW_COUNTS)
+def test_row_cases_tell_the_order_of_a_rows_factors(rows):
+    """The cases of the sort by row (1, 2, 2 and 3 digit passes): the forms
+    agree, the three full rows are where the docstring puts them, and
+    multiplying a row's factors backwards changes the bits of some row."""
+    offset, index, value, y, dic = D.row_case(rows)
+    z = D.localized(offset, index, value, dic)
+    passes = sum(1 for d in range(8) if ((1 << rows.bit_length()) - 1) >> (8 * d) & 0xFF)
+    assert passes == {255: 1, 256: 2, 65535: 2, 65536: 3}[rows]
+    lens = np.diff(offset.astype(np.int64))
+    assert 100 <= index.size <= 400 and np.mean(lens == 0) > 0.7
+    assert lens[0] == lens[rows // 2] == lens[-1] == 12 and np.sum(lens > 0) == 63
+    dual, cur_w, delta, active, nw = D.row_case_update(rows)
+    args = (dic.size, y, dual, cur_w, delta, active, 0, dic.size, nw, DELTA_MAX)
+    a = D.scalar_update_dual(D.scalar_columns(*z, dic.size), False, y, *args[2:])
+    b = D.vector_update_dual(*z, *args)
+    for x, w in zip(a, b):
+        assert same(x, np.asarray(w, x.dtype) if x.dtype != np.float64 else w)
+    r = D.vector_update_dual(*z, *args, reverse=True)
+    changed = D.bits(b[0]) != D.bits(r[0])
+    print("rows %d: %d of %d rows with factors change when reversed"
+          % (rows, changed.sum(), (b[5] > 0).sum()))
+    assert changed.any() and np.isfinite(b[0]).all() and b[0].min() > 1e-300
+    assert same(b[0][b[5] == 0], dual[b[5] == 0]) and (b[5] == 0).sum() >= rows - 63
+
+
 REVERSED_SHARE = 0.30
 
 

@@ -15,7 +15,8 @@ at most 2 x 2^-52 relatively, and every rounded operation after that adds
   objv  (rows + 1) 2^-53 objv for the reduction + 2 x 2^-52 x each row's term
 
 The largest fraction of each bound seen on an MI355X is recorded in DESIGN.md
-section 7.  One context, one server and one worker handle serve the module."""
+section 7.  One context, one server and one worker handle serve the module;
+the seam case has a worker of its own, which it closes."""
 import ctypes as C
 import functools
 import math
@@ -253,6 +254,114 @@ def test_repeatable(worker, binary):
         runs.append((G, U, worker.state()["dual"], np.array([worker.objv()])))
     for a, b in zip(*runs):
         assert same(a, b)
+
+
+# ------------------------------------------------------- the seam case --
+def test_seam_case(server):
+    """worker_ref.seam_case's structure with this worker's values (what it
+    reaches: tests/test_worker.py): more long columns than
+    darling_sum_long_kernel has waves, a column at every edge of the short /
+    long split and of a chain_sum2 batch, more than 65,536 rows (three digit
+    passes of the sort by row, objv_kernel's second trip), more than 256
+    tiles in every scan.  Init from weights, gradients over three blocks, one
+    update_dual with update_weights' special values, the objective; twice
+    from one state."""
+    import worker_ref as R
+    from parameter_server_amd.worker import sort_tile
+    offset, index, value, y, dic = D.seam_case(sort_tile())
+    z = D.localized(offset, index, value, dic)
+    nd, rows = dic.size, y.size
+    lens = np.bincount(z[1].astype(np.int64), minlength=nd)
+    assert rows > 65536 and (lens > R.LONG_RUN).sum() > 4 * R.LONG_GRID
+    assert set(R.SEAM_EDGE_RUNS) <= set(lens.tolist())
+    assert {2 * R.CHAIN2 - 1, 2 * R.CHAIN2, 2 * R.CHAIN2 + 1, 4 * R.CHAIN2,
+            4 * R.CHAIN2 + 1} <= set(R.SEAM_EDGE_RUNS)  # whole batches of chain_sum2, and one over
+    rng = np.random.default_rng(71)
+    w = rng.standard_normal(nd) * 0.5
+    third = (nd // 3, 2 * nd // 3)
+    one = int(np.nonzero(lens == 2 * R.CHAIN + 1)[0][0])
+    blocks = ((0, nd), third, (one, one + 1))
+    delta = rng.uniform(0.1, 3.0, nd)
+    active = np.ones(nd, np.uint8)
+    active[rng.choice(nd, size=nd // 50, replace=False)] = 0
+    active[one] = 1
+    big = DarlingWorker(server._h, DELTA_INIT, DELTA_MAX)
+    try:
+        big.load(offset, index, value, y, dic, w=w)
+        st = big.state()
+        # init: Xw is bit for bit the host's, then one exp
+        assert same(st["cur_w"], w) and same(st["delta"], np.full(nd, DELTA_INIT))
+        xw = R.vector_times(z[0], z[1], z[2], w)
+        want_dual = D.vector_init_dual(y, xw)
+        assert np.abs(y * xw).max() > 3 and np.isfinite(want_dual).all() and \
+            want_dual.min() > 1e-300
+        ok, f_init = within(st["dual"], want_dual, D.init_bound(want_dual))
+        assert ok
+        assert same(st["dual"][[0, 7, 8, -1]], np.ones(4))  # the empty rows
+        # from here on both sides start from the device's own dual
+        dual = st["dual"]
+        wantG, wantU = D.vector_gradients(*z, nd, y, dual, delta, active, 0, nd)
+        nw = D.update_weights(rng, w, *third, DELTA_MAX)
+        want = D.vector_update_dual(*z, nd, y, dual, w, delta, active, *third, nw, DELTA_MAX)
+        nfac = want[5]
+        assert (nfac == 0).sum() >= 4 and nfac.max() >= 4
+        assert np.isfinite(want[0]).all() and want[0].min() > 1e-300
+        assert np.isfinite(wantU[active == 1]).all()
+        runs = []
+        for _ in range(2):
+            big.set_state(dual=dual, cur_w=w, delta=delta, active=active)
+            got = [big.gradients(cb, ce) for cb, ce in blocks]
+            big.update_dual(*third, nw)
+            now = big.state()
+            runs.append(got + [now["dual"], np.array([big.objv()])])
+        f_u = 0.0
+        for (cb, ce), (G, U) in zip(blocks, runs[0][:3]):
+            assert G.size == ce - cb and same(G, wantG[cb:ce]), (cb, ce)
+            live = active[cb:ce] == 1
+            assert np.all(D.bits(U)[~live] == ONES) and np.all(D.bits(G)[~live] == ONES)
+            ok, f = within(U[live], wantU[cb:ce][live],
+                           D.u_bound(wantU[cb:ce], lens[cb:ce], False)[live])
+            assert ok, (cb, ce)
+            f_u = max(f_u, f)
+        assert same(now["cur_w"], want[1]) and same(now["delta"], want[2])
+        assert same(now["active"], want[3]) and same(now["delta_w"], want[4])
+        assert same(now["dual"][nfac == 0], dual[nfac == 0])
+        ok, f_dual = within(now["dual"], want[0], D.dual_bound(want[0], nfac))
+        assert ok
+        terms = D.scalar_objv_terms(now["dual"])
+        ok, f_objv = within(runs[0][4][0], math.fsum(terms), D.objv_bound(terms))
+        assert ok
+        print("seam case: init %.3f, U %.3f, dual %.3f (up to %d factors), objv %.3g of their "
+              "bounds" % (f_init, f_u, f_dual, nfac.max(), f_objv))
+        for a, b in zip(runs[0][:3], runs[1][:3]):
+            assert same(a[0], b[0]) and same(a[1], b[1])
+        assert same(runs[0][3], runs[1][3]) and same(runs[0][4], runs[1][4])
+    finally:
+        big.close()
+
+
+# ------------------------------------------ the sort by row's pass count --
+@pytest.mark.parametrize("rows", D.ROW_COUNTS)
+def test_row_sort_pass_counts(worker, rows):
+    """255, 256, 65,535 and 65,536 rows: 1, 2, 2 and 3 digit passes, so the
+    rows' lists end on either side of the sort's two buffers.  The cases tell
+    a wrong order of a row's factors (tests/test_darling_worker.py)."""
+    offset, index, value, y, dic = D.row_case(rows)
+    z = D.localized(offset, index, value, dic)
+    dual, cur_w, delta, active, nw = D.row_case_update(rows)
+    want = D.vector_update_dual(*z, dic.size, y, dual, cur_w, delta, active, 0, dic.size, nw,
+                                DELTA_MAX)
+    worker.load(offset, index, value, y, dic)
+    worker.set_state(dual=dual, cur_w=cur_w, delta=delta, active=active)
+    worker.update_dual(0, dic.size, nw)
+    st = worker.state()
+    nfac = want[5]
+    assert nfac[0] == nfac[rows // 2] == nfac[-1] == 12
+    assert same(st["dual"][nfac == 0], dual[nfac == 0])
+    ok, frac = within(st["dual"], want[0], D.dual_bound(want[0], nfac))
+    print("rows %d: dual %.3f of its bound" % (rows, frac))
+    assert ok
+    assert same(st["cur_w"], want[1]) and same(st["delta_w"], want[4])
 
 
 # ------------------------------------------------------------ lockstep --

@@ -83,6 +83,124 @@ def test_sort_cases_make_every_pass_matter():
     sizes = {v.size for v in c.values()}
     assert {1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 3 * TILE + 7} <= sizes
     assert c["one_key"].size > 2 * TILE  # one run over several workgroups
+    digits = lambda k: {d for d in range(8) if (differ[k] >> (8 * d)) & 0xFF}  # noqa: E731
+    assert digits("digits_0_3_7") == {0, 3, 7}  # passes on digits that are not neighbours
+    assert digits("digits_1_2_4_5_6") == {1, 2, 4, 5, 6}
+    for k in ("nine_tiles_plus_5", "seventeen_tiles_plus_3"):
+        tiles = -(-c[k].size // TILE)
+        assert tiles >= 9 and tiles % 8 and len(digits(k)) == 8  # the tile order is permuted
+    assert {9 * TILE + 5, 17 * TILE + 3} <= sizes
+
+
+def test_constants_mirror_the_kernel_source():
+    """worker_ref.py sizes the seam case by copies of psg_worker.hip's
+    constants; a change there must change them here."""
+    src = open(os.path.join(ROOT, "parameter_server_amd", "csrc", "psg_worker.hip")).read()
+
+    def number(pattern):
+        found = re.findall(pattern, src, flags=re.M)
+        assert len(found) == 1, (pattern, found)
+        return int(found[0])
+
+    assert number(r"^#define PSG_SORT_KPT (\d+)\b") == R.SORT_KPT
+    assert number(r"^#define PSG_LONG_RUN (\d+)\b") == R.LONG_RUN
+    assert number(r"^#define PSG_CHAIN_AHEAD (\d+)\b") * 64 == R.CHAIN
+    assert number(r"^#define PSG_CHAIN_AHEAD2 (\d+)\b") * 64 == R.CHAIN2
+    assert number(r"^constexpr uint32_t kFlagTile = (\d+);") == R.FLAG_TILE
+    assert number(r"^constexpr uint32_t kLongGrid = (\d+);") == R.LONG_GRID
+    # what the mirrors stand for in the source
+    assert re.search(r"^constexpr uint32_t kSortTile = 256 \* kSortKPT;", src, flags=re.M)
+    assert re.search(r"^constexpr uint32_t kLongRun = PSG_LONG_RUN;", src, flags=re.M)
+    assert re.search(r"^constexpr int kChainAhead = PSG_CHAIN_AHEAD;", src, flags=re.M)
+    assert re.search(r"^constexpr int kChainAhead2 = PSG_CHAIN_AHEAD2;", src, flags=re.M)
+    assert "for (uint32_t b = 0; b < n; b += %d)" % R.SCAN in src      # row_scan_kernel
+    assert "for (uint32_t p = threadIdx.x; p < nparts; p += %d)" % R.SCAN in src  # objv_kernel
+    assert _lib.lib().psg_mb_sort_tile() == 256 * R.SORT_KPT
+
+
+SEAM_SEED = 29
+
+
+def seam_tile():
+    return int(_lib.lib().psg_mb_sort_tile())
+
+
+def test_seam_case_reaches_every_second_level_path():
+    """The table of what no small case reaches, as assertions: a change to a
+    constant or to the generator cannot quietly empty the seam case."""
+    tile = seam_tile()
+    offset, index, value, y = R.seam_case(tile, SEAM_SEED)
+    dic = R.seam_dict(index)
+    rep = R.seam_report(offset, index, dic, tile)
+    print({k: v for k, v in rep.items() if k != "dict_run_lengths"})
+    assert rep["pairs"] == (R.SCAN + 1) * max(tile, R.FLAG_TILE) + 1 < 1 << 20
+    assert rep["rows"] == 256 * 256 + 301 and rep["empty_rows"] == [0, 7, 8, 1]
+    # row_scan_kernel goes round again, with a carry; xcd_index permutes
+    assert rep["sort_tiles"] > R.SCAN and rep["sort_tiles"] % 8
+    assert rep["flag_tiles"] > R.SCAN and rep["flag_tiles"] % 8
+    assert rep["differing_digits"] == 8 and rep["carry_passes"]
+    assert rep["heads_before"] and rep["heads_after"]
+    assert rep["kept_before"] and rep["kept_after"]
+    assert rep["dropped_before"] and rep["dropped_after"]
+    # the long-run kernels' waves go round again; a long run is dropped, too
+    assert rep["long_dict_keys"] > 4 * R.LONG_GRID and rep["long_dropped"]
+    # objv_kernel goes round again
+    assert rep["loss_partials"] > R.SCAN
+    # the short / long split and chain_sum's batches at their edges
+    assert set(R.SEAM_EDGE_RUNS) <= rep["dict_run_lengths"]
+    assert {R.LONG_RUN, R.LONG_RUN + 1, R.CHAIN - 1, R.CHAIN, R.CHAIN + 1, 2 * R.CHAIN,
+            2 * R.CHAIN + 1} <= set(R.SEAM_EDGE_RUNS)
+    assert set(range(1, 9)) <= rep["dict_run_lengths"] and rep["dict_absent"] >= 50
+    assert dic[0] < index.min() and dic[-1] > index.max()
+    assert np.all(dic[1:] > dic[:-1])
+    # the binary case is the same structure without values
+    ob, ib, vb, yb = R.seam_case(tile, SEAM_SEED, binary=True)
+    assert vb is None and np.array_equal(ib, index) and np.array_equal(ob, offset)
+    # the small case of the run edges
+    o, i, v, yy, d = R.run_edge_case()
+    st = R.Step("vector", o, i, v, yy, d)
+    assert sorted(st.cnt.tolist()) == sorted(R.RUN_EDGES) and 4000 < i.size < 6000
+    assert not np.array_equal(st.cnt, np.sort(st.cnt))  # key order is not length order
+    assert int(np.sum(st.pos + st.neg == 0)) == 2 == d.size - st.uniq.size
+
+
+def test_seam_case_sums_are_order_sensitive():
+    """test_order_sensitivity_guard's bar on the seam case: reversing a run of
+    8 or more (a row of 8 or more) changes at least 30 % of the outputs."""
+    offset, index, value, y = R.seam_case(seam_tile(), SEAM_SEED)
+    dic = R.seam_dict(index)
+    st = R.Step("vector", offset, index, value, y, dic)
+    rng = np.random.default_rng(2)
+    x, c = R.special_vector(rng, dic.size), R.special_vector(rng, y.size)
+    fwd = R.scalar_times(st.new_offset, st.new_index, st.new_value, x)
+    bwd = R.scalar_times(st.new_offset, st.new_index, st.new_value, x, reverse=True)
+    long_rows = np.diff(st.new_offset.astype(np.int64)) >= 8
+    frac = np.mean(R.bits(fwd)[long_rows] != R.bits(bwd)[long_rows])
+    print("times: %d rows of 8 or more, %.0f %% change" % (long_rows.sum(), 100 * frac))
+    assert long_rows.sum() >= 1000 and frac >= 0.30
+    gf = R.scalar_trans_times(st.new_offset, st.new_index, st.new_value, c, dic.size)
+    gb = R.scalar_trans_times(st.new_offset, st.new_index, st.new_value, c, dic.size,
+                              reverse=True)
+    long_runs = (st.pos + st.neg) >= 8
+    frac = np.mean(R.bits(gf)[long_runs] != R.bits(gb)[long_runs])
+    print("trans_times: %d runs of 8 or more, %.0f %% change" % (long_runs.sum(), 100 * frac))
+    assert long_runs.sum() > 4 * R.LONG_GRID and frac >= 0.30
+    edge = np.isin(st.pos + st.neg, R.SEAM_EDGE_RUNS[2:])  # 64 and up: one key each
+    assert edge.sum() == len(R.SEAM_EDGE_RUNS) - 2
+    assert np.mean(R.bits(gf)[edge] != R.bits(gb)[edge]) >= 0.30
+
+
+@pytest.mark.parametrize("binary", (False, True))
+def test_forms_agree_on_a_cut_down_seam_case(binary):
+    """The same generator with fewer pairs, so that the scalar form finishes
+    in seconds; every kind of run is still there."""
+    offset, index, value, y = R.seam_case(seam_tile(), SEAM_SEED, binary=binary, n=120000,
+                                          rows=16000, long_keys=800)
+    dic = R.seam_dict(index)
+    w = np.random.default_rng(5).standard_normal(dic.size) * 2.0 ** -19
+    st = both(offset, index, value, y, dic, w)
+    assert set(R.SEAM_EDGE_RUNS) <= set((st.pos + st.neg).tolist())
+    assert np.isfinite(st.loss).all() and np.any(st.remapped == 0)
 
 
 def test_cases_take_every_branch():

@@ -151,12 +151,16 @@ def test_localize_and_count_keys(mb, dname, binary):
 
 
 # ---------------------------------------------------- ordered products --
-def products(mb, case, dic, seed):
+def products(mb, case, dic, seed, want=None):
+    """want: the case's Step against dic where it is there already (Z does
+    not depend on the values, so the valued case's serves the binary one)."""
     import torch
     offset, index, value, y = case
     rng = np.random.default_rng(seed)
     x, c = R.special_vector(rng, dic.size), R.special_vector(rng, y.size)
-    want = R.Step("vector", offset, index, value, y, dic)
+    if want is None:
+        want = R.Step("vector", offset, index, value, y, dic)
+    nv = None if value is None else want.new_value
     mb.load(offset, index, value, y)
     mb.uniq()
     d = localize(mb, dic)
@@ -167,8 +171,8 @@ def products(mb, case, dic, seed):
     mb.times(tx.data_ptr(), txw.data_ptr())
     mb.trans_times(tc.data_ptr(), tg.data_ptr())
     mb.read("pos")  # waits
-    xw = R.vector_times(want.new_offset, want.new_index, want.nv, x)
-    g = R.vector_trans_times(want.new_offset, want.new_index, want.nv, c, dic.size)
+    xw = R.vector_times(want.new_offset, want.new_index, nv, x)
+    g = R.vector_trans_times(want.new_offset, want.new_index, nv, c, dic.size)
     del d
     return host(txw, np.float64, y.size), xw, host(tg, np.float64, dic.size), g
 
@@ -198,6 +202,12 @@ def test_logit_gradient_and_objv(mb):
     rng = np.random.default_rng(47)
     w = rng.standard_normal(dic.size) * 2.0 ** -17
     want = R.Step("vector", offset, index, value, y, dic, w)
+    logit_checks(mb, (offset, index, value, y), dic, w, want)
+
+
+def logit_checks(mb, case, dic, w, want):
+    """psg_mb_gradient of `case` against `want`, its Step with weights w."""
+    offset, index, value, y = case
     assert np.abs(want.xw).max() < 30 and np.abs(want.xw).max() > 1
     mb.load(offset, index, value, y)
     mb.uniq()
@@ -309,19 +319,133 @@ def test_large_small_large_on_one_handle(ctx):
         dic = np.unique(index)[::2]
         rng = np.random.default_rng(3)
         w = rng.standard_normal(dic.size) * 2.0 ** -22
-        want = R.Step("vector", offset, index, value, y, dic, w)
-        m.load(offset, index, value, y)
-        assert m.uniq() == want.uniq.size
-        localize(m, dic)
-        gradient(m, w)
-        for name, ref in (("sorted_key", want.skey), ("sorted_pos", want.spos),
-                          ("uniq_key", want.uniq), ("key_cnt", want.cnt),
-                          ("new_offset", want.new_offset), ("new_index", want.new_index),
-                          ("new_value", want.new_value), ("pos", want.pos), ("neg", want.neg),
-                          ("xw", want.xw)):
-            assert same(m.read(name), ref), name
-        assert np.all(np.abs(m.read("grad") - want.grad) <= R.grad_bound(want, y))
+        whole_step(m, (offset, index, value, y), dic, w)
     m.close()
+
+
+def whole_step(m, case, dic, w, want=None):
+    """Load to gradient on handle m, every array against the restatement."""
+    offset, index, value, y = case
+    if want is None:
+        want = R.Step("vector", offset, index, value, y, dic, w)
+    m.load(offset, index, value, y)
+    assert m.uniq() == want.uniq.size
+    localize(m, dic)
+    gradient(m, w)
+    for name, ref in (("sorted_key", want.skey), ("sorted_pos", want.spos),
+                      ("uniq_key", want.uniq), ("key_cnt", want.cnt),
+                      ("new_offset", want.new_offset), ("new_index", want.new_index),
+                      ("new_value", want.new_value), ("pos", want.pos), ("neg", want.neg),
+                      ("xw", want.xw)):
+        assert same(m.read(name), ref), name
+    assert np.all(np.abs(m.read("grad") - want.grad) <= R.grad_bound(want, y))
+
+
+# ------------------------------------------------------- the seam case --
+# One minibatch past the first iteration of every second-level structure of
+# the kernels (worker_ref.seam_case; tests/test_worker.py asserts what it
+# reaches).  Its reference step is computed once, and it has a handle of its
+# own, so the shared one keeps the small buffers the other tests grew.
+SEAM_SEED = 29
+
+
+class Seam:
+    def __init__(self, ctx):
+        self.case = R.seam_case(tile(), SEAM_SEED)
+        offset, index, value, y = self.case
+        self.binary_case = (offset, index, None, y)
+        self.dic = R.seam_dict(index)
+        self.w = np.random.default_rng(47).standard_normal(self.dic.size) * 2.0 ** -19
+        self.want = R.Step("vector", offset, index, value, y, self.dic, self.w)
+        self.mb = Minibatch(ctx)
+
+
+@pytest.fixture(scope="module")
+def seam(ctx):
+    s = Seam(ctx)
+    yield s
+    s.mb.close()
+
+
+def test_seam_sort_and_run_lengths(seam):
+    """More than 256 tiles, a tile count that is no multiple of 8, all eight
+    digit passes: row_scan_kernel's second trip and carry in every pass and
+    in the run heads' scan, xcd_index as a permutation."""
+    offset, index, value, y = seam.case
+    want, m = seam.want, seam.mb
+    m.load(offset, index, value, y)
+    assert m.uniq() == want.uniq.size
+    got_key, got_pos = m.read("sorted_key"), m.read("sorted_pos")
+    assert same(got_key, want.skey)
+    assert same(got_pos, want.spos)
+    assert same(m.read("uniq_key"), want.uniq)
+    assert same(m.read("key_cnt"), want.cnt)
+    start = np.concatenate([[0], np.cumsum(want.cnt)]).astype(np.uint32)
+    assert same(m.read("run_start"), start)
+    row_of = np.repeat(np.arange(y.size), np.diff(offset.astype(np.int64))).astype(np.uint32)
+    assert same(m.read("row_of"), row_of)
+
+
+def test_seam_localize_and_count_keys(seam):
+    """Kept and dropped pairs on both sides of flag tile 256: the
+    compaction's scan carries."""
+    offset, index, value, y = seam.case
+    want, m, dic = seam.want, seam.mb, seam.dic
+    m.load(offset, index, value, y)
+    m.uniq()
+    localize(m, dic)
+    assert same(m.read("remapped"), want.remapped)
+    assert same(m.read("new_offset"), want.new_offset)
+    assert same(m.read("new_index"), want.new_index)
+    assert same(m.read("new_value"), want.new_value)
+    assert same(m.read("pos"), want.pos)
+    assert same(m.read("neg"), want.neg)
+    absent = ~np.isin(dic, index)
+    assert absent.sum() >= 50
+    assert not m.read("pos")[absent].any() and not m.read("neg")[absent].any()
+
+
+@pytest.mark.parametrize("binary", (False, True))
+def test_seam_times_and_trans_times_bit_exact(seam, binary):
+    """More long runs than the long-run kernel has waves, and a run at every
+    edge of the short / long split and of a chain_sum batch."""
+    case = seam.binary_case if binary else seam.case
+    xw, xw_ref, g, g_ref = products(seam.mb, case, seam.dic, 59, seam.want)
+    assert same(xw, xw_ref)
+    assert same(g, g_ref)
+    if binary:
+        assert seam.mb.read("new_value").size == 0
+
+
+def test_seam_logit_gradient_and_objv(seam):
+    """More than 256 partial sums of the objective; the bounds' premise
+    n < 2^20 holds (test_worker.py asserts it of the case)."""
+    logit_checks(seam.mb, seam.case, seam.dic, seam.w, seam.want)
+
+
+def test_seam_then_small_on_one_handle(seam):
+    whole_step(seam.mb, seam.case, seam.dic, seam.w, seam.want)
+    offset, index, value, y = R.zipf_case(seed=11, rows=20, mean=3)
+    dic = np.unique(index)[::2]
+    w = np.random.default_rng(3).standard_normal(dic.size) * 2.0 ** -22
+    whole_step(seam.mb, (offset, index, value, y), dic, w)
+
+
+@pytest.mark.parametrize("binary", (False, True))
+def test_run_edges(mb, binary):
+    """A run of exactly each length around kLongRun, a wave, and one and two
+    batches of chain_sum; two dictionary keys with no run (+0.0)."""
+    offset, index, value, y, dic = R.run_edge_case(binary=binary)
+    want = R.Step("vector", offset, index, value, y, dic)
+    assert sorted(want.cnt.tolist()) == sorted(R.RUN_EDGES)
+    xw, xw_ref, g, g_ref = products(mb, (offset, index, value, y), dic, 61, want)
+    assert same(xw, xw_ref)
+    assert same(g, g_ref)
+    absent = ~np.isin(dic, index)
+    assert absent.sum() == 2 and not bits(g)[absent].any()
+    assert same(mb.read("pos") + mb.read("neg"),
+                np.where(absent, 0, np.bincount(np.searchsorted(dic, index),
+                                                minlength=dic.size)).astype(np.uint32))
 
 
 # --------------------------------------------------------- closed loop --

@@ -31,6 +31,17 @@ import numpy as np
 
 U64 = np.uint64
 
+# Mirrors of psg_worker.hip's constants, for the cases that are sized by them
+# (tests/test_worker.py checks each against the line it copies).  The sort
+# tile is read from the library (psg_mb_sort_tile) and passed in.
+SORT_KPT = 8      # PSG_SORT_KPT: the sort tile is 256 * SORT_KPT pairs
+FLAG_TILE = 2048  # kFlagTile: elements per workgroup of the flag scans
+LONG_RUN = 32     # PSG_LONG_RUN: a longer run is summed by a whole wave
+LONG_GRID = 1024  # kLongGrid: workgroups of 4 waves over the long runs
+CHAIN = 512       # 64 * PSG_CHAIN_AHEAD: terms per batch of chain_sum
+CHAIN2 = 256      # 64 * PSG_CHAIN_AHEAD2: pairs of terms per batch of chain_sum2
+SCAN = 256        # items per trip of row_scan_kernel and objv_kernel (a workgroup)
+
 
 def bits(a):
     return np.ascontiguousarray(a, np.float64).view(np.uint64)
@@ -320,7 +331,20 @@ def sort_cases(tile):
     c["top_byte"] = rng.integers(0, 256, size=tile + 9, dtype=U64) << U64(56) | U64(0x1234567)
     c["bottom_byte"] = rng.integers(0, 256, size=tile + 9, dtype=U64) | U64(0xABCDEF0123456700)
     c["upper_six"] = rng.integers(0, 1 << 16, size=tile + 9, dtype=U64) | U64(0xABCDEF0123450000)
+    # passes on digits that are not neighbours, and tile counts at which the
+    # sort's tile permutation is no identity (9 or more, no multiple of 8)
+    c["digits_0_3_7"] = digits_only(rng, tile + 9, (0, 3, 7))
+    c["digits_1_2_4_5_6"] = digits_only(rng, tile + 9, (1, 2, 4, 5, 6))
+    for name, n in (("nine_tiles_plus_5", 9 * tile + 5), ("seventeen_tiles_plus_3", 17 * tile + 3)):
+        c[name] = rng.integers(0, 50 + n // 3, size=n, dtype=U64) * U64(0x9E3779B97F4A7C15)
     return c
+
+
+def digits_only(rng, n, digits, fixed=0xA5C3E1967B2D4F08):
+    """n keys whose bytes `digits` are random and whose other bytes are `fixed`'s."""
+    mask = sum(0xFF << (8 * d) for d in digits)
+    k = rng.integers(0, 1 << 64, size=n, dtype=U64) & U64(mask)
+    return k | U64(fixed & ~mask & ((1 << 64) - 1))
 
 
 def zipf_ids(rng, n, universe=5000, a=1.1):
@@ -412,6 +436,120 @@ def branch_report(offset, index, value, dic):
         "dict_absent_inside": bool(np.any(~np.isin(dic, uniq))),
         "run_over_wave": bool(uniq.size and np.unique(index, return_counts=True)[1].max() > 64),
     }
+
+
+# ------------------------------------------------------------ the seam case --
+# One minibatch past the first iteration of every second-level structure of
+# psg_worker.hip: more than SCAN tiles in the sort and in both flag scans (so
+# row_scan_kernel carries), tile counts that are no multiple of 8 (xcd_index is
+# a real permutation), more long runs than the 4 * LONG_GRID waves of the
+# long-run kernels, more than SCAN partial sums of the objective, and a run at
+# each edge of the short / long split and of a chain_sum batch.
+SEAM_EDGE_RUNS = (LONG_RUN, LONG_RUN + 1, 64, 65, CHAIN - 1, CHAIN, CHAIN + 1, 2 * CHAIN,
+                  2 * CHAIN + 1)
+
+
+def seam_case(tile, seed, binary=False, n=None, rows=None, long_keys=None, values=None):
+    """(offset, index, value, y).  n pairs (default 257 max(tile, FLAG_TILE) +
+    1) in `rows` rows (default 256 SCAN + 301; rows 0, 7, 8 and the last are
+    empty): one key for each run length of SEAM_EDGE_RUNS, `long_keys` keys
+    (default 4 LONG_GRID + 100) with runs of 33 .. 47, and keys with runs of
+    1 .. 8 for the rest; the keys are spread over all 64 bits and the pairs
+    shuffled.  values(rng, n) gives the values (default sensitive_values).
+    n, rows and long_keys are there for a cut-down case the scalar form can
+    finish; such a case makes no claim about tile counts."""
+    rng = np.random.default_rng(seed)
+    n = (SCAN + 1) * max(tile, FLAG_TILE) + 1 if n is None else n
+    rows = SCAN * 256 + 301 if rows is None else rows
+    long_keys = 4 * LONG_GRID + 100 if long_keys is None else long_keys
+    lens = np.concatenate([np.array(SEAM_EDGE_RUNS, np.int64),
+                           rng.integers(LONG_RUN + 1, LONG_RUN + 16, size=long_keys)])
+    rest = n - int(lens.sum())
+    assert rest > 0, "no room for the short runs"
+    short = rng.integers(1, 9, size=rest)
+    short = short[:int(np.searchsorted(np.cumsum(short), rest)) + 1]
+    short[-1] -= int(short.sum()) - rest
+    lens = rng.permutation(np.concatenate([lens, short[short > 0]]))  # key order is not length order
+    keys = np.unique(rng.integers(1, (1 << 64) - 1, size=lens.size + 64, dtype=U64))
+    assert keys.size >= lens.size
+    keys = rng.permutation(keys)[:lens.size]
+    index = rng.permutation(np.repeat(keys, lens))
+    assert index.size == n
+    offset = csr_of(rng, index, rows, empty=(0, 7, 8, rows - 1))
+    value = None if binary else (sensitive_values if values is None else values)(rng, n)
+    return offset, index, value, labels(rng, rows)
+
+
+def seam_dict(index, seed=17, every=97):
+    """dict_cases' "with_absent" without about every 97th data key (the keys of
+    the edge-length runs stay): pairs are kept and dropped all over the
+    minibatch, and dictionary keys have no run."""
+    uniq, cnt = np.unique(index, return_counts=True)
+    dic = dict_cases(uniq, seed)["with_absent"]
+    gone = np.zeros(uniq.size, bool)
+    gone[::every] = True
+    gone &= ~np.isin(cnt, SEAM_EDGE_RUNS[:1] + SEAM_EDGE_RUNS[2:])  # 33 is a common length
+    first33 = np.nonzero(cnt == SEAM_EDGE_RUNS[1])[0][:1]
+    gone[first33] = False
+    return dic[~np.isin(dic, uniq[gone])]
+
+
+def seam_report(offset, index, dic, tile):
+    """What of the device code's second-level structure a (minibatch,
+    dictionary) pair reaches; tests/test_worker.py asserts on it."""
+    off = np.asarray(offset).astype(np.int64)
+    n, rows = index.size, off.size - 1
+    uniq, cnt = np.unique(index, return_counts=True)
+    dic_cnt = cnt[np.isin(uniq, dic)]
+    differ = int(np.bitwise_or.reduce(index) ^ np.bitwise_and.reduce(index))
+    passes = [d for d in range(8) if (differ >> (8 * d)) & 0xFF]
+    # the order in which pass d reads the pairs: stably sorted on the digits below d
+    carry_passes, edge = [], SCAN * tile
+    for d in passes:
+        order = np.argsort(index & U64((1 << (8 * d)) - 1), kind="stable")
+        digit = ((index[order] >> U64(8 * d)) & U64(0xFF)).astype(np.int64)
+        if np.intersect1d(digit[:edge], digit[edge:]).size:  # the digit's scan adds a carry
+            carry_passes.append(d)
+    skey = np.sort(index)
+    head = np.concatenate([[True], skey[1:] != skey[:-1]])
+    kept = np.isin(index, dic)
+    fedge = SCAN * FLAG_TILE
+    lens = np.diff(off)
+    return {
+        "pairs": n, "rows": rows, "keys": int(uniq.size), "dict": int(dic.size),
+        "sort_tiles": -(-n // tile), "flag_tiles": -(-n // FLAG_TILE),
+        "long_dict_keys": int(np.sum(dic_cnt > LONG_RUN)),
+        "dict_run_lengths": set(dic_cnt.tolist()),
+        "loss_partials": -(-rows // SCAN),
+        "differing_digits": len(passes), "carry_passes": carry_passes,
+        "heads_before": int(head[:fedge].sum()), "heads_after": int(head[fedge:].sum()),
+        "kept_before": int(kept[:fedge].sum()), "kept_after": int(kept[fedge:].sum()),
+        "dropped_before": int((~kept[:fedge]).sum()), "dropped_after": int((~kept[fedge:]).sum()),
+        "dict_absent": int(np.sum(~np.isin(dic, uniq))),
+        "long_dropped": int(np.sum(cnt[~np.isin(uniq, dic)] > LONG_RUN)),
+        "empty_rows": [int(r) for r in np.nonzero(lens == 0)[0][:3]] + [int(lens[-1] == 0)],
+    }
+
+
+RUN_EDGES = (1, LONG_RUN - 1, LONG_RUN, LONG_RUN + 1, 63, 64, 65, CHAIN - 1, CHAIN, CHAIN + 1,
+             2 * CHAIN - 1, 2 * CHAIN, 2 * CHAIN + 1)
+
+
+def run_edge_case(seed=31, rows=600, binary=False):
+    """(offset, index, value, y, dic): one key for each run length of
+    RUN_EDGES, key order not length order, and two dictionary keys (one inside,
+    one above) that the data lacks."""
+    rng = np.random.default_rng(seed)
+    lens = rng.permutation(np.array(RUN_EDGES, np.int64))
+    keys = np.unique(rng.integers(1, (1 << 64) - 1, size=lens.size + 1, dtype=U64))
+    assert keys.size == lens.size + 1
+    inside = keys[lens.size // 2]
+    keys = np.delete(keys, lens.size // 2)
+    index = rng.permutation(np.repeat(keys, lens))
+    offset = csr_of(rng, index, rows, empty=(0, rows - 1))
+    value = None if binary else sensitive_values(rng, index.size)
+    dic = np.unique(np.concatenate([keys, [inside, keys.max() + U64(1)]]).astype(U64))
+    return offset, index, value, labels(rng, rows), dic
 
 
 def closed_loop_batches(seed=23, nbatch=5, rows=200, mean=10, universe=800):
