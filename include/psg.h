@@ -691,6 +691,110 @@ int psg_mb_darling_set_state(psg_minibatch* mb, const double* dual, const double
 #define PSG_MB_DARLING_DELTA_W 36  /* double[ce - cb] of the last psg_mb_darling_update_dual */
 
 /* ------------------------------------------------------------------ */
+/* Model evaluation: the distributed AUC (src/base/auc.h:8-103) and    */
+/* the exact rank AUC (src/base/evaluation.h:17-44)                    */
+/* ------------------------------------------------------------------ */
+/* The label array of the loaded minibatch and its own Xw array, both valid
+ * until the next psg_mb_load (PSG_ERR_ARG before the first).  xw_dev holds
+ * values only after psg_mb_times has been run into it or psg_mb_gradient has
+ * run; once psg_mb_times has run into it, psg_mb_read(PSG_MB_XW) reads it.
+ * Scoring without training (ModelEvaluation::run, model_evaluation.h:48-57)
+ * is load, uniq, psg_ftrl_pull_dev of the unique keys, localize against
+ * them and psg_mb_times into xw_dev.  Defined deviation: a key the model
+ * lacks adds +0.0 * v to its row where the reference skips the entry; the
+ * bits are the same unless v is an infinity or a NaN. */
+int psg_mb_labels(psg_minibatch* mb, const double** y_dev, const double** xw_dev);
+
+/* A psg_auc is the root's two maps (auc.h:101) as one histogram resident in
+ * HBM: the distinct keys in ascending signed order, a uint64 positive and a
+ * uint64 negative count per key.  A handle's calls run in call order whatever
+ * stream they are given; stream == NULL is the context's stream.  The arrays
+ * only grow.  The host keeps an upper bound of the distinct keys (every add
+ * raises it by its item count) and reads the device's true count only when
+ * that bound passes the capacity; while there is room an add allocates
+ * nothing.  Every count is an integer and every device sum an integer sum:
+ * the histogram after any sequence of adds and merges is the one that a
+ * single compute over all the examples gives.  Destroy a handle before its
+ * context.
+ * Defined deviations from the reference:
+ *  - a product predict * goodness that is NaN or of magnitude >= 2^63 has no
+ *    defined conversion in C++; it gets the key INT64_MIN, which is what the
+ *    reference's x86-64 build produces;
+ *  - n == 0 is a legal no-op (the reference CHECKs it, auc.h:71);
+ *    n >= 2^32 - 1 is PSG_ERR_SIZE (positions are uint32);
+ *  - psg_auc_merge drops entries whose count is 0 (the reference's map keeps
+ *    the key with a count of 0, which changes no result);
+ *  - an add reads the batch's smallest and largest key (16 bytes) back before
+ *    it sorts, to choose the radix digits: it waits for its own key kernel,
+ *    as psg_mb_load waits for its OR / AND reduction;
+ *  - evaluate() as written (auc.h:49) advances over the positives while their
+ *    COUNT is at most the negative's count, where it means their KEY: with
+ *    all keys distinct (every count 1) it returns 1.0 whatever the data.
+ *    PSG_AUC_BY_KEY is auc.h:42-59 with that one condition read as
+ *    `tp_it->first <= fp_it.first`; PSG_AUC_AS_WRITTEN is the loop verbatim,
+ *    for comparing numbers with a reference run.  On 2,000 examples: as
+ *    written 0.783, 0.597, 1.0 at goodness 10, 1000, 100000; by key 0.862,
+ *    0.8704, 0.8705; the exact rank AUC 0.8705. */
+typedef struct psg_auc psg_auc;
+#define PSG_AUC_BY_KEY 0
+#define PSG_AUC_AS_WRITTEN 1
+int psg_auc_create(psg_ctx* ctx, int64_t goodness, psg_auc** h);
+void psg_auc_destroy(psg_auc* h);
+/* clear() (auc.h:62): an empty histogram; the arrays are kept.  Enqueues. */
+int psg_auc_clear(psg_auc* h);
+/* setGoodness (auc.h:10); PSG_ERR_ARG unless the histogram is empty (keys of
+ * two goodnesses do not mix). */
+int psg_auc_set_goodness(psg_auc* h, int64_t goodness);
+/* compute (auc.h:69-80) fused with merge (:14-22): example i adds one to key
+ * (int64)(predict[i] * (double)goodness) -- one rounded multiply, truncation
+ * toward zero -- as a positive iff y[i] > 0 (0, -0.0 and NaN are negatives). */
+int psg_auc_add_dev(psg_auc* h, const double* y_dev, const double* predict_dev, size_t n,
+                    void* stream);
+/* The same with host arrays, free on return. */
+int psg_auc_add(psg_auc* h, const double* y, const double* predict, size_t n);
+/* merge (auc.h:14-22) of another worker's AUCData: host arrays, keys in any
+ * order, repeats add up (the map's +=).  Takes add's device path with each
+ * entry's count as its weight. */
+int psg_auc_merge(psg_auc* h, const int64_t* tp_key, const uint64_t* tp_count, size_t ntp,
+                  const int64_t* fp_key, const uint64_t* fp_count, size_t nfp);
+/* The AUCData compute writes (auc.h:85-97): the keys with a positive count
+ * and those counts, then the same for the negatives, each list in ascending
+ * signed key order.  *ntp / *nfp = the lists' lengths; PSG_ERR_SIZE (nothing
+ * copied) if either exceeds its capacity.  Synchronises. */
+int psg_auc_data(psg_auc* h, int64_t* tp_key, uint64_t* tp_count, size_t tp_cap, size_t* ntp,
+                 int64_t* fp_key, uint64_t* fp_count, size_t fp_cap, size_t* nfp);
+/* accuracy (auc.h:26-39) over an AUCData whose lists ascend by key: pure host
+ * code, every double the reference's (x = threshold * goodness, (double)key
+ * >= x, correct and total summed as doubles, positives first).  An empty
+ * AUCData gives 0 / 0 = NaN. */
+int psg_auc_accuracy_data(int64_t goodness, const int64_t* tp_key, const uint64_t* tp_count,
+                          size_t ntp, const int64_t* fp_key, const uint64_t* fp_count, size_t nfp,
+                          double threshold, double* out);
+/* evaluate (auc.h:42-59) over such an AUCData, mode PSG_AUC_BY_KEY or
+ * PSG_AUC_AS_WRITTEN (above); pure host code, serial, in the reference's
+ * order; .5 when either list is empty. */
+int psg_auc_evaluate_data(const int64_t* tp_key, const uint64_t* tp_count, size_t ntp,
+                          const int64_t* fp_key, const uint64_t* fp_count, size_t nfp, int mode,
+                          double* out);
+/* psg_auc_data, then the function above.  Synchronise. */
+int psg_auc_accuracy(psg_auc* h, double threshold, double* v);
+int psg_auc_evaluate(psg_auc* h, int mode, double* v);
+/* Evaluation<double>::auc (evaluation.h:17-44) on device arrays: a stable sort
+ * by prediction, A = the sum over the negatives (y <= 0 or NaN) of the
+ * positives sorted before them, in uint64 (exact), then area = (double)A /
+ * ((double)P * (double)(n - P)) and area < 0.5 ? 1 - area : area.  One class
+ * absent or n == 0 gives 0 / 0: NaN is returned, as the reference would.
+ * Synchronises.  Defined deviations: a NaN prediction is PSG_ERR_ARG (counted
+ * on the device; the reference's comparator is then no strict weak order and
+ * std::sort undefined); equal predictions keep their input order (std::sort
+ * leaves it open); -0.0 and +0.0 are equal, as under the comparator; only
+ * V = double is built (ModelEvaluation's float stops counting at 2^24);
+ * n >= 2^32 - 1 is PSG_ERR_SIZE. */
+int psg_auc_exact_dev(psg_ctx* ctx, const double* y_dev, const double* predict_dev, size_t n,
+                      double* auc, void* stream);
+int psg_auc_exact(psg_ctx* ctx, const double* y, const double* predict, size_t n, double* auc);
+
+/* ------------------------------------------------------------------ */
 /* Wire ingress: key signatures of the key cache                       */
 /* ------------------------------------------------------------------ */
 /* CRC-32C of device-resident byte segments: out[i] = crc32c::Extend(

@@ -66,6 +66,8 @@ PSG_LOSS_LOGIT = 0
 (PSG_MB_SORTED_KEY, PSG_MB_SORTED_POS, PSG_MB_UNIQ_KEY, PSG_MB_KEY_CNT, PSG_MB_NEW_OFFSET,
  PSG_MB_NEW_INDEX, PSG_MB_NEW_VALUE, PSG_MB_POS, PSG_MB_NEG, PSG_MB_XW, PSG_MB_TAU, PSG_MB_LOSS,
  PSG_MB_GRAD, PSG_MB_RUN_START, PSG_MB_REMAPPED, PSG_MB_ROW_OF, PSG_MB_SCRATCH) = range(17)
+# psg_auc_evaluate's modes
+PSG_AUC_BY_KEY, PSG_AUC_AS_WRITTEN = 0, 1
 # ... and the Darling worker's state (psg_mb_darling_*)
 (PSG_MB_DARLING_DUAL, PSG_MB_DARLING_CUR_W, PSG_MB_DARLING_DELTA, PSG_MB_DARLING_ACTIVE,
  PSG_MB_DARLING_DELTA_W) = range(32, 37)
@@ -216,6 +218,23 @@ SIGNATURES = {
     "psg_mb_darling_update_dual": (C.c_int, [_p, _sz, _sz, _p, C.c_double, _p]),
     "psg_mb_darling_objv": (C.c_int, [_p, C.POINTER(C.c_double), _p]),
     "psg_mb_darling_set_state": (C.c_int, [_p, _p, _p, _p, _p]),
+    "psg_mb_labels": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
+    "psg_auc_create": (C.c_int, [_p, C.c_int64, C.POINTER(_p)]),
+    "psg_auc_destroy": (None, [_p]),
+    "psg_auc_clear": (C.c_int, [_p]),
+    "psg_auc_set_goodness": (C.c_int, [_p, C.c_int64]),
+    "psg_auc_add_dev": (C.c_int, [_p, _p, _p, _sz, _p]),
+    "psg_auc_add": (C.c_int, [_p, _p, _p, _sz]),
+    "psg_auc_merge": (C.c_int, [_p, _p, _p, _sz, _p, _p, _sz]),
+    "psg_auc_data": (C.c_int, [_p, _p, _p, _sz, _psz, _p, _p, _sz, _psz]),
+    "psg_auc_accuracy_data": (C.c_int, [C.c_int64, _p, _p, _sz, _p, _p, _sz, C.c_double,
+                                        C.POINTER(C.c_double)]),
+    "psg_auc_evaluate_data": (C.c_int, [_p, _p, _sz, _p, _p, _sz, C.c_int,
+                                        C.POINTER(C.c_double)]),
+    "psg_auc_accuracy": (C.c_int, [_p, C.c_double, C.POINTER(C.c_double)]),
+    "psg_auc_evaluate": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
+    "psg_auc_exact_dev": (C.c_int, [_p, _p, _p, _sz, C.POINTER(C.c_double), _p]),
+    "psg_auc_exact": (C.c_int, [_p, _p, _p, _sz, C.POINTER(C.c_double)]),
 }
 
 _LIB = None

@@ -6,6 +6,9 @@
 // (src/linear_method/loss.h:73-85) and grad = Z' * (-y tau)
 // (base/matrix.h:57-58 over sparse_matrix.h:87-105).  Kernels first, the
 // psg_mb_* entry points of include/psg.h after them.
+// The kernels of (a) and the flag scans of (b), (c) are in psg_sort.h, which
+// psg_auc.hip includes too; their shape constants and row_scan_kernel are
+// stated here.
 //
 // (a) Sort.  countUniqIndex sorts (key, position) pairs by key
 // (parallelSort over pair_).  Here: a stable LSD radix sort of the 64-bit
@@ -74,106 +77,18 @@ namespace {
 #ifndef PSG_SORT_KPT
 #define PSG_SORT_KPT 8  // A/B builds: 4, 16, 32
 #endif
-#ifndef PSG_LONG_RUN
-#define PSG_LONG_RUN 32  // A/B builds: 8, 256
-#endif
 constexpr int kSortKPT = PSG_SORT_KPT;           // pairs per lane per tile
 constexpr uint32_t kSortTile = 256 * kSortKPT;   // pairs per workgroup
 constexpr uint32_t kWaveSpan = 64 * kSortKPT;    // pairs per wave
-constexpr uint32_t kLongGrid = 1024;             // workgroups (of 4 waves) over the long runs
 constexpr uint32_t kFlagTile = 2048;             // elements per workgroup of the flag scans
-constexpr uint32_t kLongRun = PSG_LONG_RUN;      // runs longer than this go to the whole wave
 
-// XCD-contiguous runs of consecutive tiles (as psg_countmin.hip): tiles next
-// to each other write next to each other in every digit's output range, and
-// their partial lines meet in one XCD's L2
-__device__ __forceinline__ uint32_t xcd_index(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
+}  // namespace
+}  // namespace psg
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
-  for (uint32_t s = 1; s < 64; s <<= 1) {
-    const uint32_t u = __shfl_up(v, s, 64);
-    if (lane >= s) v += u;
-  }
-  return v;
-}
+#include "psg_sort.h"  // the sort and flag-scan kernels, of the shape above
 
-// exclusive scan of v over the 256 lanes of the workgroup; ws: 4 LDS words
-__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* ws, uint32_t* total) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  const uint32_t inc = wave_incl_scan(v, lane);
-  __syncthreads();
-  if (lane == 63) ws[w] = inc;
-  __syncthreads();
-  uint32_t b = 0, t = 0;
-  for (uint32_t i = 0; i < 4; ++i) {
-    const uint32_t x = ws[i];
-    if (i < w) b += x;
-    t += x;
-  }
-  *total = t;
-  return b + inc - v;
-}
-
-// the valid lanes of the wave whose digit equals this lane's
-__device__ __forceinline__ uint64_t match_digit(uint32_t d, bool valid) {
-  uint64_t m = __ballot(valid);
-#pragma unroll
-  for (int b = 0; b < 8; ++b) {
-    const bool bit = (d >> b) & 1u;
-    const uint64_t bal = __ballot(bit);
-    m &= bit ? bal : ~bal;
-  }
-  return m;
-}
-
-// ---- (a) ------------------------------------------------------------------
-// orand[0] |= every key, orand[1] &= every key
-__global__ __launch_bounds__(256) void key_bits_kernel(const uint64_t* __restrict__ keys,
-                                                       uint32_t n,
-                                                       unsigned long long* __restrict__ orand) {
-  uint64_t o = 0, a = ~0ull;
-  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n;
-       i += (uint64_t)gridDim.x * 256u) {
-    const uint64_t k = keys[i];
-    o |= k;
-    a &= k;
-  }
-  for (int s = 32; s >= 1; s >>= 1) {
-    o |= __shfl_xor(o, s, 64);
-    a &= __shfl_xor(a, s, 64);
-  }
-  if ((threadIdx.x & 63u) == 0) {
-    atomicOr(orand, (unsigned long long)o);
-    atomicAnd(orand + 1, (unsigned long long)a);
-  }
-}
-
-// counts[d * ntiles + t] = pairs of tile t whose digit is d
-__global__ __launch_bounds__(256) void sort_count_kernel(const uint64_t* __restrict__ keys,
-                                                         uint32_t n, int shift,
-                                                         uint32_t* __restrict__ counts,
-                                                         uint32_t ntiles) {
-  __shared__ uint32_t h[256];
-  const uint32_t t = xcd_index(blockIdx.x, gridDim.x);
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)t * kSortTile + (uint64_t)w * kWaveSpan + lane;
-#pragma unroll 4
-  for (int j = 0; j < kSortKPT; ++j) {
-    const uint64_t i = base + (uint64_t)j * 64u;
-    const bool valid = i < n;
-    const uint32_t d = valid ? (uint32_t)(keys[i] >> shift) & 255u : 0u;
-    const uint64_t m = match_digit(d, valid);
-    if (valid && (m & ((1ull << lane) - 1)) == 0)  // first lane of its group
-      atomicAdd(&h[d], (uint32_t)__popcll(m));
-  }
-  __syncthreads();
-  counts[(size_t)threadIdx.x * ntiles + t] = h[threadIdx.x];
-}
+namespace psg {
+namespace {
 
 // workgroup r: c[r * n .. + n) becomes its exclusive scan, total[r] its sum
 __global__ __launch_bounds__(256) void row_scan_kernel(uint32_t* __restrict__ c, uint32_t n,
@@ -192,121 +107,26 @@ __global__ __launch_bounds__(256) void row_scan_kernel(uint32_t* __restrict__ c,
   if (threadIdx.x == 0) total[blockIdx.x] = carry;
 }
 
-// pin null: the positions are 0 .. n-1 (the first pass)
-__global__ __launch_bounds__(256) void sort_scatter_kernel(
-    const uint64_t* __restrict__ kin, const uint32_t* __restrict__ pin, uint64_t* __restrict__ kout,
-    uint32_t* __restrict__ pout, uint32_t n, int shift, const uint32_t* __restrict__ counts,
-    const uint32_t* __restrict__ dtotal, uint32_t ntiles) {
-  __shared__ uint32_t cnt[4][256];
-  __shared__ uint32_t dbase[256];
-  __shared__ uint32_t ws[4];
-  const uint32_t t = xcd_index(blockIdx.x, gridDim.x);
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
-  for (int i = 0; i < 4; ++i) cnt[i][tid] = 0;
-  {  // first output index of digit `tid` for this tile
-    uint32_t tot;
-    const uint32_t ex = block_exscan(dtotal[tid], ws, &tot);
-    dbase[tid] = ex + counts[(size_t)tid * ntiles + t];
-  }
-  __syncthreads();
-  // The wave's counters are read by every lane and then advanced by one lane
-  // per group.  LDS operations of one wave run in order, so a step reads
-  // what the step before wrote; volatile keeps the compiler from carrying a
-  // counter in a register across steps.
-  volatile uint32_t* mine = cnt[w];
-  const uint64_t base = (uint64_t)t * kSortTile + (uint64_t)w * kWaveSpan + lane;
-  uint64_t key[kSortKPT];
-  uint32_t off[kSortKPT];
-#pragma unroll
-  for (int j = 0; j < kSortKPT; ++j) {
-    const uint64_t i = base + (uint64_t)j * 64u;
-    const bool valid = i < n;
-    key[j] = valid ? kin[i] : 0;
-    const uint32_t d = (uint32_t)(key[j] >> shift) & 255u;
-    const uint64_t m = match_digit(d, valid);
-    const uint32_t before = mine[d];  // the wave's earlier steps
-    const uint32_t below = (uint32_t)__popcll(m & ((1ull << lane) - 1));
-    const uint32_t group = (uint32_t)__popcll(m);
-    __builtin_amdgcn_wave_barrier();
-    if (valid && below + 1 == group) mine[d] = before + group;  // last lane of the group
-    __builtin_amdgcn_wave_barrier();
-    off[j] = before + below;
-  }
-  __syncthreads();
-  {  // the waves' totals of digit `tid` become their exclusive prefix
-    uint32_t run = 0;
-    for (int i = 0; i < 4; ++i) {
-      const uint32_t x = cnt[i][tid];
-      cnt[i][tid] = run;
-      run += x;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kSortKPT; ++j) {
-    const uint64_t i = base + (uint64_t)j * 64u;
-    if (i < n) {
-      const uint32_t d = (uint32_t)(key[j] >> shift) & 255u;
-      const uint32_t dst = dbase[d] + cnt[w][d] + off[j];
-      if (dst < n) {  // always, by the counts; keeps a bad count in bounds
-        kout[dst] = key[j];
-        pout[dst] = pin ? pin[i] : (uint32_t)i;
-      }
-    }
-  }
+}  // namespace
+
+// what psg_sort.h's pass loop, and psg_auc.hip through it, launch the scan by
+void enqueue_row_scan(uint32_t* c, uint32_t n, uint32_t* total, uint32_t rows, hipStream_t s) {
+  hipLaunchKernelGGL(row_scan_kernel, dim3(rows), dim3(256), 0, s, c, n, total);
 }
 
-// no digit differs: the input order is the sorted order
-__global__ __launch_bounds__(256) void sort_identity_kernel(const uint64_t* __restrict__ kin,
-                                                            uint64_t* __restrict__ kout,
-                                                            uint32_t* __restrict__ pout,
-                                                            uint32_t n) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (i < n) {
-    kout[i] = kin[i];
-    pout[i] = (uint32_t)i;
-  }
-}
+namespace {
 
-// ---- flag scans: (b) and the compaction of (c) -----------------------------
-// A lane owns 8 consecutive elements of a 2048-element tile.
-struct HeadFlag {  // element i starts a run of the sorted keys
-  const uint64_t* k;
-  __device__ bool operator()(uint32_t i) const { return i == 0 || k[i] != k[i - 1]; }
-};
+#ifndef PSG_LONG_RUN
+#define PSG_LONG_RUN 32  // A/B builds: 8, 256
+#endif
+constexpr uint32_t kLongGrid = 1024;             // workgroups (of 4 waves) over the long runs
+constexpr uint32_t kLongRun = PSG_LONG_RUN;      // runs longer than this go to the whole wave
+
 struct KeptFlag {  // position i survives the dictionary
   const uint32_t* remapped;
   __device__ bool operator()(uint32_t i) const { return remapped[i] != 0; }
 };
 
-template <class Flag>
-__global__ __launch_bounds__(256) void flag_count_kernel(Flag f, uint32_t n,
-                                                         uint32_t* __restrict__ tile_sum) {
-  __shared__ uint32_t ws[4];
-  const uint64_t i0 = (uint64_t)blockIdx.x * kFlagTile + threadIdx.x * 8u;
-  uint32_t c = 0;
-  for (uint32_t j = 0; j < 8; ++j)
-    if (i0 + j < n) c += f((uint32_t)(i0 + j)) ? 1u : 0u;
-  uint32_t tot;
-  (void)block_exscan(c, ws, &tot);
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = tot;
-}
-
-struct HeadEmit {  // ex: run heads before element i
-  const uint64_t* k;
-  uint64_t* uniq_key;
-  uint32_t* run_start;  // [n_uniq + 1]
-  uint32_t* run_of;     // [n]
-  __device__ void operator()(uint32_t i, uint32_t ex, bool head, uint32_t n) const {
-    if (head) {
-      uniq_key[ex] = k[i];
-      run_start[ex] = i;
-    }
-    const uint32_t after = ex + (head ? 1u : 0u);
-    run_of[i] = after - 1;  // i == 0 is a head: after >= 1
-    if (i == n - 1) run_start[after] = n;
-  }
-};
 struct KeptEmit {  // ex: survivors before position i
   const uint32_t* remapped;
   const double* value;  // null: binary
@@ -322,26 +142,6 @@ struct KeptEmit {  // ex: survivors before position i
     if (i == n - 1) before[n] = ex + (kept ? 1u : 0u);
   }
 };
-
-template <class Flag, class Emit>
-__global__ __launch_bounds__(256) void flag_emit_kernel(Flag f, Emit e, uint32_t n,
-                                                        const uint32_t* __restrict__ tile_base) {
-  __shared__ uint32_t ws[4];
-  const uint64_t i0 = (uint64_t)blockIdx.x * kFlagTile + threadIdx.x * 8u;
-  bool fl[8];
-  uint32_t c = 0;
-  for (uint32_t j = 0; j < 8; ++j) {
-    fl[j] = i0 + j < n && f((uint32_t)(i0 + j));
-    c += fl[j] ? 1u : 0u;
-  }
-  uint32_t tot;
-  uint32_t ex = tile_base[blockIdx.x] + block_exscan(c, ws, &tot);
-  for (uint32_t j = 0; j < 8; ++j)
-    if (i0 + j < n) {
-      e((uint32_t)(i0 + j), ex, fl[j], n);
-      ex += fl[j] ? 1u : 0u;
-    }
-}
 
 __global__ __launch_bounds__(256) void key_cnt_kernel(const uint32_t* __restrict__ run_start,
                                                       uint32_t n_uniq,
@@ -979,8 +779,6 @@ __global__ __launch_bounds__(256) void darling_objv_kernel(const double* __restr
   if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
 }
 
-inline uint32_t blocks_of(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
-
 }  // namespace
 }  // namespace psg
 
@@ -1022,6 +820,7 @@ struct psg_minibatch {
   const uint32_t* spos = nullptr;
   // (g): set by psg_mb_darling_init, cleared by psg_mb_load and psg_mb_localize
   bool darling = false;
+  bool xw_own = false;  // psg_mb_times has run into the minibatch's own Xw (psg_mb_labels)
   const uint32_t* row_pair = nullptr;  // the rows' lists (one side of their ping-pong)
   // host: pair_lo[k] = the first sorted pair of the first of keys k, k + 1, ...
   // that has a run (nnz: none); pair_hi[k] = the end of the last run among
@@ -1086,47 +885,14 @@ namespace {
 
 using namespace psg;
 
-#define LAUNCH(kernel, grid, s, ...) \
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, s, __VA_ARGS__)
-
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(PSG_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
-  return PSG_OK;
-}
-
 // the nnz keys `kin` (which may be the key_b block) stably sorted on the
 // digits that `differ` names, through the blocks key_a / key_b / pos_a / pos_b
 int enqueue_sort_keys(psg_minibatch* mb, const uint64_t* kin, uint64_t differ, int key_a,
                       int key_b, int pos_a, int pos_b, const uint64_t** skey,
                       const uint32_t** spos, hipStream_t s) {
-  const uint32_t n = (uint32_t)mb->nnz, ntiles = blocks_of(n, kSortTile);
-  const uint32_t* pin = nullptr;
-  uint64_t* kout = mb->at<uint64_t>(key_a);
-  uint32_t* pout = mb->at<uint32_t>(pos_a);
-  uint32_t* counts = mb->at<uint32_t>(B_COUNTS);
-  bool any = false;
-  for (int d = 0; d < 8; ++d) {
-    if (((differ >> (8 * d)) & 255u) == 0) continue;  // the same digit in every key
-    LAUNCH(sort_count_kernel, ntiles, s, kin, n, 8 * d, counts, ntiles);
-    LAUNCH(row_scan_kernel, 256, s, counts, ntiles, mb->d_dtotal());
-    LAUNCH(sort_scatter_kernel, ntiles, s, kin, pin, kout, pout, n, 8 * d, counts,
-           mb->d_dtotal(), ntiles);
-    kin = kout;
-    pin = pout;
-    const bool to_b = kout == mb->at<uint64_t>(key_a);
-    kout = mb->at<uint64_t>(to_b ? key_b : key_a);
-    pout = mb->at<uint32_t>(to_b ? pos_b : pos_a);
-    any = true;
-  }
-  if (!any) {
-    LAUNCH(sort_identity_kernel, blocks_of(n, 256), s, kin, kout, pout, n);
-    pin = pout;
-    kin = kout;
-  }
-  *skey = kin;
-  *spos = pin;
-  return launched("sort");
+  const SortBuffers b{mb->at<uint64_t>(key_a), mb->at<uint64_t>(key_b), mb->at<uint32_t>(pos_a),
+                      mb->at<uint32_t>(pos_b), mb->at<uint32_t>(B_COUNTS), mb->d_dtotal()};
+  return enqueue_radix_sort(kin, (uint32_t)mb->nnz, differ, b, skey, spos, s);
 }
 
 // (a): the sorted pairs end in mb->skey / mb->spos
@@ -1214,6 +980,7 @@ int psg_mb_load(psg_minibatch* mb, const uint64_t* offset, size_t rows, const ui
   if (int rc = mb->settle()) return rc;  // the previous minibatch's work
   mb->state = S_NEW;
   mb->darling = false;
+  mb->xw_own = false;
   const size_t n = (size_t)nnz, ntiles = blocks_of(n, kSortTile);
   struct {
     int id;
@@ -1317,6 +1084,7 @@ int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
   if (int rc = mb->order(s)) return rc;
   mb->state = S_UNIQ;
   mb->darling = false;
+  mb->xw_own = false;
   const uint32_t n = (uint32_t)mb->nnz, nu = (uint32_t)mb->n_uniq, nd = (uint32_t)ndict;
   const uint32_t rows = (uint32_t)mb->rows;
   uint32_t* before = mb->at<uint32_t>(B_BEFORE);
@@ -1414,7 +1182,16 @@ int psg_mb_times(psg_minibatch* mb, const double* x_dev, double* xw_dev, void* s
   hipStream_t s = mb->pick(stream);
   if (int rc = mb->order(s)) return rc;
   if (int rc = enqueue_times(mb, x_dev, xw_dev, s)) return rc;
+  if (xw_dev == mb->at<double>(B_XW)) mb->xw_own = true;
   return mb->mark(s);
+}
+
+int psg_mb_labels(psg_minibatch* mb, const double** y_dev, const double** xw_dev) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_LOADED) return fail(PSG_ERR_ARG, "psg_mb_labels before psg_mb_load");
+  if (y_dev) *y_dev = mb->at<double>(B_Y);
+  if (xw_dev) *xw_dev = mb->at<double>(B_XW);
+  return PSG_OK;
 }
 
 int psg_mb_trans_times(psg_minibatch* mb, const double* c_dev, double* g_dev, void* stream) {
@@ -1521,7 +1298,7 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
     case PSG_MB_NEW_VALUE: need_state = S_LOCAL; id = B_NEW_VALUE; n = kept_unknown; break;
     case PSG_MB_POS: need_state = S_LOCAL; id = B_CNT_POS; n = mb->ndict; break;
     case PSG_MB_NEG: need_state = S_LOCAL; id = B_CNT_NEG; n = mb->ndict; break;
-    case PSG_MB_XW: need_state = S_GRAD; id = B_XW; n = mb->rows; break;
+    case PSG_MB_XW: need_state = mb->xw_own ? S_LOCAL : S_GRAD; id = B_XW; n = mb->rows; break;
     case PSG_MB_TAU: need_state = S_GRAD; id = B_TAU; n = mb->rows; break;
     case PSG_MB_LOSS: need_state = S_GRAD; id = B_LOSS; n = mb->rows; break;
     case PSG_MB_GRAD: need_state = S_GRAD; id = B_GRAD; n = mb->ndict; break;

@@ -113,6 +113,12 @@ class Minibatch:
     def times(self, x_dev, xw_dev, stream=None) -> None:
         _lib.check(self._L.psg_mb_times(self._h, x_dev, xw_dev, stream))
 
+    def labels(self) -> Tuple[int, int]:
+        """psg_mb_labels: the device pointers of y and of the minibatch's Xw."""
+        y, xw = C.c_void_p(), C.c_void_p()
+        _lib.check(self._L.psg_mb_labels(self._h, C.byref(y), C.byref(xw)))
+        return y.value, xw.value
+
     def trans_times(self, c_dev, g_dev, stream=None) -> None:
         _lib.check(self._L.psg_mb_trans_times(self._h, c_dev, g_dev, stream))
 
@@ -189,8 +195,29 @@ class FTRLWorker:
     def close(self):
         self.mb.close()
 
-    def step(self, offset, index, value, y) -> Tuple[float, int]:
-        """One minibatch: (its objv, its number of examples)."""
+    def predict(self, offset, index, value, y) -> int:
+        """Score one minibatch against the model without training on it
+        (ModelEvaluation::run, model_evaluation.h:48-57): the device pointer
+        of Xw[rows], also ``mb.read("xw")``.  No filter insert and no push,
+        and a pull does not insert: the model is left as it was."""
+        L, mb = self._L, self.mb
+        st = mb.stream
+        mb.load(offset, index, value, y)
+        n = mb.uniq()
+        keys = mb.uniq_key_dev
+        w = mb.scratch(self._W, 8 * n)
+        _lib.check(L.psg_ftrl_pull_dev(self._ctx, keys, n, w, st))
+        mb.localize(keys, n)
+        xw = mb.labels()[1]
+        mb.times(w, xw)
+        self.dict_dev, self.w_dev, self.ndict = keys, w, n
+        return xw
+
+    def step(self, offset, index, value, y, auc=None) -> Tuple[float, int]:
+        """One minibatch: (its objv, its number of examples).  ``auc``: an
+        ``AUC`` of this context that takes (y, Xw) of the minibatch before
+        the push: Xw comes from weights that have not seen the minibatch, so
+        the histogram is a progressive-validation AUC."""
         L, mb = self._L, self.mb
         st = mb.stream  # every enqueue of the step, in order
         mb.load(offset, index, value, y)
@@ -210,6 +237,9 @@ class FTRLWorker:
         _lib.check(L.psg_ftrl_pull_dev(self._ctx, keys, ndict, w, st))   # :108-111
         mb.localize(keys, ndict)                                           # :113-119
         objv = mb.gradient(w)                                              # :128-138
+        if auc is not None:
+            y_dev, xw_dev = mb.labels()
+            auc.add_dev(y_dev, xw_dev, mb.rows, st)
         _lib.check(L.psg_ftrl_push_dev(self._ctx, keys, ndict, mb.pos_dev, mb.neg_dev,
                                        mb.grad_dev, st))                 # :141-148
         self.dict_dev, self.w_dev, self.ndict = keys, w, ndict
