@@ -23,7 +23,10 @@
 //     new table has exactly one writer.  The table ping-pongs between two sets
 //     of arrays.
 // A merge of host AUCData takes the same path with each entry's count as its
-// weight.  No float is summed anywhere on the device.
+// weight.  No float is summed anywhere on the device.  The radix passes and
+// their shape, the count / scan / emit, the binary search and the ballot fold
+// are psg_sort.h's, which psg_worker.hip includes too; the handle's blocks
+// are psg_blocks.h's.
 //
 // The exact AUC: an order-preserving key of the prediction's bits (-0.0 and
 // +0.0 share one), the same sort, an exclusive scan of the "positive" flag in
@@ -38,21 +41,8 @@
 #include <vector>
 
 #include "../../include/psg.h"
+#include "psg_blocks.h"
 #include "psg_host.h"
-
-namespace psg {
-namespace {
-
-// the sort's shape, as psg_worker.hip states it: the tests size their cases
-// by psg_mb_sort_tile()
-constexpr int kSortKPT = 8;                      // pairs per lane per tile
-constexpr uint32_t kSortTile = 256 * kSortKPT;   // pairs per workgroup
-constexpr uint32_t kWaveSpan = 64 * kSortKPT;    // pairs per wave
-constexpr uint32_t kFlagTile = 2048;             // elements per workgroup of the flag scans
-
-}  // namespace
-}  // namespace psg
-
 #include "psg_sort.h"
 
 namespace psg {
@@ -129,36 +119,14 @@ __global__ __launch_bounds__(256) void auc_run_counts_kernel(
     return;
   }
   const bool positive = valid && y[at] > 0;
-  const uint32_t rprev = __shfl_up(r, 1, 64);
-  const bool head = valid && (lane == 0 || r != rprev);
-  const uint64_t heads = __ballot(head), posb = __ballot(positive), val = __ballot(valid);
-  if (head) {
-    const uint64_t above = heads & ~((2ull << lane) - 1);  // the groups after this one
-    const int end = above ? __ffsll((unsigned long long)above) - 1 : 64;
-    const uint64_t upto = end == 64 ? ~0ull : (1ull << end) - 1;
-    const uint64_t seg = upto & ~((1ull << lane) - 1) & val;
-    const uint32_t cp = (uint32_t)__popcll(seg & posb), cn = (uint32_t)__popcll(seg) - cp;
+  uint32_t cp, cn;
+  if (run_label_counts(r, valid, positive, lane, &cp, &cn)) {
     if (cp) atomicAdd(&cnt[r], (unsigned long long)cp);
     if (cn) atomicAdd(&cnt[(size_t)n + r], (unsigned long long)cn);
   }
 }
 
 // ---- (d) ------------------------------------------------------------------
-// first index of k[0 .. n) that holds `key` or more
-__device__ __forceinline__ uint32_t lower_bound(const uint64_t* __restrict__ k, uint32_t n,
-                                                uint64_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (k[mid] < key) {
-      lo = mid + 1;
-    } else {
-      hi = mid;
-    }
-  }
-  return lo;
-}
-
 // words[0] = runs of the batch, words[1] = new keys among them (both uint32);
 // m[0] the resident count read, m[1] the count written
 // run r: its key (the batch's smallest added back), its place among the
@@ -309,57 +277,17 @@ constexpr size_t kAucSmallBytes = 5 * 8 + 256 * 4;
 
 }  // namespace
 
-struct psg_auc {
-  psg_ctx* ctx = nullptr;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev = nullptr;
-  hipStream_t last_s = nullptr;
+struct psg_auc : psg::DeviceBlocks<A_COUNT> {
   int64_t goodness = 0;
   // the table: two sets of key / pos / neg arrays of `cap` entries each
   uint64_t* tab[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
   size_t cap = 0;
   int cur = 0;       // the set that holds the table
   size_t bound = 0;  // the resident count is at most this
-  struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-  } b[A_COUNT];
-  unsigned long long* d_small = nullptr;
-  unsigned long long* h_small = nullptr;  // pinned, 8 words
 
-  template <class T>
-  T* at(int id) const {
-    return (T*)b[id].p;
-  }
   unsigned long long* d_m(int side) const { return d_small + 2 + side; }
   uint32_t* d_words() const { return (uint32_t*)(d_small + 4); }
   uint32_t* d_dtotal() const { return (uint32_t*)(d_small + 5); }
-  int need(int id, size_t bytes) {  // as psg_minibatch::need
-    if (bytes <= b[id].cap) return PSG_OK;
-    if (b[id].p) HIP_TRY(hipFree(b[id].p));
-    b[id].p = nullptr;
-    b[id].cap = 0;
-    const size_t c = (bytes + 4095) / 4096 * 4096;
-    HIP_TRY(hipMalloc(&b[id].p, c));
-    b[id].cap = c;
-    return PSG_OK;
-  }
-  int order(hipStream_t s) {
-    if (last_s && last_s != s) HIP_TRY(hipStreamWaitEvent(s, ev, 0));
-    return PSG_OK;
-  }
-  int mark(hipStream_t s) {
-    HIP_TRY(hipEventRecord(ev, s));
-    last_s = s;
-    return PSG_OK;
-  }
-  int settle() {
-    if (last_s && last_s != stream) HIP_TRY(hipStreamSynchronize(last_s));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PSG_OK;
-  }
-  hipStream_t pick(void* s) const { return s ? (hipStream_t)s : stream; }
 };
 
 namespace {
@@ -419,16 +347,12 @@ int add_items(psg_auc* h, size_t n_z, const double* y, const double* predict,
   if (n_z == 0) return PSG_OK;
   if (int rc = make_room(h, n_z)) return rc;
   const uint32_t n = (uint32_t)n_z, ntiles = blocks_of(n, kSortTile), nt = blocks_of(n, kFlagTile);
-  struct {
-    int id;
-    size_t bytes;
-  } const want[] = {
+  if (int rc = h->need_all({
       {A_BKEY, 8 * n_z}, {A_KEY_A, 8 * n_z}, {A_KEY_B, 8 * n_z}, {A_POS_A, 4 * n_z},
       {A_POS_B, 4 * n_z}, {A_COUNTS, 4 * 256 * (size_t)ntiles}, {A_TILE_SUM, 4 * (size_t)nt + 4},
       {A_UNIQ, 8 * n_z}, {A_RUN_START, 4 * (n_z + 1)}, {A_RUN_OF, 4 * n_z}, {A_CNT, 16 * n_z},
-      {A_RUNKEY, 8 * n_z}, {A_LO, 4 * n_z}, {A_ISNEW, n_z}, {A_BEFORE, 4 * (n_z + 1)}};
-  for (const auto& w : want)
-    if (int rc = h->need(w.id, w.bytes)) return rc;
+      {A_RUNKEY, 8 * n_z}, {A_LO, 4 * n_z}, {A_ISNEW, n_z}, {A_BEFORE, 4 * (n_z + 1)}}))
+    return rc;
   if (int rc = h->order(s)) return rc;
   // (a)
   h->h_small[0] = ~0ull;
@@ -462,9 +386,7 @@ int add_items(psg_auc* h, size_t n_z, const double* y, const double* predict,
   const HeadFlag hf{skey};
   const HeadEmit he{skey, h->at<uint64_t>(A_UNIQ), h->at<uint32_t>(A_RUN_START),
                     h->at<uint32_t>(A_RUN_OF)};
-  LAUNCH(flag_count_kernel<HeadFlag>, nt, s, hf, n, ts);
-  enqueue_row_scan(ts, nt, h->d_words(), 1, s);
-  LAUNCH((flag_emit_kernel<HeadFlag, HeadEmit>), nt, s, hf, he, n, ts);
+  enqueue_flag_scan(hf, he, n, ts, h->d_words(), s);
   HIP_TRY(hipMemsetAsync(cnt, 0, 16 * n_z, s));
   LAUNCH(auc_run_counts_kernel, blocks_of(n, 256), s, spos, h->at<uint32_t>(A_RUN_OF), y, weight,
          side, n, cnt);
@@ -479,9 +401,7 @@ int add_items(psg_auc* h, size_t n_z, const double* y, const double* predict,
          h->d_small, h->tab[cur][0], h->d_m(cur), n, runkey, lo_of, isnew);
   const NewFlag nf{isnew};
   const NewEmit ne{before};
-  LAUNCH(flag_count_kernel<NewFlag>, nt, s, nf, n, ts);
-  enqueue_row_scan(ts, nt, h->d_words() + 1, 1, s);
-  LAUNCH((flag_emit_kernel<NewFlag, NewEmit>), nt, s, nf, ne, n, ts);
+  enqueue_flag_scan(nf, ne, n, ts, h->d_words() + 1, s);
   LAUNCH(auc_write_new_kernel, blocks_of(n, 256), s, runkey, lo_of, isnew, before, cnt,
          h->d_words(), n, h->d_m(cur), h->d_m(nxt), h->tab[nxt][0], h->tab[nxt][1],
          h->tab[nxt][2], cap);
@@ -539,14 +459,9 @@ int psg_auc_create(psg_ctx* ctx, int64_t goodness, psg_auc** out) {
   HIP_TRY(hipSetDevice(device));
   psg_auc* h = new (std::nothrow) psg_auc();
   if (!h) return fail(PSG_ERR_OOM, "host allocation");
-  h->ctx = ctx;
-  h->device = device;
-  h->stream = stream;
   h->goodness = goodness;
-  if (hipMalloc((void**)&h->d_small, kAucSmallBytes) != hipSuccess ||
-      hipMemset(h->d_small, 0, kAucSmallBytes) != hipSuccess ||
-      hipHostMalloc((void**)&h->h_small, 64) != hipSuccess ||
-      hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess) {
+  if (!h->open(ctx, kAucSmallBytes) ||
+      hipMemset(h->d_small, 0, kAucSmallBytes) != hipSuccess) {
     (void)hipGetLastError();
     psg_auc_destroy(h);
     return fail(PSG_ERR_OOM, "auc control blocks");
@@ -557,17 +472,10 @@ int psg_auc_create(psg_ctx* ctx, int64_t goodness, psg_auc** out) {
 
 void psg_auc_destroy(psg_auc* h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->last_s && h->last_s != h->stream) (void)hipStreamSynchronize(h->last_s);
-  (void)hipStreamSynchronize(h->stream);
-  for (auto& x : h->b)
-    if (x.p) (void)hipFree(x.p);
+  h->close();
   for (auto& set : h->tab)
     for (auto& p : set)
       if (p) (void)hipFree(p);
-  if (h->d_small) (void)hipFree(h->d_small);
-  if (h->h_small) (void)hipHostFree(h->h_small);
-  if (h->ev) (void)hipEventDestroy(h->ev);
   delete h;
 }
 
@@ -786,9 +694,7 @@ int psg_auc_exact_dev(psg_ctx* ctx, const double* y_dev, const double* predict_d
     if (int e = enqueue_radix_sort(key, n, h_small[0] ^ h_small[1], sb, &skey, &spos, s)) return e;
     const PositiveFlag pf{y_dev, spos, n};
     const AreaEmit ae{term};
-    LAUNCH(flag_count_kernel<PositiveFlag>, nt, s, pf, n, ts);
-    enqueue_row_scan(ts, nt, (uint32_t*)(d_small + 4), 1, s);
-    LAUNCH((flag_emit_kernel<PositiveFlag, AreaEmit>), nt, s, pf, ae, n, ts);
+    enqueue_flag_scan(pf, ae, n, ts, (uint32_t*)(d_small + 4), s);
     LAUNCH(sum_u32_kernel, grid, s, term, n, d_small + 3);
     if (int e = launched("exact auc")) return e;
     HIP_TRY(hipMemcpyAsync(h_small + 3, d_small + 3, 16, hipMemcpyDeviceToHost, s));

@@ -1,16 +1,11 @@
-// psg_sort.h -- the device sort and flag scans that psg_worker.hip and
-// psg_auc.hip share: the stable 8-bit LSD radix passes over 64-bit keys with
-// a 32-bit payload (DESIGN.md 4.8 a) and the count / scan / emit of a flag
-// over a sorted array (4.8 b).  Kernels are file-local in each translation
-// unit that includes this (anonymous namespace).
-//
-// The including file states the sort's shape first, in psg::(anonymous):
-// kSortKPT (pairs per lane per tile), kSortTile = 256 * kSortKPT, kWaveSpan =
-// 64 * kSortKPT and kFlagTile = 2048.  psg_worker.hip's are the ones that
-// psg_mb_sort_tile() reports and tests/worker_ref.py mirrors; psg_auc.hip
-// restates them (tests/test_auc.py holds the two equal).  row_scan_kernel
-// stays in psg_worker.hip for the same reason and is reached through
-// enqueue_row_scan.
+// psg_sort.h -- the device sort and scan layer of psg_worker.hip and
+// psg_auc.hip: the stable 8-bit LSD radix passes over 64-bit keys with a
+// 32-bit payload (DESIGN.md 4.8 a), the count / scan / emit of a flag over a
+// sorted array (4.8 b), the binary search and the wave's fold of a run's
+// labels.  It stands alone: the sort's shape is defined here, once, and
+// psg_mb_sort_tile() reports it; tests/worker_ref.py mirrors it.  Kernels
+// are file-local in each translation unit that includes this (anonymous
+// namespace).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -18,13 +13,17 @@
 #include "../../include/psg.h"
 #include "psg_host.h"
 
+#ifndef PSG_SORT_KPT
+#define PSG_SORT_KPT 8  // A/B builds: 4, 16, 32
+#endif
+
 namespace psg {
-
-// psg_worker.hip's row_scan_kernel over `rows` rows of n counts each: row r of
-// c becomes its exclusive scan and total[r] its sum
-void enqueue_row_scan(uint32_t* c, uint32_t n, uint32_t* total, uint32_t rows, hipStream_t s);
-
 namespace {
+
+constexpr int kSortKPT = PSG_SORT_KPT;           // pairs per lane per tile
+constexpr uint32_t kSortTile = 256 * kSortKPT;   // pairs per workgroup
+constexpr uint32_t kWaveSpan = 64 * kSortKPT;    // pairs per wave
+constexpr uint32_t kFlagTile = 2048;             // elements per workgroup of the flag scans
 
 // XCD-contiguous runs of consecutive tiles (as psg_countmin.hip): tiles next
 // to each other write next to each other in every digit's output range, and
@@ -57,6 +56,58 @@ __device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* ws, uint3
   }
   *total = t;
   return b + inc - v;
+}
+
+// workgroup r: c[r * n .. + n) becomes its exclusive scan, total[r] its sum
+__global__ __launch_bounds__(256) void row_scan_kernel(uint32_t* __restrict__ c, uint32_t n,
+                                                       uint32_t* __restrict__ total) {
+  __shared__ uint32_t ws[4];
+  uint32_t* row = c + (size_t)blockIdx.x * n;
+  uint32_t carry = 0;
+  for (uint32_t b = 0; b < n; b += 256) {
+    const uint32_t i = b + threadIdx.x;
+    const uint32_t v = i < n ? row[i] : 0u;
+    uint32_t tot;
+    const uint32_t ex = block_exscan(v, ws, &tot);
+    if (i < n) row[i] = carry + ex;
+    carry += tot;
+  }
+  if (threadIdx.x == 0) total[blockIdx.x] = carry;
+}
+
+// first index of k[0 .. n) that holds `key` or more
+template <class T>
+__device__ __forceinline__ uint32_t lower_bound(const T* __restrict__ k, uint32_t n, T key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (k[mid] < key) {
+      lo = mid + 1;
+    } else {
+      hi = mid;
+    }
+  }
+  return lo;
+}
+
+// One lane per sorted item, r its run.  The lanes of a wave that share a run
+// (they are neighbours) fold their labels with ballots: true in the first
+// lane of each such group, with the group's positives and negatives.  Every
+// lane of the wave comes here.
+__device__ __forceinline__ bool run_label_counts(uint32_t r, bool valid, bool positive,
+                                                 uint32_t lane, uint32_t* cp, uint32_t* cn) {
+  const uint32_t rprev = __shfl_up(r, 1, 64);
+  const bool head = valid && (lane == 0 || r != rprev);
+  const uint64_t heads = __ballot(head), posb = __ballot(positive), val = __ballot(valid);
+  if (head) {
+    const uint64_t above = heads & ~((2ull << lane) - 1);  // the groups after this one
+    const int end = above ? __ffsll((unsigned long long)above) - 1 : 64;
+    const uint64_t upto = end == 64 ? ~0ull : (1ull << end) - 1;
+    const uint64_t seg = upto & ~((1ull << lane) - 1) & val;
+    *cp = (uint32_t)__popcll(seg & posb);
+    *cn = (uint32_t)__popcll(seg) - *cp;
+  }
+  return head;
 }
 
 // the valid lanes of the wave whose digit equals this lane's
@@ -259,6 +310,17 @@ inline int launched(const char* what) {
   return PSG_OK;
 }
 
+// n elements: e(i, flagged elements before i, f(i), n) for every i, and
+// *total = the flagged elements; tile_sum: blocks_of(n, kFlagTile) words
+template <class Flag, class Emit>
+void enqueue_flag_scan(Flag f, Emit e, uint32_t n, uint32_t* tile_sum, uint32_t* total,
+                       hipStream_t s) {
+  const uint32_t nt = blocks_of(n, kFlagTile);
+  LAUNCH(flag_count_kernel<Flag>, nt, s, f, n, tile_sum);
+  LAUNCH(row_scan_kernel, 1, s, tile_sum, nt, total);
+  LAUNCH((flag_emit_kernel<Flag, Emit>), nt, s, f, e, n, tile_sum);
+}
+
 // The two sides of the sort's ping-pong, its per-tile digit counts
 // (256 * tiles words) and the 256 digit totals.  `kin` may be key_b.
 struct SortBuffers {
@@ -280,7 +342,7 @@ inline int enqueue_radix_sort(const uint64_t* kin, uint32_t n, uint64_t differ,
   for (int d = 0; d < 8; ++d) {
     if (((differ >> (8 * d)) & 255u) == 0) continue;  // the same digit in every key
     LAUNCH(sort_count_kernel, ntiles, s, kin, n, 8 * d, b.counts, ntiles);
-    enqueue_row_scan(b.counts, ntiles, b.dtotal, 256, s);
+    LAUNCH(row_scan_kernel, 256, s, b.counts, ntiles, b.dtotal);
     LAUNCH(sort_scatter_kernel, ntiles, s, kin, pin, kout, pout, n, 8 * d, b.counts, b.dtotal,
            ntiles);
     kin = kout;

@@ -6,9 +6,9 @@
 // (src/linear_method/loss.h:73-85) and grad = Z' * (-y tau)
 // (base/matrix.h:57-58 over sparse_matrix.h:87-105).  Kernels first, the
 // psg_mb_* entry points of include/psg.h after them.
-// The kernels of (a) and the flag scans of (b), (c) are in psg_sort.h, which
-// psg_auc.hip includes too; their shape constants and row_scan_kernel are
-// stated here.
+// The kernels of (a), the flag scans of (b), (c), the binary search and the
+// ballot fold of (d) are in psg_sort.h, with the sort's shape constants;
+// psg_auc.hip includes it too, and psg_blocks.h, the base of both handles.
 //
 // (a) Sort.  countUniqIndex sorts (key, position) pairs by key
 // (parallelSort over pair_).  Here: a stable LSD radix sort of the 64-bit
@@ -68,52 +68,12 @@
 #include <vector>
 
 #include "../../include/psg.h"
+#include "psg_blocks.h"
 #include "psg_host.h"
 #include "psg_internal.h"
+#include "psg_sort.h"
 
 namespace psg {
-namespace {
-
-#ifndef PSG_SORT_KPT
-#define PSG_SORT_KPT 8  // A/B builds: 4, 16, 32
-#endif
-constexpr int kSortKPT = PSG_SORT_KPT;           // pairs per lane per tile
-constexpr uint32_t kSortTile = 256 * kSortKPT;   // pairs per workgroup
-constexpr uint32_t kWaveSpan = 64 * kSortKPT;    // pairs per wave
-constexpr uint32_t kFlagTile = 2048;             // elements per workgroup of the flag scans
-
-}  // namespace
-}  // namespace psg
-
-#include "psg_sort.h"  // the sort and flag-scan kernels, of the shape above
-
-namespace psg {
-namespace {
-
-// workgroup r: c[r * n .. + n) becomes its exclusive scan, total[r] its sum
-__global__ __launch_bounds__(256) void row_scan_kernel(uint32_t* __restrict__ c, uint32_t n,
-                                                       uint32_t* __restrict__ total) {
-  __shared__ uint32_t ws[4];
-  uint32_t* row = c + (size_t)blockIdx.x * n;
-  uint32_t carry = 0;
-  for (uint32_t b = 0; b < n; b += 256) {
-    const uint32_t i = b + threadIdx.x;
-    const uint32_t v = i < n ? row[i] : 0u;
-    uint32_t tot;
-    const uint32_t ex = block_exscan(v, ws, &tot);
-    if (i < n) row[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) total[blockIdx.x] = carry;
-}
-
-}  // namespace
-
-// what psg_sort.h's pass loop, and psg_auc.hip through it, launch the scan by
-void enqueue_row_scan(uint32_t* c, uint32_t n, uint32_t* total, uint32_t rows, hipStream_t s) {
-  hipLaunchKernelGGL(row_scan_kernel, dim3(rows), dim3(256), 0, s, c, n, total);
-}
-
 namespace {
 
 #ifndef PSG_LONG_RUN
@@ -187,15 +147,7 @@ __global__ __launch_bounds__(256) void run_search_kernel(const uint64_t* __restr
   const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (r >= n_uniq) return;
   const uint64_t key = uniq_key[r];
-  uint32_t lo = 0, hi = ndict;  // first index with dict[index] >= key
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (dict[mid] < key) {
-      lo = mid + 1;
-    } else {
-      hi = mid;
-    }
-  }
+  const uint32_t lo = lower_bound(dict, ndict, key);
   const bool found = lo < ndict && dict[lo] == key;
   run_rank[r] = found ? lo + 1 : 0u;
   if (found) dict_run[lo] = (uint32_t)r;
@@ -268,15 +220,8 @@ __global__ __launch_bounds__(256) void count_keys_kernel(
     uint32_t at;
     positive = y[pair_row(spos, row_of, i, n, &at)] > 0;
   }
-  const uint32_t rprev = __shfl_up(r, 1, 64);
-  const bool head = valid && (lane == 0 || r != rprev);
-  const uint64_t heads = __ballot(head), posb = __ballot(positive), val = __ballot(valid);
-  if (head) {
-    const uint64_t above = heads & ~((2ull << lane) - 1);  // the groups after this one
-    const int end = above ? __ffsll((unsigned long long)above) - 1 : 64;
-    const uint64_t upto = end == 64 ? ~0ull : (1ull << end) - 1;
-    const uint64_t seg = upto & ~((1ull << lane) - 1) & val;
-    const uint32_t cp = (uint32_t)__popcll(seg & posb), cn = (uint32_t)__popcll(seg) - cp;
+  uint32_t cp, cn;
+  if (run_label_counts(r, valid, positive, lane, &cp, &cn)) {
     const uint32_t rank = r < n_uniq ? run_rank[r] : 0u;
     if (rank != 0 && rank <= ndict) {
       if (cp) atomicAdd(&pos[rank - 1], cp);
@@ -417,6 +362,17 @@ __global__ __launch_bounds__(256) void trans_times_long_kernel(
 }
 
 // ---- (f) ------------------------------------------------------------------------
+// the tree sum of the workgroup's 256 values v, over s (256 doubles of LDS):
+// s[0] on return, for lane 0 to read
+__device__ __forceinline__ void block_tree_sum(double v, double* s) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+    __syncthreads();
+  }
+}
+
 // loss.h:74,81 as written; partial[workgroup] = the tree sum of its 256 losses
 __global__ __launch_bounds__(256) void logit_kernel(const double* __restrict__ y,
                                                     const double* __restrict__ xw, uint32_t rows,
@@ -435,12 +391,7 @@ __global__ __launch_bounds__(256) void logit_kernel(const double* __restrict__ y
     c[i] = -yi * t;
     loss[i] = l;
   }
-  s[threadIdx.x] = l;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-    __syncthreads();
-  }
+  block_tree_sum(l, s);
   if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
 }
 
@@ -450,12 +401,7 @@ __global__ __launch_bounds__(256) void objv_kernel(const double* __restrict__ pa
   __shared__ double s[256];
   double a = 0.0;
   for (uint32_t p = threadIdx.x; p < nparts; p += 256) a += partial[p];
-  s[threadIdx.x] = a;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-    __syncthreads();
-  }
+  block_tree_sum(a, s);
   if (threadIdx.x == 0) *objv = s[0];
 }
 
@@ -510,16 +456,7 @@ __global__ __launch_bounds__(256) void row_start_kernel(const uint64_t* __restri
                                                         uint32_t* __restrict__ row_start) {
   const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (r > rows) return;
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo) / 2;
-    if (rkey[mid] < r) {
-      lo = mid + 1;
-    } else {
-      hi = mid;
-    }
-  }
-  row_start[r] = lo;
+  row_start[r] = lower_bound(rkey, n, r);
 }
 
 // range[2k], range[2k + 1] = key k's run of sorted pairs (0, 0: none)
@@ -600,7 +537,9 @@ __global__ __launch_bounds__(256) void darling_sum_short_kernel(
 // chain_sum over pairs of terms: one load and one LDS read bring both terms
 // of a sorted pair, and each has its own accumulator, so the two add chains
 // overlap.  A load is 16 B per lane here, so half as many are kept ahead.
-// stage: 64 x kChainAhead2 double2 of the wave.
+// stage: 64 x kChainAhead2 double2 of the wave.  Not chain_sum as a template
+// over double / double2: its double2 arrays spill (darling_sum_long_kernel 87
+// VGPRs and 160 B of scratch per lane, against 117 and none split by hand).
 #ifndef PSG_CHAIN_AHEAD2
 #define PSG_CHAIN_AHEAD2 4
 #endif
@@ -741,15 +680,8 @@ __global__ __launch_bounds__(256) void darling_rows_kernel(
   const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   if (r >= rows) return;
   const uint32_t e = row_start[r + 1] < n ? row_start[r + 1] : n;
-  uint32_t a = row_start[r] < e ? row_start[r] : e, z = e;
-  while (a < z) {  // the first entry at or past lo
-    const uint32_t mid = a + (z - a) / 2;
-    if (row_pair[mid] < lo) {
-      a = mid + 1;
-    } else {
-      z = mid;
-    }
-  }
+  uint32_t a = row_start[r] < e ? row_start[r] : e;
+  a += lower_bound(row_pair + a, e - a, lo);  // the first entry at or past lo
   double d = 0.0;
   bool touched = false;
   for (uint32_t j = a; j < e; ++j) {
@@ -770,12 +702,7 @@ __global__ __launch_bounds__(256) void darling_objv_kernel(const double* __restr
                                                            double* __restrict__ partial) {
   __shared__ double s[256];
   const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  s[threadIdx.x] = i < rows ? log(1 + 1 / dual[i]) : 0.0;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-    __syncthreads();
-  }
+  block_tree_sum(i < rows ? log(1 + 1 / dual[i]) : 0.0, s);
   if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
 }
 
@@ -806,12 +733,7 @@ enum State { S_NEW = 0, S_LOADED, S_UNIQ, S_LOCAL, S_GRAD };
 
 }  // namespace
 
-struct psg_minibatch {
-  psg_ctx* ctx = nullptr;
-  int device = 0;
-  hipStream_t stream = nullptr;  // the context's
-  hipEvent_t ev = nullptr;       // the last enqueue, for calls on another stream
-  hipStream_t last_s = nullptr;
+struct psg_minibatch : psg::DeviceBlocks<B_COUNT> {
   int state = S_NEW;
   size_t rows = 0, nnz = 0, n_uniq = 0, ndict = 0;
   bool binary = false;
@@ -828,13 +750,7 @@ struct psg_minibatch {
   std::vector<uint32_t> pair_lo, pair_hi;
   size_t n_long = 0;  // the length of the long-run list, read at psg_mb_darling_init
   size_t last_cb = 0, last_ce = 0;  // the columns of the last psg_mb_darling_update_dual
-  struct Buf {
-    void* p = nullptr;
-    size_t cap = 0;
-  } b[B_COUNT];
   size_t scratch_len[4] = {0, 0, 0, 0};
-  unsigned long long* d_small = nullptr;
-  unsigned long long* h_small = nullptr;  // pinned, 8 words
   // psg_mb_profile: a pair of timing events around each stage's launches
   bool prof = false;
   hipEvent_t tev[2 * PSG_MB_STAGES] = {};
@@ -844,41 +760,8 @@ struct psg_minibatch {
     if (prof && tev[i] && hipEventRecord(tev[i], s) == hipSuccess) tset[i] = true;
   }
 
-  template <class T>
-  T* at(int id) const {
-    return (T*)b[id].p;
-  }
   uint32_t* d_u32(int word) const { return (uint32_t*)(d_small + 4) + word; }
   uint32_t* d_dtotal() const { return (uint32_t*)(d_small + 6); }
-
-  // Buffers only grow.  Growing one frees the old block, which waits for the
-  // device, so nothing in flight can still use it.
-  int need(int id, size_t bytes) {
-    if (bytes <= b[id].cap) return PSG_OK;
-    if (b[id].p) HIP_TRY(hipFree(b[id].p));
-    b[id].p = nullptr;
-    b[id].cap = 0;
-    const size_t cap = (bytes + 4095) / 4096 * 4096;
-    HIP_TRY(hipMalloc(&b[id].p, cap));
-    b[id].cap = cap;
-    return PSG_OK;
-  }
-  int order(hipStream_t s) {
-    if (last_s && last_s != s) HIP_TRY(hipStreamWaitEvent(s, ev, 0));
-    return PSG_OK;
-  }
-  int mark(hipStream_t s) {
-    HIP_TRY(hipEventRecord(ev, s));
-    last_s = s;
-    return PSG_OK;
-  }
-  // everything enqueued for this minibatch, on whatever stream, has run
-  int settle() {
-    if (last_s && last_s != stream) HIP_TRY(hipStreamSynchronize(last_s));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PSG_OK;
-  }
-  hipStream_t pick(void* s) const { return s ? (hipStream_t)s : stream; }
 };
 
 namespace {
@@ -935,13 +818,7 @@ int psg_mb_create(psg_ctx* ctx, psg_minibatch** out) {
   HIP_TRY(hipSetDevice(device));
   psg_minibatch* mb = new (std::nothrow) psg_minibatch();
   if (!mb) return fail(PSG_ERR_OOM, "host allocation");
-  mb->ctx = ctx;
-  mb->device = device;
-  mb->stream = stream;
-  if (hipMalloc((void**)&mb->d_small, kSmallBytes) != hipSuccess ||
-      hipHostMalloc((void**)&mb->h_small, 64) != hipSuccess ||
-      hipEventCreateWithFlags(&mb->ev, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
+  if (!mb->open(ctx, kSmallBytes)) {
     psg_mb_destroy(mb);
     return fail(PSG_ERR_OOM, "minibatch control blocks");
   }
@@ -951,14 +828,7 @@ int psg_mb_create(psg_ctx* ctx, psg_minibatch** out) {
 
 void psg_mb_destroy(psg_minibatch* mb) {
   if (!mb) return;
-  (void)hipSetDevice(mb->device);
-  if (mb->last_s && mb->last_s != mb->stream) (void)hipStreamSynchronize(mb->last_s);
-  (void)hipStreamSynchronize(mb->stream);
-  for (auto& x : mb->b)
-    if (x.p) (void)hipFree(x.p);
-  if (mb->d_small) (void)hipFree(mb->d_small);
-  if (mb->h_small) (void)hipHostFree(mb->h_small);
-  if (mb->ev) (void)hipEventDestroy(mb->ev);
+  mb->close();
   for (hipEvent_t e : mb->tev)
     if (e) (void)hipEventDestroy(e);
   delete mb;
@@ -982,10 +852,7 @@ int psg_mb_load(psg_minibatch* mb, const uint64_t* offset, size_t rows, const ui
   mb->darling = false;
   mb->xw_own = false;
   const size_t n = (size_t)nnz, ntiles = blocks_of(n, kSortTile);
-  struct {
-    int id;
-    size_t bytes;
-  } const want[] = {
+  if (int rc = mb->need_all({
       {B_OFFSET, 8 * (rows + 1)}, {B_Y, 8 * rows}, {B_INDEX, 8 * n},
       {B_VALUE, value ? 8 * n : 0}, {B_KEY_A, 8 * n}, {B_KEY_B, 8 * n}, {B_POS_A, 4 * n},
       {B_POS_B, 4 * n}, {B_COUNTS, 4 * 256 * ntiles},
@@ -994,9 +861,8 @@ int psg_mb_load(psg_minibatch* mb, const uint64_t* offset, size_t rows, const ui
       {B_RUN_RANK, 4 * n}, {B_REMAPPED, 4 * n}, {B_BEFORE, 4 * (n + 1)},
       {B_NEW_OFFSET, 8 * (rows + 1)}, {B_NEW_INDEX, 4 * n}, {B_NEW_VALUE, value ? 8 * n : 0},
       {B_TERM, 8 * n}, {B_XW, 8 * rows}, {B_TAU, 8 * rows}, {B_C, 8 * rows}, {B_LOSS, 8 * rows},
-      {B_PARTIAL, 8 * (size_t)blocks_of(rows, 256) + 8}};
-  for (const auto& w : want)
-    if (int rc = mb->need(w.id, w.bytes)) return rc;
+      {B_PARTIAL, 8 * (size_t)blocks_of(rows, 256) + 8}}))
+    return rc;
   hipStream_t s = mb->stream;
   HIP_TRY(hipMemcpyAsync(mb->b[B_OFFSET].p, offset, 8 * (rows + 1), hipMemcpyHostToDevice, s));
   if (rows) HIP_TRY(hipMemcpyAsync(mb->b[B_Y].p, y, 8 * rows, hipMemcpyHostToDevice, s));
@@ -1040,14 +906,10 @@ int psg_mb_uniq(psg_minibatch* mb, const uint64_t** keys_dev, const uint32_t** c
       if (int rc = enqueue_sort(mb, s)) return rc;
       mb->tick(PSG_MB_STAGE_SORT, 1, s);
       mb->tick(PSG_MB_STAGE_RUNS, 0, s);
-      const uint32_t nt = blocks_of(n, kFlagTile);
-      uint32_t* ts = mb->at<uint32_t>(B_TILE_SUM);
       const HeadFlag f{mb->skey};
       const HeadEmit e{mb->skey, mb->at<uint64_t>(B_UNIQ_KEY), mb->at<uint32_t>(B_RUN_START),
                        mb->at<uint32_t>(B_RUN_OF)};
-      LAUNCH(flag_count_kernel<HeadFlag>, nt, s, f, n, ts);
-      LAUNCH(row_scan_kernel, 1, s, ts, nt, mb->d_u32(0));
-      LAUNCH((flag_emit_kernel<HeadFlag, HeadEmit>), nt, s, f, e, n, ts);
+      enqueue_flag_scan(f, e, n, mb->at<uint32_t>(B_TILE_SUM), mb->d_u32(0), s);
       mb->tick(PSG_MB_STAGE_RUNS, 1, s);
       if (int rc = launched("run heads")) return rc;
       HIP_TRY(hipMemcpyAsync(mb->h_small + 4, mb->d_small + 4, 8, hipMemcpyDeviceToHost, s));
@@ -1075,11 +937,10 @@ int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
   if (ndict >= 0xffffffffull)  // CHECK_LT(idx_dict.size(), kuint32max), localizer.h:115
     return fail(PSG_ERR_SIZE, "dictionary of %zu keys >= 2^32 - 1", ndict);
   HIP_TRY(hipSetDevice(mb->device));
-  if (int rc = mb->need(B_DICT_RUN, 4 * ndict)) return rc;
-  if (int rc = mb->need(B_CNT_POS, 4 * ndict)) return rc;
-  if (int rc = mb->need(B_CNT_NEG, 4 * ndict)) return rc;
-  if (int rc = mb->need(B_GRAD, 8 * ndict)) return rc;
-  if (int rc = mb->need(B_LONG_LIST, 4 * ndict)) return rc;
+  if (int rc = mb->need_all({{B_DICT_RUN, 4 * ndict}, {B_CNT_POS, 4 * ndict},
+                             {B_CNT_NEG, 4 * ndict}, {B_GRAD, 8 * ndict},
+                             {B_LONG_LIST, 4 * ndict}}))
+    return rc;
   hipStream_t s = mb->pick(stream);
   if (int rc = mb->order(s)) return rc;
   mb->state = S_UNIQ;
@@ -1099,14 +960,10 @@ int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
     HIP_TRY(hipMemsetAsync(mb->b[B_REMAPPED].p, 0, 4 * (size_t)n, s));
     LAUNCH(remap_kernel, blocks_of(n, 256), s, mb->spos, mb->at<uint32_t>(B_RUN_OF),
            mb->at<uint32_t>(B_RUN_RANK), n, nu, mb->at<uint32_t>(B_REMAPPED));
-    const uint32_t nt = blocks_of(n, kFlagTile);
-    uint32_t* ts = mb->at<uint32_t>(B_TILE_SUM);
     const KeptFlag f{mb->at<uint32_t>(B_REMAPPED)};
     const KeptEmit e{mb->at<uint32_t>(B_REMAPPED), mb->binary ? nullptr : mb->at<double>(B_VALUE),
                      before, mb->at<uint32_t>(B_NEW_INDEX), mb->at<double>(B_NEW_VALUE)};
-    LAUNCH(flag_count_kernel<KeptFlag>, nt, s, f, n, ts);
-    LAUNCH(row_scan_kernel, 1, s, ts, nt, mb->d_u32(1));
-    LAUNCH((flag_emit_kernel<KeptFlag, KeptEmit>), nt, s, f, e, n, ts);
+    enqueue_flag_scan(f, e, n, mb->at<uint32_t>(B_TILE_SUM), mb->d_u32(1), s);
   } else {
     HIP_TRY(hipMemsetAsync(before, 0, 4, s));
   }
@@ -1377,16 +1234,12 @@ int psg_mb_darling_init(psg_minibatch* mb, double delta_init, const double* w_de
   HIP_TRY(hipSetDevice(mb->device));
   mb->darling = false;
   const size_t rows_z = mb->rows, n_z = mb->nnz, nd_z = mb->ndict;
-  struct {
-    int id;
-    size_t bytes;
-  } const want[] = {
+  if (int rc = mb->need_all({
       {B_DUAL, 8 * rows_z}, {B_CUR_W, 8 * nd_z}, {B_DELTA, 8 * nd_z}, {B_ACTIVE, nd_z},
       {B_DELTA_W, 8 * nd_z}, {B_EXP_DELTA, mb->binary ? 8 * nd_z : 0}, {B_TERM2, 16 * n_z},
       {B_RKEY_A, 8 * n_z}, {B_RKEY_B, 8 * n_z}, {B_RPOS_A, 4 * n_z}, {B_RPOS_B, 4 * n_z},
-      {B_ROW_START, 4 * (rows_z + 1)}, {B_COL_RANGE, 8 * nd_z}};
-  for (const auto& w : want)
-    if (int rc = mb->need(w.id, w.bytes)) return rc;
+      {B_ROW_START, 4 * (rows_z + 1)}, {B_COL_RANGE, 8 * nd_z}}))
+    return rc;
   hipStream_t s = mb->pick(stream);
   if (int rc = mb->order(s)) return rc;
   const uint32_t n = (uint32_t)n_z, nd = (uint32_t)nd_z, nu = (uint32_t)mb->n_uniq;

@@ -161,18 +161,20 @@ def test_bad_arguments_need_no_device():
 
 
 def test_the_sort_shape_of_psg_auc_is_the_workers():
-    """psg_auc.hip restates the shape that psg_sort.h's kernels are built to;
-    the GPU tests size their cases by psg_mb_sort_tile(), psg_worker.hip's."""
+    """psg_sort.h defines the shape its kernels are built to, once; psg_auc.hip
+    and psg_worker.hip include it and define none of it, so the GPU tests,
+    which size their cases by psg_mb_sort_tile(), size them for both."""
     import os
     import re
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                         "parameter_server_amd", "csrc")
-    worker = open(os.path.join(csrc, "psg_worker.hip")).read()
-    mine = open(os.path.join(csrc, "psg_auc.hip")).read()
-    kpt = re.findall(r"^#define PSG_SORT_KPT (\d+)\b", worker, flags=re.M)
-    assert len(kpt) == 1
-    assert re.findall(r"^constexpr int kSortKPT = (\d+);", mine, flags=re.M) == kpt
-    for name in ("kSortTile", "kWaveSpan", "kFlagTile"):
-        pat = r"^constexpr uint32_t %s = ([^;]+);" % name
-        a, b = re.findall(pat, worker, flags=re.M), re.findall(pat, mine, flags=re.M)
-        assert len(a) == 1 and a == b, name
+    sort, worker, mine = (open(os.path.join(csrc, f)).read()
+                          for f in ("psg_sort.h", "psg_worker.hip", "psg_auc.hip"))
+    for name in ("PSG_SORT_KPT", "kSortKPT", "kSortTile", "kWaveSpan", "kFlagTile"):
+        pat = r"^\s*(?:#\s*define\s+%s\b|(?:static\s+)?(?:constexpr|const)\b[^;=]*\b%s\s*=)" % (
+            name, name)
+        assert len(re.findall(pat, sort, flags=re.M)) == 1, name
+        for src in (worker, mine):
+            assert not re.findall(pat, src, flags=re.M), name
+    for src in (worker, mine):
+        assert len(re.findall(r'^#include "psg_sort.h"', src, flags=re.M)) == 1

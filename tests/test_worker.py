@@ -93,9 +93,11 @@ def test_sort_cases_make_every_pass_matter():
 
 
 def test_constants_mirror_the_kernel_source():
-    """worker_ref.py sizes the seam case by copies of psg_worker.hip's
-    constants; a change there must change them here."""
-    src = open(os.path.join(ROOT, "parameter_server_amd", "csrc", "psg_worker.hip")).read()
+    """worker_ref.py sizes the seam case by copies of the constants of
+    psg_sort.h (the sort and the scans) and psg_worker.hip (the rest); a
+    change there must change them here.  Each is defined once across the two."""
+    csrc = os.path.join(ROOT, "parameter_server_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in ("psg_sort.h", "psg_worker.hip"))
 
     def number(pattern):
         found = re.findall(pattern, src, flags=re.M)
@@ -109,12 +111,16 @@ def test_constants_mirror_the_kernel_source():
     assert number(r"^constexpr uint32_t kFlagTile = (\d+);") == R.FLAG_TILE
     assert number(r"^constexpr uint32_t kLongGrid = (\d+);") == R.LONG_GRID
     # what the mirrors stand for in the source
-    assert re.search(r"^constexpr uint32_t kSortTile = 256 \* kSortKPT;", src, flags=re.M)
-    assert re.search(r"^constexpr uint32_t kLongRun = PSG_LONG_RUN;", src, flags=re.M)
-    assert re.search(r"^constexpr int kChainAhead = PSG_CHAIN_AHEAD;", src, flags=re.M)
-    assert re.search(r"^constexpr int kChainAhead2 = PSG_CHAIN_AHEAD2;", src, flags=re.M)
-    assert "for (uint32_t b = 0; b < n; b += %d)" % R.SCAN in src      # row_scan_kernel
-    assert "for (uint32_t p = threadIdx.x; p < nparts; p += %d)" % R.SCAN in src  # objv_kernel
+    def once(pattern):
+        return len(re.findall(pattern, src, flags=re.M)) == 1
+
+    assert once(r"^constexpr uint32_t kSortTile = 256 \* kSortKPT;")
+    assert once(r"^constexpr uint32_t kLongRun = PSG_LONG_RUN;")
+    assert once(r"^constexpr int kChainAhead = PSG_CHAIN_AHEAD;")
+    assert once(r"^constexpr int kChainAhead2 = PSG_CHAIN_AHEAD2;")
+    # row_scan_kernel's trips and objv_kernel's
+    assert src.count("for (uint32_t b = 0; b < n; b += %d)" % R.SCAN) == 1
+    assert src.count("for (uint32_t p = threadIdx.x; p < nparts; p += %d)" % R.SCAN) == 1
     assert _lib.lib().psg_mb_sort_tile() == 256 * R.SORT_KPT
 
 

@@ -31,9 +31,10 @@ import numpy as np
 
 U64 = np.uint64
 
-# Mirrors of psg_worker.hip's constants, for the cases that are sized by them
-# (tests/test_worker.py checks each against the line it copies).  The sort
-# tile is read from the library (psg_mb_sort_tile) and passed in.
+# Mirrors of the kernels' constants, for the cases that are sized by them
+# (tests/test_worker.py checks each against the line it copies): SORT_KPT,
+# FLAG_TILE and row_scan_kernel are psg_sort.h's, the rest psg_worker.hip's.
+# The sort tile is read from the library (psg_mb_sort_tile) and passed in.
 SORT_KPT = 8      # PSG_SORT_KPT: the sort tile is 256 * SORT_KPT pairs
 FLAG_TILE = 2048  # kFlagTile: elements per workgroup of the flag scans
 LONG_RUN = 32     # PSG_LONG_RUN: a longer run is summed by a whole wave
