@@ -630,8 +630,12 @@ size_t orc_ff_query(const uint8_t* data, uint32_t n, int k, const uint64_t* keys
 /* tag >> 2, or in 1..4 following bytes when that is 60..63), 1 copy of    */
 /* 4 + ((tag >> 2) & 7) bytes at offset (tag >> 5) << 8 | next byte, 2 / 3  */
 /* copy of 1 + (tag >> 2) bytes at a 2 / 4-byte little-endian offset.      */
-/* PARITY UNPINNED: no snappy test vectors ship in /root/reference; the    */
-/* tests use spec-derived hand-made streams and this file's compressor.    */
+/* DECODER PINNED: no snappy test vectors ship with the reference, so the   */
+/* decoder is checked against streams recorded from google snappy's own    */
+/* compressor (tests/golden/snappy_pin/, tools/record_snappy.py,           */
+/* tests/test_snappy_pin.py), besides the spec-derived hand-made streams.  */
+/* The compressor below stays UNPINNED: a test aid whose output is only    */
+/* checked to decode, here and through the real snappy_uncompress.         */
 /* ---------------------------------------------------------------------- */
 int orc_snappy_uncompressed_length(const uint8_t* src, size_t n, size_t* out) {
   uint64_t v = 0;

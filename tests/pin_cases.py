@@ -8,6 +8,9 @@ same inputs here, check their SHA-256 against the fixture and compare bit for
 bit.  Every input comes from splitmix64 in numpy uint64 arithmetic, never
 from a library RNG, so a fixture does not depend on the numpy version.
 Floats are integers scaled by a power of two, plus listed special values.
+The inputs of the snappy fixtures (tests/golden/snappy_pin/*.npz, recorded
+by tools/record_snappy.py from the real snappy compressor) are built here
+too, the same way: snappy_cases().
 
 What the inputs avoid, and why: two NaNs never meet in one add (which
 payload survives is not fixed by IEEE 754) and +inf never meets -inf, nor
@@ -396,16 +399,353 @@ def cm_case(n, k, seed=0):
     return CmCase(n, k, batches, query)
 
 
+# --------------------------------------------------------------- snappy cases
+# Inputs of tests/golden/snappy_pin/*.npz: tools/record_snappy.py compresses
+# each with the real snappy compressor and stores the stream.  One fixture file
+# per group.  The n of each case was chosen by search with the recorder
+# (element = a literal or a copy after the preamble, what the table form of
+# psg_snappy.hip counts against kTabMax = 4096); recorded with snappy 1.1.8:
+#
+#   case               n   bytes elements  copy-1 high-bit  longest   npend
+#                                                           copy run
+#   keys24          1000    8000     1997     997        0        1     971
+#   keys40_le       2221   17768     4095    1988       23        1    1070
+#   keys40_gt       2222   17776     4097    1988       22        1       -
+#   keys_dense      8200   65600    16369    8150       73        2       -
+#   keys63          2000   16000        1       0        0        0       0
+#   f32_eighths     6000   24000     5755    5339     2095      503       -
+#   f64_sent70      3000   24000     1559     292      138        3     897
+#   f64_sent98      9000   72000     1424      34       16       33    1227
+#   f64_sent_all    9000   72000     1127       0        0     1024    1117
+#   f32_zero       20000   80000     1252       0        0     1024    1242
+#   f32_gauss       1500    6000        1       0        0        0       0
+#   abc             3000    9000      142       0        0      141     137
+#   rep2047        6+12B   12294      149       1        1      148      21
+#   rep2048        6+31B   12319      157       0        0      156      28
+#   records          400   12800      749     370      349        1      17
+#   alpha4          8000    8000     1909    1754     1016      208    1512
+#   len0 .. len61: one literal each (none for len0)
+# and the parts of the two pushes, pushA_p{0..3}_{keys,v0,v1} and
+# pushB_p{0,1}_{keys,v0,v1} (their tallies are in the fixture's meta).
+# keys40_le / keys40_gt: n draws are n keys here (no two collide); 2221 is the
+# largest n in 2000..2499 with <= 4096 elements, 2222 the smallest with more
+# (`tools/record_snappy.py --seam`).  high-bit: copy-1 elements whose offset is
+# 256 or more, i.e. with a non-zero (tag >> 5) << 8 term.  npend: the copies
+# the table form cannot place from the input (snappy_table_npend below, a host
+# replay of the kernel's step 2); more than kTabPend = 64 of them, or more than
+# kTabMax elements (-), and the streamed form decodes the part.  Key and value
+# arrays are copies of copies, so all of them go that way; `records` (400
+# records, chosen so that 1 <= npend <= 64 with hundreds of high-bit copy-1)
+# is the stream the table form decodes itself.
+SNAPPY_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "snappy_pin")
+SNAPPY_GROUPS = ("keys", "values", "bytes", "pushes")
+SNAPPY_SEAM_N = (2221, 2222)  # keys below 2^40: <= 4096 elements, > 4096 elements
+SNAPPY_EDGE_LENGTHS = (0, 1, 4, 15, 16, 17, 60, 61)
+SENTINEL = U64  # Darling's inactive mark: every bit of the f64 set
+
+
+class SnappyCase:
+    def __init__(self, name, group, data):
+        self.name, self.group, self.data = name, group, bytes(data)
+
+    def digest(self):
+        return hashlib.sha256(self.data).hexdigest()
+
+
+def le_bytes(a):
+    a = np.ascontiguousarray(a)
+    return a.astype(a.dtype.newbyteorder("<"), copy=False).tobytes()
+
+
+def random_bytes(seed, n):
+    return le_bytes(splitmix64(seed, (n + 7) // 8))[:n]
+
+
+def keys_below(seed, n, bits):
+    """Sorted distinct keys below 2^bits out of n draws (nested in n)."""
+    return np.unique(splitmix64(seed, n) >> _u(64 - bits))
+
+
+def quantised(seed, n):
+    """f32 multiples of 1/8 in [-4, 4)."""
+    q = ((splitmix64(seed, n) >> _u(40)) % _u(64)).astype(np.int64) - 32
+    return q.astype(np.float32) / np.float32(8)
+
+
+def with_sentinel(seed, n, p):
+    """f64 bits: scaled draws, the all-ones sentinel with probability p."""
+    b = fbits(scaled(splitmix64(seed, n), np.float64)).copy()
+    b[chance(splitmix64(seed + 1, n), p)] = _u(SENTINEL)
+    return b
+
+
+def near_gaussian(seed, n):
+    """f32: the sum of twelve 20-bit uniforms, centred, / 2^20 (exact in f32;
+    no libm, so the bits do not depend on the platform)."""
+    x = splitmix64(seed, 12 * n).reshape(12, n) >> _u(44)
+    return (x.sum(axis=0).astype(np.int64) - 6 * (1 << 20)).astype(np.float32) / np.float32(1 << 20)
+
+
+def short_match_records(seed, n):
+    """n records of 32 bytes: 24 fresh random bytes, then an 8-byte piece.
+    From record 16 on the piece repeats 8 bytes of a record 8 to 55 back (256
+    to 1,791 bytes): three times in four out of that record's fresh bytes,
+    else that record's own piece.  The compressor turns each into a copy-1 of
+    8 to 11 bytes whose source is literal data, or a copy one to a few levels
+    above it: what the table form places straight from the input."""
+    fresh = np.frombuffer(random_bytes(seed, 32 * n), np.uint8).reshape(n, 32).copy()
+    draw = splitmix64(seed + 1, n)
+    for r in range(16, n):
+        d = int(draw[r])
+        s = r - min(r, 8 + d % 48)
+        a = 24 if (d >> 8) % 4 == 0 else (d >> 16) % 17
+        fresh[r, 24:] = fresh[s, a:a + 8]
+    return fresh.tobytes()
+
+
+class SnappyPush:
+    """A server key set D and value pushes [(keys, [vals] * m)], received as
+    snappy parts.  `clean`: the pushes whose keys all lie in D."""
+
+    def __init__(self, name, dtype, m, D, pushes, clean):
+        self.name, self.dtype, self.m = name, np.dtype(dtype), m
+        self.D, self.pushes, self.clean = D, pushes, clean
+
+    def part_names(self, p):
+        return ["push%s_p%d_keys" % (self.name, p)] + \
+               ["push%s_p%d_v%d" % (self.name, p, i) for i in range(self.m)]
+
+
+def snappy_push(name):
+    if name == "A":
+        # f32, m = 2: 3,000 server keys below 2^40, four pushes keeping each
+        # with p = 0.4, values in eighths; the last push carries one key that
+        # is not in D (the matched count falls one short of its size)
+        D = keys_below(41000, 3000, 40)
+        pushes = []
+        for p in range(4):
+            k = D[chance(splitmix64(41100 + p, D.size), 0.4)]
+            if p == 3:
+                extra = D[D.size // 2] + _u(1)
+                assert not np.isin(extra, D)
+                k = np.sort(np.append(k, extra))
+            pushes.append((np.ascontiguousarray(k),
+                           [quantised(41200 + 10 * p + i, k.size) for i in range(2)]))
+        return SnappyPush(name, np.float32, 2, D, pushes, (0, 1, 2))
+    if name == "B":
+        # f64, m = 2, Darling's G (signed) and U (non-negative) of a block: 4,000
+        # server keys, two pushes keeping each with p = 0.3; a key held by one
+        # push alone is inactive (the sentinel, in both arrays) with p = 0.86,
+        # about 60 % of a push -- never on a key both pushes hold, so that no
+        # two NaNs meet in an add
+        D = keys_below(42000, 4000, 40)
+        keep = [chance(splitmix64(42100 + p, D.size), 0.3) for p in range(2)]
+        pushes = []
+        for p in range(2):
+            k = D[keep[p]]
+            off = (keep[p] & ~keep[1 - p])[keep[p]] & chance(splitmix64(42150 + p, k.size), 0.86)
+            g = fbits(scaled(splitmix64(42200 + p, k.size), np.float64)).copy()
+            u = fbits(np.abs(scaled(splitmix64(42300 + p, k.size), np.float64))).copy()
+            g[off] = u[off] = _u(SENTINEL)
+            pushes.append((np.ascontiguousarray(k), [g.view(np.float64), u.view(np.float64)]))
+        return SnappyPush(name, np.float64, 2, D, pushes, (0, 1))
+    raise KeyError(name)
+
+
+SNAPPY_PUSH_NAMES = ("A", "B")
+
+
+def snappy_cases():
+    """[SnappyCase]: what the wire carries, as bytes."""
+    out = []
+
+    def add(group, name, data):
+        out.append(SnappyCase(name, group, data if isinstance(data, bytes) else le_bytes(data)))
+    # sorted distinct uint64 keys
+    add("keys", "keys24", keys_below(40001, 1000, 24))
+    add("keys", "keys40_le", keys_below(40002, SNAPPY_SEAM_N[0], 40))
+    add("keys", "keys40_gt", keys_below(40002, SNAPPY_SEAM_N[1], 40))
+    add("keys", "keys_dense", np.arange(8200, dtype=np.uint64) * _u(3) + _u(7))
+    add("keys", "keys63", keys_below(40003, 2000, 63))
+    # values
+    add("values", "f32_eighths", quantised(40010, 6000))
+    add("values", "f64_sent70", with_sentinel(40020, 3000, 0.70))
+    add("values", "f64_sent98", with_sentinel(40030, 9000, 0.98))
+    add("values", "f64_sent_all", np.full(9000, SENTINEL, np.uint64))
+    add("values", "f32_zero", np.zeros(20000, np.float32))
+    add("values", "f32_gauss", near_gaussian(40040, 1500))
+    # byte patterns
+    add("bytes", "abc", b"abc" * 3000)
+    # a block six times and the first t bytes of a seventh: the compressor cuts
+    # the one long match into 64-byte copies and a rest; t makes the rest 11
+    # bytes, short enough for a copy-1 where the offset allows one (2047: the
+    # largest, tag 0xfd) and a copy-2 where it does not (2048)
+    for n, t in ((2047, 12), (2048, 31)):
+        block = random_bytes(40050 + n, n)
+        add("bytes", "rep%d" % n, block * 6 + block[:t])
+    add("bytes", "records", short_match_records(40070, 400))
+    add("bytes", "alpha4", bytes(b"acgt"[i] for i in (splitmix64(40052, 8000) >> _u(62)).tolist()))
+    for n in SNAPPY_EDGE_LENGTHS:
+        add("bytes", "len%d" % n, random_bytes(40060 + n, n))
+    for pn in SNAPPY_PUSH_NAMES:
+        c = snappy_push(pn)
+        for p, (k, vs) in enumerate(c.pushes):
+            for name, a in zip(c.part_names(p), [k] + [fbits(v) for v in vs]):
+                add("pushes", name, a)
+    return out
+
+
+def snappy_elements(stream):
+    """The tag walk of a raw snappy stream: (declared length, [(position of
+    the tag, kind, length, offset-or-literal-header-bytes)]), kind 0 = literal,
+    1 / 2 / 4 = copy with that many offset bytes.  Stops at the first element
+    that does not fit the stream (a cut one is not listed)."""
+    s, p, ulen, shift = bytes(stream), 0, 0, 0
+    while True:
+        if p >= len(s) or p >= 5:
+            return None, []
+        b = s[p]
+        ulen |= (b & 0x7F) << shift
+        shift += 7
+        p += 1
+        if not b & 0x80:
+            break
+    el = []
+    while p < len(s):
+        tag = s[p]
+        kind = tag & 3
+        if kind == 0:
+            nb = max(tag >> 2, 59) - 59
+            if p + 1 + nb > len(s):
+                break
+            ln = (int.from_bytes(s[p + 1:p + 1 + nb], "little") if nb else tag >> 2) + 1
+            if p + 1 + nb + ln > len(s):
+                break
+            el.append((p, 0, ln, 1 + nb))
+            p += 1 + nb + ln
+        else:
+            nb = (1, 2, 4)[kind - 1]
+            if p + 1 + nb > len(s):
+                break
+            field = int.from_bytes(s[p + 1:p + 1 + nb], "little")
+            if kind == 1:
+                el.append((p, 1, 4 + (tag >> 2 & 7), (tag >> 5) << 8 | field))
+            else:
+                el.append((p, nb, (tag >> 2) + 1, field))
+            p += 1 + nb
+    return ulen, el
+
+
+def snappy_tally(stream):
+    """What a stream holds, for the fixtures' meta and the coverage asserts."""
+    ulen, el = snappy_elements(stream)
+    t = dict(uncompressed=ulen, elements=len(el), literals=0, lit_inline=0, lit_1byte=0, lit_2byte=0,
+             lit_3byte=0, copy1=0, copy1_high=0, copy1_max_offset=0, copy2=0, copy2_min_offset=0,
+             copy4=0, overlapping=0, longest_copy_run=0)
+    run = 0
+    for _, kind, ln, x in el:
+        if kind == 0:
+            t["literals"] += 1
+            t[("lit_inline", "lit_1byte", "lit_2byte", "lit_3byte")[min(x - 1, 3)]] += 1
+            run = 0
+            continue
+        run += 1
+        t["longest_copy_run"] = max(t["longest_copy_run"], run)
+        t["overlapping"] += x < ln
+        if kind == 1:
+            t["copy1"] += 1
+            t["copy1_high"] += x >= 256
+            t["copy1_max_offset"] = max(t["copy1_max_offset"], x)
+        elif kind == 2:
+            t["copy2"] += 1
+            t["copy2_min_offset"] = min(t["copy2_min_offset"] or x, x)
+        else:
+            t["copy4"] += 1
+    t = {k: int(v) for k, v in t.items()}
+    t["table_npend"] = snappy_table_npend(el)
+    return t
+
+
+K_TAB_MAX, K_TAB_PEND, K_TAB_DEPTH = 4096, 64, 4  # psg_snappy.hip kTabMax, kTabPend, kTabDepth
+
+
+def snappy_table_npend(el):
+    """The table form's own count of the copies it cannot place from the input
+    (psg_snappy.hip snappy_tab_kernel step 2, `resolve`): byte l of a copy at
+    output position o with offset a repeats output byte o - a + l mod a; that
+    byte is looked up in the element table, and if it lies in a copy, followed
+    through that copy in the same way, kTabDepth look-ups at the most.  A copy
+    with a byte that has not reached a literal by then is left for step 3, and
+    a part with more than kTabPend of them is decoded again by the streamed
+    form.  None for a part of more than kTabMax elements (the walk stops
+    there and the streamed form decodes it)."""
+    if len(el) > K_TAB_MAX:
+        return None
+    if not el:
+        return 0
+    kind = np.array([e[1] for e in el], np.int64)
+    ln = np.array([e[2] for e in el], np.int64)
+    off = np.where(kind > 0, np.array([e[3] for e in el], np.int64), 1)
+    x = np.concatenate([[0], np.cumsum(ln)[:-1]])  # output position of each element
+    copies = np.nonzero(kind > 0)[0]
+    if copies.size == 0:
+        return 0
+    owner = np.repeat(copies, ln[copies])  # one entry per copied byte
+    l = np.arange(owner.size) - np.repeat(np.cumsum(ln[copies]) - ln[copies], ln[copies])
+    q = x[owner] - off[owner] + l % off[owner]
+    open_ = np.ones(owner.size, bool)
+    for _ in range(K_TAB_DEPTH):
+        j = np.searchsorted(x, q, "right") - 1
+        lit = kind[j] == 0
+        open_ &= ~lit
+        q = np.where(lit, q, x[j] - off[j] + (q - x[j]) % off[j])
+    return int(np.unique(owner[open_]).size)
+
+
+def snappy_form(tally):
+    """Which decoder a part of a launch of <= 64 parts ends in."""
+    n = tally["table_npend"]
+    return "table" if n is not None and n <= K_TAB_PEND else "streamed"
+
+
+_recorded = {}
+
+
+def snappy_recorded():
+    """{name: (case, recorded stream, recorded info)} in case order, each
+    input's SHA-256 checked against the fixture; built once, read only."""
+    if not _recorded:
+        fx = {g: load_fixture(g, SNAPPY_GOLDEN) for g in SNAPPY_GROUPS}
+        for c in snappy_cases():
+            meta, arrays = fx[c.group]
+            info = meta["cases"][c.name]
+            assert info["input_sha256"] == c.digest(), c.name
+            _recorded[c.name] = (c, arrays[c.name].tobytes(), info)
+        assert sum(len(m["cases"]) for m, _ in fx.values()) == len(_recorded)
+    return _recorded
+
+
+def snappy_truncations(stream):
+    """[(what, bytes)]: a stream cut after its preamble, in a copy-1 (tag
+    present, offset byte missing), in a literal and one byte short."""
+    ulen, el = snappy_elements(stream)
+    copy1 = [e for e in el if e[1] == 1]
+    lit = [e for e in el if e[1] == 0 and e[2] >= 2 and e[0] > el[0][0]]
+    c, lt = copy1[len(copy1) // 2], lit[len(lit) // 2]
+    return [("preamble", stream[:el[0][0]]), ("copy1", stream[:c[0] + 1]),
+            ("literal", stream[:lt[0] + lt[3] + lt[2] // 2]), ("short", stream[:-1])]
+
+
 # -------------------------------------------------------------------- fixtures
-def save_fixture(name, meta, arrays):
+def save_fixture(name, meta, arrays, directory=GOLDEN):
     """Recorder only.  meta: JSON-able; arrays: little-endian numpy arrays."""
-    os.makedirs(GOLDEN, exist_ok=True)
+    os.makedirs(directory, exist_ok=True)
     blob = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), np.uint8)
-    np.savez_compressed(os.path.join(GOLDEN, name + ".npz"), meta=blob, **arrays)
+    np.savez_compressed(os.path.join(directory, name + ".npz"), meta=blob, **arrays)
 
 
-def load_fixture(name):
-    with np.load(os.path.join(GOLDEN, name + ".npz")) as z:
+def load_fixture(name, directory=GOLDEN):
+    with np.load(os.path.join(directory, name + ".npz")) as z:
         arrays = {k: z[k] for k in z.files if k != "meta"}
         meta = json.loads(z["meta"].tobytes().decode())
     return meta, arrays

@@ -510,6 +510,8 @@ def test_hold_buffers_option():
 
 
 # ------------------------------------------------------------- snappy ----
+# Streams from the real snappy compressor: tests/test_snappy_pin.py (CPU) and
+# tests/test_snappy_pin_gpu.py over the fixtures of tests/golden/snappy_pin/.
 # Spec-derived known answers (snappy format_description.txt; no snappy
 # vectors ship with the reference): preamble varint, literal, copy-1,
 # overlapping copy-2 (run length), a 4-byte-offset copy, long literals.
