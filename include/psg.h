@@ -255,6 +255,10 @@ int psg_plan_matched(psg_plan* plan, uint64_t* matched);
 int psg_plan_form(psg_plan* plan, int* form);
 /* Algorithmic HBM bytes of one run (SURVEY.md 8d general form). */
 int psg_plan_bytes(psg_plan* plan, uint64_t* bytes, uint64_t* kv_pairs);
+/* The plan's resident bucket index (absent: 0 bytes): its size, 4 bits per
+ * server slot of every tile, and the tiles whose table is not stored (a
+ * bucket of more than 14 keys), which the kernels build on every run. */
+int psg_plan_index_info(psg_plan* plan, uint64_t* index_bytes, uint64_t* marked_tiles);
 int psg_plan_destroy(psg_plan* plan);
 
 /* Device-resident gather (pull reply) over resident keys/values. */

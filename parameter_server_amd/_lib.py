@@ -143,6 +143,7 @@ SIGNATURES = {
     "psg_plan_matched": (C.c_int, [_p, _pu64]),
     "psg_plan_bytes": (C.c_int, [_p, _pu64, _pu64]),
     "psg_plan_form": (C.c_int, [_p, C.POINTER(C.c_int)]),
+    "psg_plan_index_info": (C.c_int, [_p, _pu64, _pu64]),
     "psg_plan_destroy": (C.c_int, [_p]),
     "psg_gather_dev": (C.c_int, [C.c_int, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     "psg_key_union_dev": (C.c_int, [_p, _u64, _p, _u64, _p, _pu64, _p]),

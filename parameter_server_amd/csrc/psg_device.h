@@ -155,6 +155,99 @@ __device__ __forceinline__ uint32_t bucket_scale(uint64_t r32, uint32_t nb) {
   return f >= 4294967295.0f ? 0xffffffffu : (uint32_t)f;
 }
 
+// ----------------------------------------------------------------------
+// A plan's resident bucket index (psg_tile.hip bucket_index_kernel): per
+// tile of kNB buckets, kNB / 2 bytes; nibble b (bits 4 (b % 8) of u32 word
+// b / 8) is the number of server keys in bucket b, 0..14.  A first nibble of
+// 15 marks a tile whose table is not stored (a bucket of more than 14 keys):
+// its kernels build the table themselves, as without an index.
+// One wave decodes a tile: lane l holds the kNB / 64 nibbles of buckets
+// [l kNB / 64, (l + 1) kNB / 64), loaded by bucket_index_load; the bucket
+// starts are the running sum of the counts (an in-lane prefix on packed
+// bytes, then one wave scan).
+// ----------------------------------------------------------------------
+template <int kNB>
+struct BucketIndexWords {
+  static_assert(kNB == 1024 || kNB == 2048 || kNB == 4096, "8, 16 or 32 B per lane");
+  uint32_t x[kNB / 512];
+};
+
+template <int kNB>
+__device__ __forceinline__ BucketIndexWords<kNB> bucket_index_load(const uint32_t* ix, int lane) {
+  typedef uint32_t v2 __attribute__((ext_vector_type(2)));
+  typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+  BucketIndexWords<kNB> r;
+  if constexpr (kNB == 1024) {
+    const v2 a = __builtin_nontemporal_load(
+        (const __attribute__((address_space(1))) v2*)ix + lane);
+    r.x[0] = a.x; r.x[1] = a.y;
+  } else {
+#pragma unroll
+    for (int i = 0; i < kNB / 2048; ++i) {
+      const v4 a = __builtin_nontemporal_load(
+          (const __attribute__((address_space(1))) v4*)ix + lane * (kNB / 2048) + i);
+      r.x[4 * i] = a.x; r.x[4 * i + 1] = a.y; r.x[4 * i + 2] = a.z; r.x[4 * i + 3] = a.w;
+    }
+  }
+  return r;
+}
+
+// inclusive 64-lane prefix sum by DPP (row shifts, then row broadcasts)
+__device__ __forceinline__ uint32_t wave_scan_incl_dpp(uint32_t x) {
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);  // row_shr:1
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);  // row_shr:2
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);  // row_shr:4
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);  // row_shr:8
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
+  return x;
+}
+
+// Called by every lane of ONE wave with the words of bucket_index_load:
+// writes the kNB u16 bucket starts to bt32 (as the kernels' tables: u16 b at
+// half b of the array), and the word past them: bt[kNB] = nt (the end of the
+// last bucket), bt[kNB + 1] = 1 iff the tile is marked -- then the table is
+// zeroed instead, a cleared histogram for the caller's own build.  The
+// caller's next workgroup barrier publishes all of it; bucket_index_marked
+// reads the flag back (workgroup-uniform).
+template <int kNB>
+__device__ __forceinline__ void bucket_index_decode(const BucketIndexWords<kNB>& ix,
+                                                    uint32_t* bt32, uint32_t nt, int lane) {
+  typedef uint32_t v4 __attribute__((ext_vector_type(4)));
+  constexpr int W = kNB / 512;
+  const bool marked = ((uint32_t)__builtin_amdgcn_readfirstlane((int)ix.x[0]) & 15u) == 15u;
+  // per word, on packed bytes (8 counts <= 14: sums below 256): ev/od byte j
+  // = the counts of the word before nibble 2j / 2j + 1
+  uint32_t ev[W], od[W], before[W], tot = 0;
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const uint32_t lo = ix.x[i] & 0x0f0f0f0fu, hi = (ix.x[i] >> 4) & 0x0f0f0f0fu;
+    const uint32_t s = (lo + hi) * 0x01010101u;  // byte j: counts through nibble 2j + 1
+    ev[i] = s - lo - hi;
+    od[i] = s - hi;
+    before[i] = tot;
+    tot += s >> 24;
+  }
+  const uint32_t off = wave_scan_incl_dpp(tot) - tot;
+#pragma unroll
+  for (int i = 0; i < W; ++i) {
+    const uint32_t base = (off + before[i]) * 0x00010001u;  // starts <= nt < 2^16: no carry
+    v4 o;
+    o.x = ((ev[i] & 0xffu) | (od[i] & 0xffu) << 16) + base;
+    o.y = ((ev[i] >> 8 & 0xffu) | (od[i] >> 8 & 0xffu) << 16) + base;
+    o.z = ((ev[i] >> 16 & 0xffu) | (od[i] >> 16 & 0xffu) << 16) + base;
+    o.w = ((ev[i] >> 24) | (od[i] >> 24) << 16) + base;
+    if (marked) o = v4{0u, 0u, 0u, 0u};
+    *(v4*)&bt32[4 * (lane * W + i)] = o;
+  }
+  if (lane == 0) bt32[kNB / 2] = nt | (marked ? 0x10000u : 0u);
+}
+
+template <int kNB>
+__device__ __forceinline__ bool bucket_index_marked(const uint32_t* bt32) {
+  return ((uint32_t)__builtin_amdgcn_readfirstlane((int)bt32[kNB / 2]) >> 16) != 0u;
+}
+
 // One step of the per-key fold in push-arrival order.  p = push index in
 // this launch, lp = last push index in this launch that held the key (-1:
 // none yet).  Serial (the reference default) adds +0.0 for every absent

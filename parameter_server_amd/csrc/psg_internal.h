@@ -72,8 +72,8 @@ struct TileDesc {
   uint32_t flags;
   uint32_t segb;                  // the job's segb
   const uint64_t* dpos;           // dense jobs: job position of each push's first key
-  // tile kernel: the tile's bucket table built once with D (a plan's resident
-  // bucket index, launch_bucket_index), or null: built in the kernel
+  // the tile's bucket counts built once with D (a plan's resident bucket
+  // index, launch_bucket_index), or null: the table is built in the kernel
   const uint32_t* bt;
 };
 
@@ -129,11 +129,13 @@ hipError_t launch_partition(const JobDev* d_jobs, const uint32_t* d_split_item_j
 // tiles)
 hipError_t launch_aggregate_tile(int dtype, int m, const TileDesc* d_tiles, uint32_t ntiles,
                                  int form, hipStream_t stream);
-// the bucket tables of the tile kernel's tiles (psg_tile.hip), built from D
-// alone: bucket_index_words(wide) u32 per tile at out + tile * words
+// the bucket index of the aggregate kernels' tiles (psg_tile.hip), built from
+// D alone: bucket_index_words(tile_slots) u32 per tile at out + tile * words,
+// 4 bits per bucket (the format and its decoder: psg_device.h); *nmarked
+// (zeroed by the caller) counts the tiles whose table is not stored
 uint32_t bucket_index_words(uint32_t tile_slots);
 hipError_t launch_bucket_index(const TileDesc* d_tiles, uint32_t ntiles, uint32_t tile_slots,
-                               uint32_t* out,
+                               uint32_t* out, unsigned long long* nmarked,
                                hipStream_t stream);
 // cursor form (d_chunks non-null): one workgroup per chunk of consecutive
 // tiles (t0, t1 index d_tiles), boundary words (nchunks + 1) x kPackCursorPushes

@@ -197,6 +197,7 @@ struct JobTable {
   // plans (D fixed for their lifetime): the stream jobs' splitters are
   // written once, at build, and a run launches only the partition proper
   bool split_once = false;
+  uint64_t index_bytes = 0, marked_tiles = 0;  // a plan's resident bucket index
   bool all_search = false;  // every job's partition searches (launch_partition xcd)
   void* blob = nullptr;
   size_t blob_bytes = 0;
@@ -402,6 +403,9 @@ struct JobTable {
     const uint32_t iw = psg::bucket_index_words(tile);
     const size_t index_off = off;
     if (use_index) off = align_up(off + 4 * (size_t)iw * tiles, 256);
+    // the index kernel's count of marked tiles (read back once, below)
+    const size_t marked_off = off;
+    if (use_index) off += 256;
     const size_t sitems_off = off;
     off = align_up(off + 4 * sitems, 256);
     const size_t items_off = off;
@@ -485,6 +489,7 @@ struct JobTable {
     // (seg, splitters, bucket index) by a kernel before any read.  Zeroing
     // the whole image cost ~0.1 ms per flush of a 16.8 M-slot aggregate
     memset(img + zero_off, 0, zero_end - zero_off);
+    if (use_index) memset(img + marked_off, 0, 8);
     psg::TileDesc* htiles = (psg::TileDesc*)(img + tiles_off);
     uint32_t* hsitems = (uint32_t*)(img + sitems_off);
     uint64_t* hitems = (uint64_t*)(img + items_off);
@@ -670,15 +675,26 @@ struct JobTable {
     if (cacheable) last_shape.swap(shape);
     else last_shape.clear();
     HIP_TRY(hipEventRecord(himg_ev[ib], strm));
+    index_bytes = 0;
+    marked_tiles = 0;
     if (use_index)
       HIP_TRY(psg::launch_bucket_index(d_tiles, ntiles, tile,
-                                       (uint32_t*)((char*)blob + index_off), strm));
+                                       (uint32_t*)((char*)blob + index_off),
+                                       (unsigned long long*)((char*)blob + marked_off), strm));
     split_once = index && nsplit > 0 && !dense && !cursor && !pcursor;
     all_search = true;
     for (const JobDev& d : h) all_search = all_search && d.mode == psg::kSearch;
     if (split_once)  // the splitter pass alone (it also clears the fail counters once)
       HIP_TRY(psg::launch_partition(d_jobs, d_split_items, nsplit, nullptr, 0, strm));
     if (!async) HIP_TRY(hipStreamSynchronize(strm));
+    if (use_index) {  // plans only (built synchronously)
+      index_bytes = 4 * (uint64_t)iw * tiles;
+      if (tiles) {
+        HIP_TRY(hipMemcpyAsync(&marked_tiles, (char*)blob + marked_off, 8, hipMemcpyDeviceToHost,
+                               strm));
+        HIP_TRY(hipStreamSynchronize(strm));
+      }
+    }
     return PSG_OK;
   }
 
@@ -1636,6 +1652,13 @@ int psg_plan_form(psg_plan* plan, int* form) {
           : T.pack  ? PSG_KERNEL_PACKED
           : T.wide  ? PSG_KERNEL_TILE64
                     : PSG_KERNEL_TILE;
+  return PSG_OK;
+}
+
+int psg_plan_index_info(psg_plan* plan, uint64_t* index_bytes, uint64_t* marked_tiles) {
+  if (!plan) return fail(PSG_ERR_ARG, "null plan");
+  if (index_bytes) *index_bytes = plan->table.index_bytes;
+  if (marked_tiles) *marked_tiles = plan->table.marked_tiles;
   return PSG_OK;
 }
 

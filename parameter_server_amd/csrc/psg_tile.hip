@@ -83,9 +83,9 @@ __device__ __forceinline__ AS1 T* GW(T* p) {
 //      so its push-uniform rounds are fuller (cfg3: ~30 -> ~60 of 64 lanes).
 constexpr int ts_of(int g) { return g == 64 ? kWideSlots : kTileSlots; }
 constexpr int nt_of(int g) { return ts_of(g) / 4; }
-// one bucket per slot in both forms: a plan's resident index is then 2 B per
-// slot of HBM reads per run (2 per slot measured 2.5 % slower on cfg2,
-// profiles/r03_ab_index.txt)
+// one bucket per slot in both forms (2 slots per bucket measured 2.5 %
+// slower on cfg2, profiles/r03_ab_index.txt); a plan's resident index is
+// 4 bits per slot of HBM reads per run
 constexpr int nb_of(int g) { return ts_of(g); }
 constexpr int cb_of(int g) { return ts_of(g) / 64 > 16 ? 5 : 4; }  // round-chunk bits
 static_assert(ts_of(64) <= 0x7ffe, "u16 positions");
@@ -103,10 +103,10 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
 #define PSG_FUSECNT 1  // A/B builds: 0 = sums and contributor counts in separate arrays
 #endif
 #ifndef PSG_DDMA
-#define PSG_DDMA 1  // A/B builds: 0 = D and the resident bucket table through registers
+#define PSG_DDMA 1  // A/B builds: 0 = D through registers
 #endif
 // 16 B per lane from global memory straight into LDS (gfx950 LDS-DMA): lane l
-// writes lds + 16 l; nontemporal (D and the bucket table are read by one tile)
+// writes lds + 16 l; nontemporal (D is read by one tile)
 // Issued by inline asm (M0 saved and restored, as the compiler reserves it):
 // the builtin form made the compiler's wait-count pass wait for the DMA at
 // the next reuse of its address registers, i.e. right after issuing it.  The
@@ -276,26 +276,36 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
   // ---- D keys, continued sums: thread t owns slots 4t..4t+3
   const uint32_t s0 = 4u * (uint32_t)tid;
   const uint32_t* Bg = T.bt;
-  // full tiles: D (and a plan's resident bucket table) by LDS-DMA, issued
+  // full tiles: D by LDS-DMA, issued
   // before the push tables are waited for and left in flight across barrier
   // (1) and the element loads, so D's HBM trip overlaps theirs (through
   // registers, D had to land before barrier (1), and the element loads went
   // out only after it: r05 phase clocks, profiles/r05_phases_cfg2.txt)
-  const bool dma = PSG_DDMA && nt == (uint32_t)kTS && ((uintptr_t)Dg & 15u) == 0u &&
-                   ((uintptr_t)Bg & 15u) == 0u;
+  const bool dma = PSG_DDMA && nt == (uint32_t)kTS && ((uintptr_t)Dg & 15u) == 0u;
   auto issue_dma = [&]() {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {  // kTS / 2 16-B units: 2 wave instructions per wave
       const uint32_t c = 2u * w + (uint32_t)j;
       dma16(Dg + 128u * c + 2u * (uint32_t)lane, (char*)dk + 1024u * c);
     }
-    static_assert(kNB / 512 <= kNW, "one 1-KB unit of the bucket table per wave at most");
-    if (Bg && w < (uint32_t)kNB / 512u)
-      dma16((const char*)Bg + 1024u * w + 16u * (uint32_t)lane, (char*)bt32 + 1024u * w);
   };
-  if (dma && w != 0) issue_dma();
-  if (np) load_tables(0);
-  if (dma && w == 0) issue_dma();  // after wave 0's table loads: its wait for them does not wait for D
+  // a plan's resident index (4 bits per bucket, psg_device.h): the last wave
+  // loads the tile's kNB / 2 bytes and turns them into the bucket starts
+  // beside wave 0's push tables, and issues its part of D once the words
+  // have landed, as wave 0 does after its table loads (issued before, the
+  // wait for the words would wait for D as well: the compiler does not see
+  // the LDS-DMA).  Decoded by wave 0 after its tables, the scan sat on every
+  // wave's way to barrier (1): cfg3 +1.3 % (profiles/index4_ab_index_cuts.txt)
+  constexpr uint32_t kIxWave = (uint32_t)kNW - 1u;
+  if (dma && w != 0 && w != kIxWave) issue_dma();
+  if (w == kIxWave) {
+    if (Bg) dev::bucket_index_decode<kNB>(dev::bucket_index_load<kNB>(Bg, lane), bt32, nt, lane);
+    if (dma) issue_dma();
+  }
+  if (w == 0) {
+    if (np) load_tables(0);
+    if (dma) issue_dma();  // after wave 0's table loads: its wait for them does not wait for D
+  }
   // through registers (partial or unaligned tiles): loaded and installed
   // on this branch only, so no load of it is pending where the LDS-DMA
   // path rejoins (a pending one would make the compiler wait for all, D's
@@ -313,15 +323,8 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
 #pragma unroll
       for (int j = 0; j < 4; ++j) d[j] = s0 + j < nt ? G(Dg)[s0 + j] : ~0ull;
     }
-    // the resident bucket table (plans): kBPT u16 entries per thread
-    u32x2 btw = {0u, 0u};
-    if (Bg) btw = __builtin_nontemporal_load((const AS1 u32x2*)Bg + tid);
 #pragma unroll
     for (int j = 0; j < 4; ++j) dk[s0 + j] = d[j];
-    if (Bg) {
-      bt32[tid * (kBPT / 2)] = btw.x;
-      bt32[tid * (kBPT / 2) + 1] = btw.y;
-    }
     // drained here, explicitly: the compiler's merge of this branch's wait
     // state into the LDS-DMA path otherwise left a vmcnt(0) on that path
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
@@ -362,16 +365,14 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
     cnt32[2 * tid + 1] = 0u;
   }
   if (tid < 4) dk[kTS + tid] = ~0ull;
-  if (Bg) {  // resident table: installed above or by the LDS-DMA
-    if (tid == 0) bt[kNB] = (uint16_t)nt;  // past its kNB entries
-  } else {
+  if (!Bg) {  // (a resident index: the last wave wrote the table, or zeros for a marked tile)
     uint32_t z = 0;  // zero
 #pragma unroll
     for (int i = 0; i < kBPT / 2; ++i) bt32[tid * (kBPT / 2) + i] = z;
   }
   if (tid == 0) pcarry = -1;
   if (dma)
-    lds_barrier();  // (1) tables, sums, counts (D and the bucket table still in flight)
+    lds_barrier();  // (1) tables, bucket starts, sums, counts (D still in flight)
   else
     __syncthreads();  // (1) tables, D, cleared histogram (or the resident bucket table)
   PH(0);
@@ -437,7 +438,7 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
     }
   };
   if (U) load_pass();
-  if (dma) {  // (1b) D and the bucket table landed (with the element loads)
+  if (dma) {  // (1b) D landed (with the element loads)
     dma_wait();
     __syncthreads();
   }
@@ -469,7 +470,7 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
   // (skipped when the plan's resident index supplied it).  D keys back from
   // LDS: the registers that held them are free during the pass's element
   // loads (8 waves/SIMD leave 64 VGPRs)
-  if (!Bg) {
+  if (!Bg || dev::bucket_index_marked<kNB>(bt32)) {
   const u64x2 y0 = *(const u64x2*)&dk[s0];
   const u64x2 y1 = *(const u64x2*)&dk[s0 + 2];
   const uint64_t dd[4] = {y0.x, y0.y, y1.x, y1.y};
@@ -751,24 +752,23 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
 
 // The bucket table of every tile, from D alone (a plan's resident index,
 // built once at plan creation: the plan contract fixes D for its
-// lifetime).  Exactly the tile kernel's histogram + scan with the same
-// bucket map, written out as the kNB u16 bucket starts of each tile.
+// lifetime).  Exactly the tile kernel's histogram with the same bucket map,
+// written out as 4 bits per bucket (the format: psg_device.h); *nmarked
+// counts the tiles whose table is not stored.
 template <int kTSl>
 __global__ __launch_bounds__(kTSl / 4) void bucket_index_kernel(
-    const TileDesc* __restrict__ tiles, uint32_t ntiles, uint32_t* __restrict__ out) {
+    const TileDesc* __restrict__ tiles, uint32_t ntiles, uint32_t* __restrict__ out,
+    unsigned long long* __restrict__ nmarked) {
   constexpr int kNT = kTSl / 4;
-  constexpr int kNW = kNT / 64;
   constexpr int kNB = kTSl;  // one bucket per slot (every kernel's map)
   constexpr int kBPT = kNB / kNT;
   __shared__ __attribute__((aligned(16))) uint32_t bt32[(kNB + 8) / 2];
-  __shared__ uint32_t wsum[kNW];
   const uint32_t ti = blockIdx.x;
   if (ti >= ntiles) return;
   const TileDesc& T = tiles[ti];
   const uint32_t nt = T.nt;
   const uint64_t* Dg = T.dk;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const uint32_t w = uni((uint32_t)tid >> 6);
+  const int tid = threadIdx.x;
   const uint32_t s0 = 4u * (uint32_t)tid;
   const uint64_t klo = G(Dg)[0];
   const uint64_t khi = G(Dg)[nt - 1];
@@ -789,30 +789,24 @@ __global__ __launch_bounds__(kTSl / 4) void bucket_index_kernel(
                              __HIP_MEMORY_SCOPE_WORKGROUP);
     }
   __syncthreads();
-  uint32_t e[kBPT];
+  // this thread's kBPT = 4 counts as nibbles: one u16 of the tile's kNB / 2 bytes
+  static_assert(kBPT == 4, "one u16 of nibbles per thread");
+  uint32_t nib = 0;
+  bool big = false;
 #pragma unroll
   for (int i = 0; i < kBPT / 2; ++i) {
     const uint32_t h = bt32[tid * (kBPT / 2) + i];
-    e[2 * i] = h & 0xffffu;
-    e[2 * i + 1] = h >> 16;
+    const uint32_t c0 = h & 0xffffu, c1 = h >> 16;
+    big |= c0 > 14u || c1 > 14u;
+    nib |= ((c0 < 14u ? c0 : 14u) | (c1 < 14u ? c1 : 14u) << 4) << (8 * i);
   }
-  uint32_t tot = 0;
-#pragma unroll
-  for (int j = 0; j < kBPT; ++j) {
-    const uint32_t c = e[j];
-    e[j] = tot;
-    tot += c;
-  }
-  const uint32_t x = wave_scan_incl(tot);
-  if (lane == 63) wsum[w] = x;
-  __syncthreads();
-  uint32_t off = x - tot;
-#pragma unroll
-  for (uint32_t v = 0; v < (uint32_t)kNW - 1u; ++v) off += v < w ? wsum[v] : 0u;
-  uint32_t* o = out + (size_t)ti * (kNB / 2);
-#pragma unroll
-  for (int i = 0; i < kBPT / 2; ++i)
-    o[tid * (kBPT / 2) + i] = (e[2 * i] + off) | (e[2 * i + 1] + off) << 16;
+  // a bucket of more than 14 keys: the tile is marked (its first word all
+  // ones; no count is 15) and the kernels build its table themselves
+  const bool marked = __syncthreads_or(big) != 0;
+  if (marked && tid < 2) nib = 0xffffu;
+  ((uint16_t*)(out + (size_t)ti * (kNB / 8)))[tid] = (uint16_t)nib;
+  if (marked && tid == 0)
+    __hip_atomic_fetch_add(GW(nmarked), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 #ifndef PSG_PAD_LDS
@@ -849,23 +843,24 @@ extern "C" int psg_debug_phases(uint32_t* out, uint32_t ntiles) {
 }
 #endif
 
-uint32_t bucket_index_words(uint32_t tile_slots) { return tile_slots / 2u; }
+uint32_t bucket_index_words(uint32_t tile_slots) { return tile_slots / 8u; }
 
 hipError_t launch_bucket_index(const TileDesc* d_tiles, uint32_t ntiles, uint32_t tile_slots,
-                               uint32_t* out, hipStream_t stream) {
+                               uint32_t* out, unsigned long long* nmarked,
+                               hipStream_t stream) {
   if (ntiles == 0) return hipSuccess;
   switch (tile_slots) {
     case 1024:
       hipLaunchKernelGGL(bucket_index_kernel<1024>, dim3(ntiles), dim3(256), 0, stream, d_tiles,
-                         ntiles, out);
+                         ntiles, out, nmarked);
       break;
     case 2048:
       hipLaunchKernelGGL(bucket_index_kernel<2048>, dim3(ntiles), dim3(512), 0, stream, d_tiles,
-                         ntiles, out);
+                         ntiles, out, nmarked);
       break;
     case 4096:
       hipLaunchKernelGGL(bucket_index_kernel<4096>, dim3(ntiles), dim3(1024), 0, stream, d_tiles,
-                         ntiles, out);
+                         ntiles, out, nmarked);
       break;
     default:
       return hipErrorInvalidValue;

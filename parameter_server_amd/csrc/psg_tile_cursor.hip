@@ -249,8 +249,10 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void cursor_kernel(
             d[j] = s0 + j < nt ? G(Dg)[s0 + j] : o;
           }
         }
-        const u32x2 btw =
-            __builtin_nontemporal_load((const AS1 u32x2*)(J.bt + (size_t)t * (kNB / 2)) + tid);
+        // the resident index (psg_device.h), decoded by wave 0 below (plain: this
+        // opt-in form is not tuned)
+        dev::BucketIndexWords<kNB> ix;
+        if (w == 0) ix = dev::bucket_index_load<kNB>(J.bt + (size_t)t * (kNB / 8), lane);
         V a0[M][4];
 #pragma unroll
         for (int mi = 0; mi < M; ++mi)
@@ -271,9 +273,41 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void cursor_kernel(
           *(u32x4*)&cnt[s0] = u32x4{z, z, z, z};
           if (tid < 4) dk[kTS + tid] = (uint64_t)o << 32 | o;
         }
-        *(u32x2*)&bt32[2 * tid] = btw;
-        if (tid == 0) bt[kNB] = (uint16_t)nt;
+        if (w == 0) dev::bucket_index_decode<kNB>(ix, bt32, nt, lane);
         __syncthreads();  // (A) the tile's tables
+        if (dev::bucket_index_marked<kNB>(bt32)) {
+          // a marked tile: the table from D, as the tile kernel builds it
+          // (histogram in the zeroed table, scan)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (s0 + j < nt) {
+              const uint32_t b = bucket(dk[s0 + j]);
+              __hip_atomic_fetch_add(&bt32[b >> 1], 1u << (16 * (b & 1u)), __ATOMIC_RELAXED,
+                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+          __syncthreads();
+          const u32x2 h = *(const u32x2*)&bt32[2 * tid];
+          uint32_t e[4] = {h.x & 0xffffu, h.x >> 16, h.y & 0xffffu, h.y >> 16};
+          uint32_t tot = 0;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const uint32_t c = e[j];
+            e[j] = tot;
+            tot += c;
+          }
+          uint32_t* const wsum = cnt;  // zeroed again below
+          const uint32_t x = dev::wave_scan_incl_dpp(tot);
+          if (lane == 63) wsum[w] = x;
+          __syncthreads();
+          uint32_t off = x - tot;
+#pragma unroll
+          for (uint32_t v = 0; v < (uint32_t)kNW - 1u; ++v) off += v < w ? wsum[v] : 0u;
+          __syncthreads();
+          if (tid < kNW) wsum[tid] = 0u;
+          *(u32x2*)&bt32[2 * tid] =
+              u32x2{(e[0] + off) | (e[1] + off) << 16, (e[2] + off) | (e[3] + off) << 16};
+          __syncthreads();
+        }
       }
 
       // ---- piece bounds: the first key of a round that is past the push or

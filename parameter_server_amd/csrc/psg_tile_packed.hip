@@ -111,7 +111,7 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
 }
 
 #ifndef PSG_DDMA
-#define PSG_DDMA 1  // A/B builds: 0 = D and the resident bucket table through registers
+#define PSG_DDMA 1  // A/B builds: 0 = D through registers
 #endif
 // 16 B per lane from global memory straight into LDS (gfx950 LDS-DMA), as
 // in psg_tile.hip: inline asm (the builtin made the compiler wait for it at
@@ -496,26 +496,29 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
   };
   // ---- D keys, continued sums: thread t owns slots 4t..4t+3
   const uint32_t s0i = 4u * (uint32_t)tid;
-  // the plan's resident bucket table (psg_tile.hip bucket_index_kernel<64>:
-  // the same 2048 buckets over the same tile)
+  // the plan's resident bucket index (psg_tile.hip bucket_index_kernel: the
+  // same buckets over the same tile), decoded by wave 2 (psg_device.h)
   const uint32_t* Bg = T.bt;
-  // full tiles of the partition form: D and the resident bucket table by
+  // full tiles of the partition form: D by
   // LDS-DMA, left in flight across barriers (1) and (1b) and the element
   // loads (through registers, D had to land before (1) and the element
   // loads went out after it; psg_tile.hip, profiles/r05_phases_cfg2.txt)
-  const bool dma = !CUR && PSG_DDMA && nt == (uint32_t)kTS && ((uintptr_t)Dg & 15u) == 0u &&
-                   ((uintptr_t)Bg & 15u) == 0u;
+  const bool dma = !CUR && PSG_DDMA && nt == (uint32_t)kTS && ((uintptr_t)Dg & 15u) == 0u;
   auto issue_dma = [&]() {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {  // kTS / 2 16-B units: 2 wave instructions per wave
       const uint32_t c = 2u * w + (uint32_t)j;
       dma16(Dg + 128u * c + 2u * (uint32_t)lane, (char*)dk + 1024u * c);
     }
-    static_assert(kNB / 512 <= kNW, "one 1-KB unit of the bucket table per wave at most");
-    if (Bg && w < (uint32_t)kNB / 512u)
-      dma16((const char*)Bg + 1024u * w + 16u * (uint32_t)lane, (char*)bt32 + 1024u * w);
   };
-  if (dma && w >= 2) issue_dma();
+  if (dma && w > 2) issue_dma();
+  // wave 2 (no tables to load) decodes the index, and issues its part of D
+  // after the words have landed, as waves 0-1 do after their table loads:
+  // issued before, the wait for the words would wait for D as well
+  if (w == 2) {
+    if (Bg) dev::bucket_index_decode<kNB>(dev::bucket_index_load<kNB>(Bg, lane), bt32, nt, lane);
+    if (dma) issue_dma();
+  }
   if (np) {
     if constexpr (!CUR) tables_a(0);
   }
@@ -533,11 +536,8 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j) d[j] = s0i + j < nt ? G(Dg)[s0i + j] : ~0ull;
     }
-    u32x2 btw = {0u, 0u};
-    if (Bg) btw = __builtin_nontemporal_load((const AS1 u32x2*)Bg + tid);
 #pragma unroll
     for (int j = 0; j < 4; ++j) dk[s0i + j] = d[j];
-    if (Bg) *(u32x2*)&bt[tid * kBPT] = btw;
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
   }
   // cursor form: the pieces, while D and the index are in flight
@@ -576,12 +576,13 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
   {
     uint32_t z = 0;  // opaque zero: not a hoisted (and spilled) constant vector
     asm volatile("" : "+v"(z));
-    if (!Bg) *(u32x2*)&bt[tid * kBPT] = u32x2{z, z};  // a cleared histogram
-    if (Bg && tid == 0) bt[kNB] = (uint16_t)nt;  // past the table's kNB entries
+    // a cleared histogram (a resident index: wave 0 wrote the table, or
+    // zeros for a marked tile)
+    if (!Bg) *(u32x2*)&bt[tid * kBPT] = u32x2{z, z};
   }
   if (tid == 0) pcarry = (int)ones;
   if (dma)
-    lds_barrier();  // (1) pieces scanned, sums (D and the bucket table in flight)
+    lds_barrier();  // (1) pieces scanned, bucket starts, sums (D in flight)
   else
     __syncthreads();  // (1) pieces scanned, D, cleared histogram (or the resident bucket table)
   if (np) {
@@ -646,7 +647,7 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
     }
   };
   if (U) load_pass();
-  if (dma) {  // (1c) D and the bucket table landed (with the element loads)
+  if (dma) {  // (1c) D landed (with the element loads)
     dma_wait();
     __syncthreads();
   }
@@ -715,7 +716,7 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
     }
     __syncthreads();  // (4)
   };
-  if (!Bg) build_bt(false);
+  if (!Bg || dev::bucket_index_marked<kNB>(bt32)) build_bt(false);
 
   for (;;) {
     if (!U) {  // this group of pushes has no keys in the tile, or is done
@@ -936,9 +937,11 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
     // the bucket table back from the resident index when another pass or
     // group searches it (its first half held the collision bitmaps)
     if (done + kNW * Rw < U || g0 + gp < np) {
-      if (Bg) {
-        const uint32_t t = 64u * w + lane_id();
-        *(u32x2*)&bt[t * kBPT] = __builtin_nontemporal_load((const AS1 u32x2*)Bg + t);
+      if (Bg && !dev::bucket_index_marked<kNB>(bt32)) {  // (the flag lies past the bitmaps)
+        if (w == 2) {
+          const int l = (int)lane_id();
+          dev::bucket_index_decode<kNB>(dev::bucket_index_load<kNB>(Bg, l), bt32, nt, l);
+        }
         __syncthreads();
       } else {
         build_bt(true);

@@ -248,6 +248,9 @@ class MergePlan:
         f = C.c_int()
         _lib.check(self._L.psg_plan_form(h, C.byref(f)))
         self.form = f.value  # _lib.PSG_KERNEL_*
+        ib, mt = C.c_uint64(), C.c_uint64()
+        _lib.check(self._L.psg_plan_index_info(h, C.byref(ib), C.byref(mt)))
+        self.index_bytes, self.marked_tiles = ib.value, mt.value
 
     def run(self, stream: Optional[int] = None) -> None:
         _lib.check(self._L.psg_plan_run(self._h, stream or None))
