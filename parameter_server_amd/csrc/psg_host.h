@@ -1,6 +1,7 @@
 // psg_host.h -- host-side helpers shared by the C-ABI translation units
-// (psg_runtime.hip, psg_exchange.hip): the thread-local last-error text
-// behind psg_last_error() and the HIP error check.
+// (psg_runtime.hip and the others that share psg_ctx.h, psg_jobtable.hip,
+// psg_jobimage.cc, psg_exchange.hip): the thread-local last-error text behind
+// psg_last_error() (psg_runtime.hip) and the HIP error check.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,5 +1,6 @@
 // psg_internal.h -- shared between the gfx950 kernels and the host runtime
-// behind the C ABI (psg_runtime.hip).  Not installed.
+// behind the C ABI (psg_ctx.h and the translation units it names).  Not
+// installed.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -237,7 +237,7 @@ __device__ __forceinline__ void stream_item(const JobDev& J, uint32_t p, uint32_
   // inside its piece, and a piece whose bounds run backwards is an
   // overflow -- so the push's fail counter is only reset here, by its
   // first chunk, ahead of the aggregate launch that adds to it (plans then
-  // need no per-run splitter pass, psg_runtime.hip run_stage)
+  // need no per-run splitter pass, psg_jobtable.hip run_stage)
   if (c == 0 && lane == 0) J.fail[p] = 0ull;
 }
 

@@ -349,7 +349,7 @@ def test_against_the_recorded_reference_model(pinned_case, tmp_path, pname, mode
     P, c, fixtures = pinned_case
     meta, fx = fixtures[pname]
     if mode == "no_rehash":
-        # the table's arithmetic (psg_runtime.hip buckets_for): the smallest
+        # the table's arithmetic (psg_ctx.h buckets_for): the smallest
         # power of two whose 3 * nb / 2 slots hold the hint, and no growth while
         # every key pushed so far fits
         nb = 1
