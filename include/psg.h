@@ -208,6 +208,65 @@ int psg_gather(psg_ctx* ctx, int chl, const uint64_t* keys, size_t n,
                void* out, size_t* matched);
 
 /* ------------------------------------------------------------------ */
+/* Device-array forms of the server context: push and pull for        */
+/* producers and consumers whose arrays are already in HBM            */
+/* (psg_mb_darling_gradients / _update_dual, psg_exchange_recv).      */
+/* ------------------------------------------------------------------ */
+/* Ordering rule of every device form of the context (here and
+ * psg_darling_update_dev below): operations on one channel's values and on
+ * one aggregate apply in CALL order, whatever streams they are given.  A pull
+ * sees every update called before it; an update waits for every pull called
+ * before it; pushes of one time fold in call order, host and device pushes
+ * alike.  The order is kept with events between the streams: no caller's
+ * stream is ever made to wait on the host.  stream == NULL is the device's
+ * default stream, as for psg_ftrl_*_dev.
+ *
+ * Deferred errors: what a device form finds out only on the device -- an
+ * update skipped because a push of its block did not match
+ * (PSG_ERR_UNMATCHED), a pull request that was not sorted (PSG_ERR_UNSORTED)
+ * -- is reported once by the next psg_dev_status or psg_darling_progress,
+ * and then cleared; later operations apply normally.  If both kinds are
+ * pending, PSG_ERR_UNMATCHED is the one returned and both are cleared. */
+
+/* setValue of a value message (kv_vector.h:75-204), exactly as psg_push, for
+ * keys_dev[n] and vals_dev[i][n] (the HOST array of m pointers) in the memory
+ * of the context's device, produced by work enqueued on `stream`.  The
+ * context takes its own copy by one launch enqueued on `stream` before the
+ * call returns: the caller may overwrite its arrays with work enqueued on
+ * `stream` afterwards.  Arrays need only element alignment.  No host wait,
+ * and no allocation once the pool has seen the shape.  Unchanged from
+ * psg_push: n == 0 is ignored; the errors psg_push finds before it stages
+ * anything are immediate (PSG_ERR_EMPTY_KEYS, the pigeonhole
+ * PSG_ERR_UNMATCHED, PSG_ERR_RANGE, PSG_ERR_CHANNEL, bad m); m may differ
+ * between pushes of one time; host and device pushes may share an aggregate;
+ * unmatched, unsorted or duplicated keys are reported by psg_received(time)
+ * as PSG_ERR_UNMATCHED.
+ * The host cannot read the keys, so psg_push's test for a contiguous slice
+ * of the server keys is replaced by `slice`: PSG_NO_SLICE takes the searching
+ * path (the match of kv_vector.h:84-137,171-204); any other value
+ * is the caller's claim that the keys are exactly the server keys D[slice,
+ * slice + n) (absolute positions), which leads to the dense kernel.  The
+ * claim is checked on the device: every keys_dev[i] != D[slice + i] counts as
+ * an unmatched key of the aggregate, so a false claim is PSG_ERR_UNMATCHED at
+ * psg_received and skips psg_darling_update(_dev).  A claim outside the
+ * positions of [kb, ke) is PSG_ERR_ARG at once. */
+#define PSG_NO_SLICE ((size_t)-1)
+int psg_push_dev(psg_ctx* ctx, int chl, int time, uint64_t kb, uint64_t ke,
+                 const uint64_t* keys_dev, size_t n, int m, const void* const* vals_dev,
+                 size_t slice, void* stream);
+/* getValue(msg) (kv_vector.h:206-227), as psg_gather, in one launch on
+ * `stream`: out_dev[i] = value(chl) at keys_dev[i], +0 where it is not a
+ * server key (or repeats the key before it); *matched_dev (nullable) is set
+ * to the matched count.  n == 0 is a no-op.  PSG_ERR_SIZE at once when the
+ * channel's key and value counts differ (kv_vector.h:220); a request that is
+ * not sorted (repeats are legal) is a deferred PSG_ERR_UNSORTED. */
+int psg_pull_dev(psg_ctx* ctx, int chl, const uint64_t* keys_dev, size_t n, void* out_dev,
+                 unsigned long long* matched_dev, void* stream);
+/* Synchronises the context's streams and every channel's last device
+ * operation, and returns the deferred error (above) or PSG_OK. */
+int psg_dev_status(psg_ctx* ctx);
+
+/* ------------------------------------------------------------------ */
 /* Device-resident batched merge: the hot path with every buffer      */
 /* already in HBM (benchmarks, multi-GPU shards, graph capture).      */
 /* ------------------------------------------------------------------ */
@@ -413,6 +472,29 @@ int psg_darling_reset_active(psg_ctx* ctx, int chl);
  * model untouched. */
 int psg_darling_update(psg_ctx* ctx, int chl, int time, const psg_darling_param* p,
                        double* violation);
+/* The same step (darling.cc:251-262, updateWeight :437-477) with no host
+ * wait: the same argument checks, fold and kernel, and the aggregate of
+ * `time` is erased.  The block's violation is max-accumulated into a device
+ * word of the channel -- violation_ = std::max(violation_, vio) across
+ * blocks, darling.cc:466 -- which psg_darling_progress reads.  A block whose
+ * pushes did not all match leaves the model untouched and sets the deferred
+ * PSG_ERR_UNMATCHED (see "Deferred errors" at psg_push_dev; the ordering rule
+ * stated there holds here). */
+int psg_darling_update_dev(psg_ctx* ctx, int chl, int time, const psg_darling_param* p);
+/* The server branch of Darling::evaluateProgress (darling.cc:538-555) for one
+ * channel: *nnz_w = the weights that are neither inactive nor zero, *objv =
+ * lambda * sum |w| over them, *violation = the word psg_darling_update_dev
+ * accumulates (reset_violation != 0 zeroes it after reading: violation_ = 0,
+ * darling.cc:163-166), *nnz_active = active_set.nnz().  Any output may be
+ * NULL.  Synchronises, and reports and clears the deferred error like
+ * psg_dev_status.  Needs psg_darling_init.  inactive(w) is w != w
+ * (darling.h): every NaN is inactive, whatever its bits; -0.0 is zero.
+ * Defined deviation: sum |w| is not the serial chain of darling.cc:543-547
+ * but a fixed-order device reduction (a tree over each 256 weights, then
+ * over those sums): the same bits on every run of the same values, within
+ * n * 2^-53 * (the exact sum) of it; nnz_w and nnz_active are exact. */
+int psg_darling_progress(psg_ctx* ctx, int chl, double lambda, int reset_violation,
+                         size_t* nnz_w, double* objv, double* violation, size_t* nnz_active);
 /* Copies of delta[off, off+n) and the active bits (one byte each, 0/1);
  * *nnz_active = active_set.nnz() (darling.cc:549).  Any output may be NULL. */
 int psg_darling_state(psg_ctx* ctx, int chl, size_t off, size_t n, double* delta,

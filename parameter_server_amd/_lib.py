@@ -35,6 +35,7 @@ PSG_KC_SIG = 1
 PSG_KC_KEYS = 2
 PSG_KC_ERASE = 4
 PSG_MAX_SIG_LEN = 2048
+PSG_NO_SLICE = (1 << 64) - 1  # (size_t)-1: psg_push_dev without a slice claim
 
 PSG_F32 = 0
 PSG_F64 = 1
@@ -135,6 +136,10 @@ SIGNATURES = {
     "psg_received_shape": (C.c_int, [_p, C.c_int, C.POINTER(C.c_int), _psz, _psz]),
     "psg_received": (C.c_int, [_p, C.c_int, C.c_int, C.POINTER(_p)]),
     "psg_gather": (C.c_int, [_p, C.c_int, _p, _sz, _p, _psz]),
+    "psg_push_dev": (C.c_int, [_p, C.c_int, C.c_int, _u64, _u64, _p, _sz, C.c_int,
+                               C.POINTER(_p), _sz, _p]),
+    "psg_pull_dev": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p]),
+    "psg_dev_status": (C.c_int, [_p]),
     "psg_plan_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint,
                                   C.POINTER(MergeJob), C.c_int, C.POINTER(_p)]),
     "psg_plan_max_push": (C.c_int, []),
@@ -189,6 +194,9 @@ SIGNATURES = {
     "psg_darling_init": (C.c_int, [_p, C.c_int, C.c_double]),
     "psg_darling_reset_active": (C.c_int, [_p, C.c_int]),
     "psg_darling_update": (C.c_int, [_p, C.c_int, C.c_int, _p, C.POINTER(C.c_double)]),
+    "psg_darling_update_dev": (C.c_int, [_p, C.c_int, C.c_int, _p]),
+    "psg_darling_progress": (C.c_int, [_p, C.c_int, C.c_double, C.c_int, _psz,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double), _psz]),
     "psg_darling_state": (C.c_int, [_p, C.c_int, _sz, _sz, _p, _p, _psz]),
     "psg_ftrl_init": (C.c_int, [_p, _p, _sz]),
     "psg_ftrl_reserve": (C.c_int, [_p, _sz]),

@@ -1,13 +1,16 @@
 // psg_ctx.h -- the server context behind the C ABI (include/psg.h), shared by
 // the translation units that implement it: psg_runtime.hip (the context
 // core), psg_ctx_freq.hip (frequency filter), psg_ctx_ftrl.hip (FTRL model),
-// psg_plan.hip (plans and the stateless device helpers).  Not installed.
+// psg_ctx_dev.hip (device-array forms), psg_plan.hip (plans and the stateless
+// device helpers).  Not installed.
 //
 // psg_ctx mirrors KVVector<uint64,V> (src/parameter/kv_vector.h:13-62): per
 // channel sorted server keys key_[chl] and values val_[chl], and per time t
 // the aggregate recved_val_[t].  Keys/values/aggregates live in the HBM of
 // one device; a host mirror of key_[chl] serves findRange without a device
-// round trip.  All device work is ordered on one HIP stream per context;
+// round trip.  All device work is ordered on one HIP stream per context (the
+// device-array forms run on their callers' streams and are tied to it by
+// events, psg_ctx_dev.hip);
 // a mutex gives the reference's threading contract (setValue on the
 // executor thread, received() from the app thread, kv_vector.h:45,67).
 #pragma once
@@ -78,7 +81,17 @@ struct Channel {
   double* d_delta = nullptr;
   uint32_t* d_active = nullptr;
   size_t dn = 0;
+  // device forms (psg_ctx_dev.hip).  d_dev: kChanWordBytes of device words,
+  // [0] the violation accumulated by psg_darling_update_dev, [1..2] the pull
+  // kernel's count and ticket.  last / last_s: like a Filter's -- operations
+  // on the channel's values run in call order whatever streams they are
+  // enqueued on; each waits for the event recorded after the previous one
+  // when their streams differ.
+  unsigned long long* d_dev = nullptr;
+  hipEvent_t last = nullptr;
+  hipStream_t last_s = nullptr;
 };
+constexpr size_t kChanWordBytes = 64;
 
 struct PendingPush {
   KeyRef keys;
@@ -553,11 +566,13 @@ struct psg_ctx {
     return PSG_OK;
   }
 
-  int new_keys(size_t n, KeyRef* out) {
+  int new_keys(size_t n, KeyRef* out) { return new_keys(n, out, copy); }
+  // `writer`: the stream the keys are written on
+  int new_keys(size_t n, KeyRef* out, hipStream_t writer) {
     KeyBuf* k = new KeyBuf();
     k->n = n;
     k->bytes = 8 * n;
-    if (int rc = dev_get(k->bytes, (void**)&k->d, copy)) {
+    if (int rc = dev_get(k->bytes, (void**)&k->d, writer)) {
       delete k;
       return rc;
     }
@@ -686,6 +701,19 @@ struct psg_ctx {
     return PSG_OK;
   }
 
+  // a channel's values in call order across streams (Channel::last)
+  int chan_order(Channel& C, hipStream_t s) {
+    if (C.last && C.last_s != s) HIP_TRY(hipStreamWaitEvent(s, C.last, 0));
+    return PSG_OK;
+  }
+  int chan_mark(Channel& C, hipStream_t s) {
+    if (!C.last)
+      if (int rc = event(&C.last)) return rc;
+    HIP_TRY(hipEventRecord(C.last, s));
+    C.last_s = s;
+    return PSG_OK;
+  }
+
   int ensure_scratch(size_t b) {
     if (b <= scratch_bytes) return PSG_OK;
     HIP_TRY(hipStreamSynchronize(stream));
@@ -793,6 +821,10 @@ struct psg_ctx {
                   const void* const* vals, void* vblock = nullptr,
                   const size_t* slice = nullptr, void* sblock = nullptr, size_t sbytes = 0,
                   const PendingPush* comp = nullptr);
+  // findRange of a push and the consistency checks of setValue, before any
+  // data is staged
+  int check_push(int chl, int time, uint64_t kb, uint64_t ke, size_t n, int m, size_t* lo,
+                 size_t* hi);
   int decode_pending(Aggregate& a, size_t take, void** blk, size_t* bytes);
   // the aggregate of `time` (created on first use) over [kb, ke) of chl
   int aggregate_for(int chl, int time, uint64_t kb, uint64_t ke, int m, Aggregate** out);

@@ -134,6 +134,28 @@ __global__ __launch_bounds__(kVioSlots) void darling_vio_kernel(unsigned long lo
   }
 }
 
+// psg_darling_update_dev's form: the slots' max folded into the channel's
+// violation word, violation_ = std::max(violation_, vio) across blocks
+// (darling.cc:466); nothing reads it back per block.  A block darling_kernel
+// skipped (*bad != 0) counts once in *skipped, the context's deferred error.
+__global__ __launch_bounds__(kVioSlots) void darling_vio_acc_kernel(
+    unsigned long long* __restrict__ slots, unsigned long long* __restrict__ word,
+    const unsigned long long* __restrict__ bad, unsigned long long* __restrict__ skipped) {
+  unsigned long long vb = slots[threadIdx.x * 8];
+  slots[threadIdx.x * 8] = 0;
+  vb = wave_max(vb);
+  __shared__ unsigned long long wmax[kVioSlots / 64];
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = vb;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < kVioSlots / 64; ++i) vb = wmax[i] > vb ? wmax[i] : vb;
+    // the channel's updates run one after another: a plain read-modify-write
+    if (vb > *word) *word = vb;
+    if (*bad)
+      __hip_atomic_fetch_add(skipped, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 __global__ __launch_bounds__(256) void bitmap_fill_kernel(uint32_t* __restrict__ a, uint64_t nbits) {
   const uint64_t wi = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   const uint64_t nw = (nbits + 31) >> 5;
@@ -168,6 +190,22 @@ hipError_t launch_darling(const double* G, const double* U, double* w, double* d
   hipLaunchKernelGGL(darling_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, G, U, w, delta,
                      active, lo, n, P, bad, slots);
   hipLaunchKernelGGL(darling_vio_kernel, dim3(1), dim3(kVioSlots), 0, s, slots, vio);
+  return hipGetLastError();
+}
+
+hipError_t launch_darling_dev(const double* G, const double* U, double* w, double* delta,
+                              uint32_t* active, uint64_t lo, uint64_t n, const DarlingParam& P,
+                              const unsigned long long* bad, unsigned long long* slots,
+                              unsigned long long* word, unsigned long long* skipped,
+                              hipStream_t s) {
+  if (n) {
+    const uint64_t span = lo + n - (lo & ~31ull);
+    const uint64_t blocks = (span + 255) / 256;
+    hipLaunchKernelGGL(darling_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, G, U, w, delta,
+                       active, lo, n, P, bad, slots);
+  }
+  hipLaunchKernelGGL(darling_vio_acc_kernel, dim3(1), dim3(kVioSlots), 0, s, slots, word, bad,
+                     skipped);
   return hipGetLastError();
 }
 

@@ -143,6 +143,20 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum,
   return (w > 0 ? wsum[w - 1] : 0u) + x - v;
 }
 
+// The fixed-order sum every device objv is built on (psg_mb_gradient,
+// psg_mb_darling_objv, psg_darling_progress): the tree sum of a 256-thread
+// workgroup's values v, over s (256 doubles of LDS); s[0] on return, for
+// thread 0 to read.  The result's bits depend on this order: change it for
+// all callers or for none.
+__device__ __forceinline__ void block_tree_sum(double v, double* s) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
+    __syncthreads();
+  }
+}
+
 // Scale of the tile kernels' bucket map bucket(x) = umulhi(x, mul): every
 // x <= r32 (< 2^32) lands below nb.  An f32 reciprocal with a 2^-20 margin
 // (reciprocal ~2^-23, conversions and products 2^-24 each) replaces the

@@ -156,6 +156,36 @@ hipError_t launch_gather(int dtype, const uint64_t* dkeys, uint64_t nd,
                          const void* dvals, const uint64_t* req, uint64_t nreq,
                          void* out, unsigned long long* matched,
                          hipStream_t stream);
+// psg_pull_dev (psg_kernels.hip): launch_gather's results, *matched (device,
+// nullable) set to the matched count and the request's non-strict order
+// violations added to *unsorted_total, in one launch.  ctl: two zeroed device
+// words, left zero; launches sharing them must not overlap.
+hipError_t launch_pull(int dtype, const uint64_t* dkeys, uint64_t nd, const void* dvals,
+                       const uint64_t* req, uint64_t nreq, void* out, unsigned long long* matched,
+                       unsigned long long* ctl, unsigned long long* unsorted_total,
+                       hipStream_t stream);
+// Intake of one device message (psg_ctx_dev.hip): n arrays copied from the
+// caller's element-aligned arrays (esz = 4 or 8 bytes, len a multiple of it)
+// and, for a slice claim, claim_keys[i] != D[i] over nclaim keys added to *bad.
+struct IntakeArgs {
+  const void* src[kMaxM + 1];
+  void* dst[kMaxM + 1];
+  uint64_t len[kMaxM + 1];
+  uint32_t esz[kMaxM + 1];
+  uint32_t n = 0;
+  const uint64_t* claim_keys = nullptr;
+  const uint64_t* D = nullptr;
+  uint64_t nclaim = 0;
+  unsigned long long* bad = nullptr;
+};
+hipError_t launch_intake(const IntakeArgs& a, hipStream_t stream);
+// Darling::evaluateProgress's server sums over w[n] (psg_ctx_dev.hip): res[0]
+// = the count of weights that are neither NaN nor zero, res[1] = the bits of
+// sum |w| over them, a tree over each 256 weights and then over those sums
+// (psg_mb_gradient's objv shape).  partial: 2 * progress_parts(n) words.
+inline uint64_t progress_parts(uint64_t n) { return (n + 255) / 256; }
+hipError_t launch_progress(const double* w, uint64_t n, unsigned long long* partial,
+                           unsigned long long* res, hipStream_t stream);
 // keys strictly increasing?  *bad (device) += number of violations.
 // copies between pinned host memory and the device made by the GPU itself
 // (zero-copy; src/dst are device-visible addresses, 16-B aligned)
@@ -206,6 +236,14 @@ hipError_t launch_darling(const double* G, const double* U, double* w, double* d
                           uint32_t* active, uint64_t lo, uint64_t n, const DarlingParam& P,
                           const unsigned long long* bad, unsigned long long* slots,
                           unsigned long long* vio, hipStream_t stream);
+// the same update with no word to read back: the block's violation is
+// max-folded into *word (the channel's accumulated violation) and a skipped
+// block (*bad != 0) adds one to *skipped
+hipError_t launch_darling_dev(const double* G, const double* U, double* w, double* delta,
+                              uint32_t* active, uint64_t lo, uint64_t n, const DarlingParam& P,
+                              const unsigned long long* bad, unsigned long long* slots,
+                              unsigned long long* word, unsigned long long* skipped,
+                              hipStream_t stream);
 hipError_t launch_darling_init(double* delta, uint32_t* active, uint64_t n, double delta_init,
                                hipStream_t stream);
 hipError_t launch_bitmap_fill(uint32_t* active, uint64_t n, hipStream_t stream);

@@ -38,11 +38,14 @@ namespace {
 constexpr int kGR = 1024;  // requests per workgroup
 constexpr int kGS = 4096;  // server keys staged in LDS (32 KB)
 
+// One workgroup's kGR requests.  *found = this thread's matched requests,
+// *unsorted = those of its requests that are below the request before them
+// (launch_check_sorted's non-strict test: repeats are legal).
 template <typename V>
-__global__ __launch_bounds__(256) void gather_kernel(
+__device__ __forceinline__ void gather_block(
     const uint64_t* __restrict__ D, uint64_t nd, const V* __restrict__ W,
-    const uint64_t* __restrict__ req, uint64_t nreq, V* __restrict__ out,
-    unsigned long long* __restrict__ matched) {
+    const uint64_t* __restrict__ req, uint64_t nreq, V* __restrict__ out, int* found_out,
+    int* unsorted_out) {
   constexpr int kI = kGR / 256;
   __shared__ uint64_t t[kGS];
   __shared__ uint64_t rg[2];
@@ -84,6 +87,7 @@ __global__ __launch_bounds__(256) void gather_kernel(
   const uint64_t prev0 = lane > 0 ? up : (w > 0 ? wlast[w - 1] : before);
   uint64_t pos[kI];
   bool ok[kI];
+  int unsorted = 0;
 #pragma unroll
   for (int q = 0; q < kI; ++q) {
     const uint64_t i = ib + q;
@@ -99,6 +103,7 @@ __global__ __launch_bounds__(256) void gather_kernel(
     }
     const uint64_t prev = q == 0 ? prev0 : k[q > 0 ? q - 1 : 0];
     const bool rep = i > 0 && i < r1 && prev == k[q];
+    unsorted += i > 0 && i < r1 && k[q] < prev;
     ok[q] = i < r1 && hit && !rep;
     pos[q] = ok[q] ? p : 0;
   }
@@ -113,6 +118,18 @@ __global__ __launch_bounds__(256) void gather_kernel(
       found += ok[q];
     }
   }
+  *found_out = found;
+  *unsorted_out = unsorted;
+}
+
+template <typename V>
+__global__ __launch_bounds__(256) void gather_kernel(
+    const uint64_t* __restrict__ D, uint64_t nd, const V* __restrict__ W,
+    const uint64_t* __restrict__ req, uint64_t nreq, V* __restrict__ out,
+    unsigned long long* __restrict__ matched) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int found, unsorted;
+  gather_block<V>(D, nd, W, req, nreq, out, &found, &unsorted);
   // the workgroup's total, one atomic per workgroup: every wave's atomic on
   // the one counter serialised at one L2 channel (r05: 4,096 atomics took
   // most of a 1 M-request gather's 59 us)
@@ -124,6 +141,53 @@ __global__ __launch_bounds__(256) void gather_kernel(
   if (threadIdx.x == 0) {
     const int tot = wfound[0] + wfound[1] + wfound[2] + wfound[3];
     if (tot) atomicAdd(matched, (unsigned long long)tot);
+  }
+}
+
+// psg_pull_dev: the gather, the matched count and the request's order check
+// (launch_check_sorted, strict = false) in one launch, with no counter to
+// zero beforehand.  *matched (nullable) is SET: a launch of one workgroup
+// stores its count; a larger one adds the workgroups' counts into ctl[0] and
+// the workgroup that takes the last ticket of ctl[1] stores the sum and
+// leaves both words zero for the next launch (launches that share ctl run one
+// after another).  Order violations are added to *unsorted_total.
+template <typename V>
+__global__ __launch_bounds__(256) void pull_kernel(
+    const uint64_t* __restrict__ D, uint64_t nd, const V* __restrict__ W,
+    const uint64_t* __restrict__ req, uint64_t nreq, V* __restrict__ out,
+    unsigned long long* __restrict__ matched, unsigned long long* __restrict__ ctl,
+    unsigned long long* __restrict__ unsorted_total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int found, unsorted;
+  gather_block<V>(D, nd, W, req, nreq, out, &found, &unsorted);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    found += __shfl_xor(found, d, 64);
+    unsorted += __shfl_xor(unsorted, d, 64);
+  }
+  __shared__ int wsum[4][2];
+  if (lane == 0) {
+    wsum[w][0] = found;
+    wsum[w][1] = unsorted;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const unsigned long long tot = (unsigned long long)(wsum[0][0] + wsum[1][0] + wsum[2][0] + wsum[3][0]);
+  const int uns = wsum[0][1] + wsum[1][1] + wsum[2][1] + wsum[3][1];
+  if (uns)
+    __hip_atomic_fetch_add(unsorted_total, (unsigned long long)uns, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+  if (!matched) return;
+  if (gridDim.x == 1) {
+    *matched = tot;
+    return;
+  }
+  if (tot) __hip_atomic_fetch_add(ctl, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned long long ticket =
+      __hip_atomic_fetch_add(ctl + 1, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket == (unsigned long long)gridDim.x - 1) {
+    *matched = __hip_atomic_exchange(ctl, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(ctl + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -250,6 +314,22 @@ hipError_t launch_gather(int dtype, const uint64_t* dkeys, uint64_t nd,
     hipLaunchKernelGGL(gather_kernel<double>, dim3((uint32_t)blocks), dim3(256), 0,
                        stream, dkeys, nd, (const double*)dvals, req, nreq,
                        (double*)out, matched);
+  return hipGetLastError();
+}
+
+hipError_t launch_pull(int dtype, const uint64_t* dkeys, uint64_t nd, const void* dvals,
+                       const uint64_t* req, uint64_t nreq, void* out, unsigned long long* matched,
+                       unsigned long long* ctl, unsigned long long* unsorted_total,
+                       hipStream_t stream) {
+  if (nreq == 0) return hipSuccess;
+  const uint64_t blocks = (nreq + kGR - 1) / kGR;
+  if (dtype == 0)
+    hipLaunchKernelGGL(pull_kernel<float>, dim3((uint32_t)blocks), dim3(256), 0, stream, dkeys, nd,
+                       (const float*)dvals, req, nreq, (float*)out, matched, ctl, unsorted_total);
+  else
+    hipLaunchKernelGGL(pull_kernel<double>, dim3((uint32_t)blocks), dim3(256), 0, stream, dkeys,
+                       nd, (const double*)dvals, req, nreq, (double*)out, matched, ctl,
+                       unsorted_total);
   return hipGetLastError();
 }
 

@@ -71,6 +71,8 @@ int psg_create(int device, int dtype, unsigned flags, psg_ctx** out) {
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->copy_ev, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming);
   if (e == hipSuccess) e = hipMalloc((void**)&c->d_small, 256);
+  // zeroed: the deferred-error words of the device forms (psg_ctx_dev.hip)
+  if (e == hipSuccess) e = hipMemsetAsync(c->d_small, 0, 256, c->stream);
   if (e == hipSuccess) e = hipMalloc((void**)&c->d_vio_slots, 64 * psg::kVioSlots);
   if (e == hipSuccess) e = hipMemsetAsync(c->d_vio_slots, 0, 64 * psg::kVioSlots, c->stream);
   if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_small, 256);
@@ -93,6 +95,11 @@ int psg_destroy(psg_ctx* c) {
   c->agg.clear();
   c->kcache.clear();
   for (auto& kv : c->ch) {
+    if (kv.second.last) {  // the device forms' last operation, on a caller's stream
+      (void)hipEventSynchronize(kv.second.last);
+      c->free_ev.push_back(kv.second.last);
+    }
+    c->dev_put(kv.second.d_dev, kChanWordBytes);
     c->dev_put(kv.second.d_keys, kv.second.kbytes);
     c->dev_put(kv.second.d_vals, kv.second.nvals * vsize(c->dtype));
     c->dev_put(kv.second.d_delta, 8 * kv.second.dn);
@@ -180,6 +187,8 @@ int key_union_impl(psg_ctx* c, int chl, const std::vector<const uint64_t*>& d_pu
     if (kv.second.chl == chl && !kv.second.pending.empty())
       if (int rc = c->flush(kv.second)) return rc;
   if (int rc = c->join_copy()) return rc;
+  // ... and after the device pulls still reading the keys and values
+  if (int rc = c->chan_order(C, c->stream)) return rc;
   bool changed = false;
   // once a merge applied, the key set (so every position) changed: the
   // mirror is refreshed and val_[chl] cleared (kv_vector.h:180) on every
@@ -239,10 +248,13 @@ int key_union_impl(psg_ctx* c, int chl, const std::vector<const uint64_t*>& d_pu
   return settle(PSG_OK);
 }
 
+}  // namespace
+
 // findRange of a push and the consistency checks of setValue, before any
 // data is staged
-int check_push(psg_ctx* c, int chl, int time, uint64_t kb, uint64_t ke, size_t n, int m,
-               size_t* lo, size_t* hi) {
+int psg_ctx::check_push(int chl, int time, uint64_t kb, uint64_t ke, size_t n, int m,
+                        size_t* lo, size_t* hi) {
+  psg_ctx* c = this;
   if (m < 1 || m > PSG_MAX_VALUE_ARRAYS) return fail(PSG_ERR_ARG, "m=%d", m);
   if (ke < kb) return fail(PSG_ERR_ARG, "invalid key range");
   auto cit = c->ch.find(chl);
@@ -265,8 +277,6 @@ int check_push(psg_ctx* c, int chl, int time, uint64_t kb, uint64_t ke, size_t n
   }
   return PSG_OK;
 }
-
-}  // namespace
 
 int psg_ctx::decode_pending(Aggregate& a, size_t take, void** blk, size_t* bytes) {
   *blk = nullptr;
@@ -380,7 +390,7 @@ int psg_ctx::push_values(int chl, int time, uint64_t kb, uint64_t ke, const KeyR
     pp.kd = ch[chl].d_keys + *slice;
     if (keys->d) {
       HIP_TRY(psg::launch_check_sorted(keys->d, n, A.d_bad, copy, true));
-    } else {
+    } else if (keys->host) {  // neither: a device push's claim, checked by its intake
       HIP_TRY(psg::launch_check_sorted_host(keys->host, n, A.d_bad, copy));
       pinned_wait = pinned_wait || !(flags & PSG_HOLD_BUFFERS);
     }
@@ -471,8 +481,10 @@ int psg_value_assign(psg_ctx* c, int chl, const void* vals, size_t n) {
   if (int rc = set_dev(c->device)) return rc;
   Channel& C = c->ch[chl];
   const size_t sv = vsize(c->dtype);
-  // the old array goes back to the pool (after any kernel reading it); the
-  // new one is written on the copy stream once it is free
+  // the old array goes back to the pool (after any kernel reading it, a
+  // device pull on a caller's stream included); the new one is written on
+  // the copy stream once it is free
+  if (int rc = c->chan_order(C, c->stream)) return rc;
   c->dev_put(C.d_vals, C.nvals * sv);
   C.d_vals = nullptr;
   C.nvals = 0;
@@ -480,6 +492,9 @@ int psg_value_assign(psg_ctx* c, int chl, const void* vals, size_t n) {
     if (int rc = c->dev_get(n * sv, &C.d_vals, c->copy)) return rc;
     C.nvals = n;
     if (int rc = c->h2d(C.d_vals, vals, n * sv)) return rc;
+    // a device pull on another stream waits for the copy
+    if (C.last)
+      if (int rc = c->chan_mark(C, c->copy)) return rc;
   }
   return c->h2d_finish();
 }
@@ -500,6 +515,7 @@ int psg_value_copy(psg_ctx* c, int chl, size_t off, size_t n, void* out) {
   if (off + n > have) return fail(PSG_ERR_ARG, "value copy out of range");
   if (int rc = set_dev(c->device)) return rc;
   if (int rc = c->join_copy()) return rc;
+  if (int rc = c->chan_order(it->second, c->stream)) return rc;
   const size_t sv = vsize(c->dtype);
   if (n)
     HIP_TRY(hipMemcpyAsync(out, (char*)it->second.d_vals + off * sv, n * sv,
@@ -518,7 +534,7 @@ int psg_push(psg_ctx* c, int chl, int time, uint64_t kb, uint64_t ke,
   std::lock_guard<std::mutex> l(c->mu);
   if (int rc = set_dev(c->device)) return rc;
   size_t lo, hi;
-  if (int rc = check_push(c, chl, time, kb, ke, n, m, &lo, &hi)) return rc;
+  if (int rc = c->check_push(chl, time, kb, ke, n, m, &lo, &hi)) return rc;
   // Dense test ("back - front + 1 == n"): the push's first
   // key is server key a, its last is server key a + n - 1, and those n
   // server keys are n consecutive integers.  Then n strictly increasing
@@ -591,7 +607,7 @@ int psg_push_compressed(psg_ctx* c, int chl, int time, uint64_t kb, uint64_t ke,
   std::lock_guard<std::mutex> l(c->mu);
   if (int rc = set_dev(c->device)) return rc;
   size_t lo, hi;
-  if (int rc = check_push(c, chl, time, kb, ke, n, m, &lo, &hi)) return rc;
+  if (int rc = c->check_push(chl, time, kb, ke, n, m, &lo, &hi)) return rc;
   // staging block: the m + 1 compressed parts back to back; they are
   // decoded right before the merge that needs them (psg_ctx::flush), with
   // every other compressed push pending then, in one launch
@@ -748,7 +764,7 @@ int push_cached_impl(psg_ctx* c, int sender, int chl, int time, uint64_t kb, uin
     return fail(PSG_ERR_SIZE, "%zu values for %zu keys", nvals, n);
   }
   size_t lo, hi;
-  if (int rc = check_push(c, chl, time, kb, ke, n, m, &lo, &hi)) {
+  if (int rc = c->check_push(chl, time, kb, ke, n, m, &lo, &hi)) {
     if (sigcheck) (void)store_check(nullptr);
     return rc;
   }
@@ -895,6 +911,7 @@ int psg_darling_update(psg_ctx* c, int chl, int time, const psg_darling_param* p
     return fail(PSG_ERR_SIZE, "channel %d: %zu keys, %zu values, Darling state of %zu", chl,
                 C.n, C.nvals, C.dn);
   int rc = c->flush(A);
+  if (rc == PSG_OK) rc = c->chan_order(C, c->stream);
   if (rc == PSG_OK) {
     const psg::DarlingParam P{p->eta, p->lambda, p->kkt_filter_threshold, p->delta_max};
     unsigned long long* dv = c->d_small + 4;
@@ -966,6 +983,7 @@ int psg_gather(psg_ctx* c, int chl, const uint64_t* keys, size_t n, void* out,
   void* d_out = (char*)c->scratch + align_up(8 * n, 256);
   if (int rc = c->h2d(d_req, keys, 8 * n)) return rc;
   if (int rc = c->join_copy()) return rc;
+  if (int rc = c->chan_order(C, c->stream)) return rc;
   HIP_TRY(hipMemsetAsync(c->d_small, 0, 16, c->stream));
   HIP_TRY(psg::launch_check_sorted(d_req, n, c->d_small + 1, c->stream, false));
   HIP_TRY(psg::launch_gather(c->dtype, C.d_keys, C.n, C.d_vals, d_req, n, d_out,

@@ -69,6 +69,7 @@
 
 #include "../../include/psg.h"
 #include "psg_blocks.h"
+#include "psg_device.h"
 #include "psg_host.h"
 #include "psg_internal.h"
 #include "psg_sort.h"
@@ -362,16 +363,7 @@ __global__ __launch_bounds__(256) void trans_times_long_kernel(
 }
 
 // ---- (f) ------------------------------------------------------------------------
-// the tree sum of the workgroup's 256 values v, over s (256 doubles of LDS):
-// s[0] on return, for lane 0 to read
-__device__ __forceinline__ void block_tree_sum(double v, double* s) {
-  s[threadIdx.x] = v;
-  __syncthreads();
-  for (int h = 128; h >= 1; h >>= 1) {
-    if ((int)threadIdx.x < h) s[threadIdx.x] += s[threadIdx.x + h];
-    __syncthreads();
-  }
-}
+using dev::block_tree_sum;  // the fixed-order sum of the workgroup's 256 values
 
 // loss.h:74,81 as written; partial[workgroup] = the tree sum of its 256 losses
 __global__ __launch_bounds__(256) void logit_kernel(const double* __restrict__ y,

@@ -9,16 +9,24 @@ worker's lines of ``preprocessData`` (:110-117) and ``evaluateProgress``
 dictionary positions ``[cb, ce)`` are the reference's ``seg_pos``.
 
 ``block_step`` is one worker pass of ``Darling::updateModel`` (:203-250)
-against a ``KVVector`` server in the same context.  G, U and the pulled
-weights pass through the host there: the KVVector push (``psg_push``) and
-gather (``psg_gather``) take host arrays and have no device-pointer forms.
-Adding those is a separate change; the kernels on both sides already read and
-write device arrays.
+against a ``KVVector`` server in the same context with G, U and the pulled
+weights passing through the host (``psg_push``, ``psg_darling_update``,
+``psg_gather``): five host waits per block.  It is kept as the comparison
+path of the device form.
+
+``push_block`` / ``pull_block`` / ``block_step_dev`` are the same pass over
+the context's device-array forms (``psg_push_dev``, ``psg_darling_update_dev``,
+``psg_pull_dev``): G and U go from ``psg_mb_darling_gradients``' scratch block
+into the server's aggregate and the pulled weights from the server's values
+into ``psg_mb_darling_update_dual`` without leaving HBM, all enqueued on the
+minibatch's stream, with no host wait.  ``darling_pass`` drives a whole pass
+over the key blocks for W workers that way, and ``server_progress`` is the
+server branch of ``evaluateProgress`` (:538-555), the one place that waits.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -43,7 +51,8 @@ class DarlingWorker:
     ``delta_max`` are conf_.darling()'s delta_init_value and delta_max_value."""
 
     _DICT, _W = 0, 1  # uploaded blocks
-    _GU = 0           # scratch slot of the minibatch
+    _GU = 0           # scratch slot of the minibatch: (G, U) of a block
+    _PULL = 1         # ... and the block's pulled weights (device forms)
 
     def __init__(self, ctx, delta_init: float, delta_max: float, device: int = 0):
         self._L = _lib.lib()
@@ -164,3 +173,141 @@ class DarlingWorker:
         server.getValue(pull)                                              # :225-250
         self.update_dual(cb, ce, pull.value[0])                            # :238
         return vio.value
+
+    # ---- the same pass with G, U and the weights resident (device forms) ----
+    def reserve_block(self, ncols: int) -> None:
+        """Scratch for blocks of up to ``ncols`` columns.  A scratch block
+        that grows is reallocated, which waits for the device: sized once for
+        the widest block, no later push_block / pull_block allocates."""
+        self.mb.scratch(self._GU, max(16 * ncols, 8))
+        self.mb.scratch(self._PULL, max(8 * ncols, 8))
+
+    def _key_range(self, cb: int, ce: int) -> tuple:
+        return (int(self.dict_keys[cb]),
+                int(self.dict_keys[ce]) if ce < self.ndict else (1 << 64) - 1)
+
+    def push_block(self, server: KVVector, chl: int, time: int, cb: int, ce: int,
+                   key_range: Optional[tuple] = None, slice: Optional[int] = None) -> None:
+        """computeGradients over columns [cb, ce) (:208) and the push of
+        (G, U) as one m = 2 message at ``time`` (:215-220), enqueued on the
+        minibatch's stream: psg_mb_darling_gradients into scratch, then
+        psg_push_dev of the dictionary's device slice with the two arrays.
+        ``slice``: the claim that these keys are the server's
+        key(chl)[slice, slice + ce - cb) (psg_push_dev).  No host wait; a
+        no-op for ce <= cb (seg_pos.empty())."""
+        if ce <= cb:
+            return
+        m = ce - cb
+        if key_range is None:
+            key_range = self._key_range(cb, ce)
+        s = self.mb.stream
+        p = self.mb.scratch(self._GU, 16 * m)
+        _lib.check(self._L.psg_mb_darling_gradients(self.mb._h, cb, ce, p, p + 8 * m, s))
+        server.push_dev(chl, time, key_range, self._dev[self._DICT].data_ptr() + 8 * cb, m,
+                        [p, p + 8 * m], slice=slice, stream=s)
+
+    def pull_block(self, server: KVVector, chl: int, cb: int, ce: int) -> None:
+        """The pull of the block's weights (:225-250) into scratch by
+        psg_pull_dev, then updateDual from them (:238).  No host wait; a no-op
+        for ce <= cb."""
+        if ce <= cb:
+            return
+        m = ce - cb
+        s = self.mb.stream
+        p = self.mb.scratch(self._PULL, 8 * m)
+        server.pull_dev(chl, self._dev[self._DICT].data_ptr() + 8 * cb, m, p, stream=s)
+        _lib.check(self._L.psg_mb_darling_update_dual(self.mb._h, cb, ce, p, self.delta_max, s))
+
+    def block_step_dev(self, server: KVVector, chl: int, time: int, cb: int, ce: int,
+                       param: dict, key_range: Optional[tuple] = None,
+                       slice: Optional[int] = None) -> None:
+        """block_step for a single worker with nothing crossing the host:
+        push_block, psg_darling_update_dev, pull_block.  The block's violation
+        is accumulated on the server (server_progress reads it)."""
+        if ce <= cb:
+            return
+        self.push_block(server, chl, time, cb, ce, key_range, slice)
+        server_update_dev(server, chl, time, param, self.delta_max)
+        self.pull_block(server, chl, cb, ce)
+
+
+def server_update_dev(server: KVVector, chl: int, time: int, param: dict,
+                      delta_max: float) -> None:
+    """The server's UPDATE_MODEL step on the aggregate of ``time``
+    (psg_darling_update_dev): enqueued, no host wait."""
+    p = _lib.DarlingParam(param["eta"], param["lambda_"], param["kkt_filter_threshold"],
+                          delta_max)
+    _lib.check(server._L.psg_darling_update_dev(server._h, chl, time,
+                                                C.cast(C.byref(p), C.c_void_p)))
+
+
+def block_columns(dict_keys: np.ndarray, kb: int, ke: int) -> Tuple[int, int]:
+    """A worker's columns [cb, ce) of the global key block [kb, ke): the
+    positions of its dictionary's keys in the block, SArray::findRange's two
+    lower_bounds (psg_find_range's rule).  Pure numpy."""
+    d = np.asarray(dict_keys, dtype=np.uint64)
+    cb = int(np.searchsorted(d, np.uint64(kb), side="left"))
+    ce = int(np.searchsorted(d, np.uint64(ke), side="left"))
+    return cb, max(ce, cb)
+
+
+def pass_schedule(dicts: Sequence[np.ndarray], key_blocks: Sequence[tuple]) -> List[list]:
+    """For every key block of ``key_blocks``, in order, the (worker, cb, ce) of
+    each worker that holds a key of it (ce > cb); an empty list where none
+    does.  Pure numpy: darling_pass's block-to-columns mapping."""
+    out = []
+    for kb, ke in key_blocks:
+        row = []
+        for w, d in enumerate(dicts):
+            cb, ce = block_columns(d, kb, ke)
+            if ce > cb:
+                row.append((w, cb, ce))
+        out.append(row)
+    return out
+
+
+def darling_pass(server: KVVector, workers: Sequence[DarlingWorker], chl: int, time: int,
+                 key_blocks: Sequence[tuple], param: dict) -> int:
+    """One data pass of Darling::updateModel (:196-267) for W workers against
+    ``server``, with no host wait inside the pass.  For each global key block
+    [kb, ke) of ``key_blocks``, in the given order: every worker holding a
+    key of it pushes (push_block, key_range = the block), the server updates
+    once (psg_darling_update_dev), then every such worker pulls (pull_block).
+    Blocks run strictly one after another -- max_block_delay = 0; the
+    reference's bounded-delay schedule (darling.cc:44-58) is not built.  Time
+    advances by 3 per block (the push at t, the server's update at t + 1 and
+    the pull at t + 2 of :215-250 are one block's times); a block in which no
+    worker holds a key is skipped, time included: nothing is pushed, so there
+    is no aggregate to update (the reference would CHECK-fail in received).
+    Returns the time after the last block.  Errors found on the device are
+    reported by server.dev_status() or server_progress()."""
+    sched = pass_schedule([w.dict_keys for w in workers], key_blocks)
+    for w in workers:
+        w.reserve_block(max([ce - cb for row in sched for i, cb, ce in row
+                             if workers[i] is w], default=0))
+    delta_max = workers[0].delta_max if workers else 0.0
+    for (kb, ke), row in zip(key_blocks, sched):
+        if not row:
+            continue
+        for i, cb, ce in row:
+            workers[i].push_block(server, chl, time, cb, ce, key_range=(int(kb), int(ke)))
+        server_update_dev(server, chl, time, param, delta_max)
+        for i, cb, ce in row:
+            workers[i].pull_block(server, chl, cb, ce)
+        time += 3
+    return time
+
+
+def server_progress(server: KVVector, chl: int, lambda_: float,
+                    reset_violation: bool = False) -> dict:
+    """The server branch of evaluateProgress (:538-555) by
+    psg_darling_progress: nnz_w, objv = lambda * sum |w|, the violation
+    accumulated since the last reset, nnz_active.  Waits for the device and
+    raises the deferred error of the device forms, if any."""
+    nnz_w, nnz_as = C.c_size_t(), C.c_size_t()
+    objv, vio = C.c_double(), C.c_double()
+    _lib.check(server._L.psg_darling_progress(server._h, chl, float(lambda_),
+                                              1 if reset_violation else 0, C.byref(nnz_w),
+                                              C.byref(objv), C.byref(vio), C.byref(nnz_as)))
+    return {"nnz_w": nnz_w.value, "objv": objv.value, "violation": vio.value,
+            "nnz_active": nnz_as.value}

@@ -207,6 +207,34 @@ class KVVector:
         return matched.value
 
 
+    # -- device-array forms (psg_push_dev / psg_pull_dev / psg_dev_status) --
+    def push_dev(self, channel: int, time: int, key_range, keys_dev: int, n: int,
+                 vals_dev: Sequence[int], slice: Optional[int] = None,
+                 stream: Optional[int] = None) -> None:
+        """setValue of a value message whose keys_dev[n] and vals_dev[i][n]
+        are device pointers of this context's device, produced on ``stream``
+        (None: the device's default stream).  ``slice``: the claim that the
+        keys are key(channel)[slice, slice + n).  Enqueues only."""
+        arr = _lib.ptr_array(list(vals_dev))
+        _lib.check(self._L.psg_push_dev(self._h, channel, time, int(key_range[0]),
+                                        int(key_range[1]), keys_dev, n, len(vals_dev), arr,
+                                        _lib.PSG_NO_SLICE if slice is None else int(slice),
+                                        stream or None))
+
+    def pull_dev(self, channel: int, keys_dev: int, n: int, out_dev: int,
+                 matched_dev: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """getValue into out_dev[n] for the sorted device keys keys_dev[n];
+        matched_dev: an optional device uint64 set to the matched count.
+        Enqueues only."""
+        _lib.check(self._L.psg_pull_dev(self._h, channel, keys_dev, n, out_dev,
+                                        matched_dev or None, stream or None))
+
+    def dev_status(self) -> None:
+        """Waits for the device forms' work and raises their deferred error
+        (psg_dev_status), once."""
+        _lib.check(self._L.psg_dev_status(self._h))
+
+
 class MergePlan:
     """A prepared device-resident batch of (channel, time) merges.
 
