@@ -709,6 +709,98 @@ int psg_mb_stream(psg_minibatch* mb, void** stream);
 size_t psg_mb_sort_tile(void);
 
 /* ------------------------------------------------------------------ */
+/* Text ingest: LIBSVM / ADFEA lines to a resident minibatch           */
+/* (StreamReader::readMatricesFromText, src/data/stream_reader.h:50-122,*/
+/* over ExampleParser::parseLibsvm / parseAdfea,                       */
+/* src/data/example_parser.cc:84-160), in the configuration ftrl.cc:80 */
+/* requires: ignore_feature_group = true, one label vector and one     */
+/* sparse matrix.                                                      */
+/* ------------------------------------------------------------------ */
+/* The result is what psg_mb_load would have been given: offset / index /
+ * value / y, so every later psg_mb_* call works unchanged.
+ * Lines are what fgets returns: bytes up to and including '\n'; a last line
+ * without '\n' counts only when final != 0 (the buffer ends the data).  At
+ * most max_rows lines are taken.
+ * PSG_TEXT_LIBSVM: tokens split at " \t\r\n".  Token 0 is the label by
+ * strtof, y = (double)label.  Every further token is idx:val, split at its
+ * first ':'; idx by strtoull (base 10), val by strtof, both consumed to the
+ * end; idx must not decrease within the line (equal is allowed).  The matrix
+ * is valued: value = (double)(float)val.
+ * PSG_TEXT_ADFEA: tokens split at " :" only, so '\n', '\r' and '\t' are
+ * token bytes.  Tokens 0 and 1 are skipped, token 2 is the label by strtol
+ * (truncated to int32), y = label > 0 ? 1 : -1; after it odd tokens are keys
+ * (strtoull) and even tokens slot ids, which are not parsed; a key is
+ * appended when its slot token arrives.  The matrix is binary.  What follows
+ * from that is kept: a trailing slot token may carry "\r\n"; a line whose
+ * last token is the label or a key is rejected (the token ends in '\n'); a
+ * last key with no slot token on a final line without '\n' is dropped.
+ * A rejected line ends the minibatch (readOneLineFromText returning false,
+ * stream_reader.h:95): the rows before it are loaded, the line is consumed
+ * and reported in bad_line.
+ * Defined deviations from the reference, each a rejected line:
+ *  - a LIBSVM line with no token (the reference calls strtof(NULL)) and an
+ *    ADFEA line with fewer than three tokens (no label value: the CHECK_EQ of
+ *    stream_reader.h:104);
+ *  - a line of kMaxLineLength_ - 1 = 61439 bytes or more, its '\n' counted
+ *    (the reference splits it in two);
+ *  - a line that holds a NUL byte.
+ * The fast grammar.  A token is converted where it is parsed (on the device
+ * in psg_mb_load_text) only if it matches:
+ *  - key / idx: 1..20 decimal digits; a value past 2^64 - 1 saturates;
+ *  - ADFEA label: an optional '-' and 1..9 digits;
+ *  - val / LIBSVM label: an optional '-', digits, an optional '.' digits, at
+ *    most 64 bytes, whose decimal significand w (leading zeros and trailing
+ *    fraction zeros dropped) is <= 2^24 with k <= 10 fraction digits; the
+ *    result is (float)((double)w / 10^k), which is strtof's; "-0" is -0.0f.
+ * Every other token (signs, blanks, empty digit strings, exponents, hex
+ * floats, inf / nan, more digits, '\n' inside an ADFEA token, ...) is a slow
+ * token: the host calls the reference's own libc function on a NUL-terminated
+ * copy and the result, or the line's rejection, is patched in.  Results do
+ * not depend on how many tokens are slow.  A LIBSVM idx:val token counts as
+ * one token and is slow if either half is.
+ * Out of scope: TERAFEA, ignore_feature_group = false, files, gzip, the
+ * protobuf and binary formats, text that is already on the device. */
+#define PSG_TEXT_ADFEA 4   /* DataConfig::ADFEA */
+#define PSG_TEXT_LIBSVM 5  /* DataConfig::LIBSVM */
+typedef struct psg_text_result {
+  uint64_t rows;        /* rows loaded */
+  uint64_t nnz;         /* entries loaded */
+  uint64_t consumed;    /* bytes of text used up, the rejected line included */
+  int64_t bad_line;     /* the rejected line (0-based; == rows), -1: none */
+  uint64_t slow_tokens; /* tokens that went to libc.  psg_mb_load_text counts
+                         * those of all the lines it took (up to max_rows);
+                         * psg_text_parse_host stops at the rejected line */
+  double parse_ms;      /* psg_mb_load_text with psg_mb_profile on: its
+                         * kernels' time by HIP events (the slow tokens' host
+                         * time included), else -1 */
+} psg_text_result;
+/* Text in host memory, free on return; replaces the previous minibatch and
+ * leaves it as psg_mb_load does.  All of [0, nbytes) is copied to the device
+ * and counted, so hand it about a minibatch of text, not a whole file.
+ * PSG_ERR_ARG: a null argument, an unknown format.  PSG_ERR_SIZE: nbytes or
+ * the entries >= 2^32 - 1.  One host wait more than psg_mb_load (the sizes);
+ * two more when there are slow tokens; three when a line is rejected. */
+int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format,
+                     size_t max_rows, int final, psg_text_result* result);
+/* The same parse, serially on the host, for callers without a device.  Two
+ * calls: with offset == NULL it only fills *result (rows, nnz: the sizes);
+ * then offset[rows + 1], index[nnz], value[nnz] (LIBSVM; may be NULL, and is
+ * not written for ADFEA) and y[rows], with rows <= rows_cap and nnz <=
+ * nnz_cap, or PSG_ERR_SIZE (the arrays then hold a part of the result).  One
+ * call does when the arrays are known to be large enough. */
+int psg_text_parse_host(const char* text, size_t nbytes, int format, size_t max_rows, int final,
+                        uint64_t* offset, uint64_t* index, double* value, double* y,
+                        size_t rows_cap, size_t nnz_cap, psg_text_result* result);
+/* Bytes of text per workgroup of the ingest kernels (tests place tokens and
+ * newlines around its multiples). */
+size_t psg_text_chunk(void);
+/* psg_mb_read ids of the loaded CSR (after either load) */
+#define PSG_MB_OFFSET 24 /* uint64[rows + 1] */
+#define PSG_MB_INDEX 25  /* uint64[nnz] */
+#define PSG_MB_VALUE 26  /* double[nnz], none for a binary matrix */
+#define PSG_MB_Y 27      /* double[rows] */
+
+/* ------------------------------------------------------------------ */
 /* Batch worker step: the worker half of Darling::updateModel          */
 /* (src/linear_method/darling.cc:196-250) on a localized minibatch:    */
 /* computeGradients (:306-356), updateDual (:358-435), the worker's    */

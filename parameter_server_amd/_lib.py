@@ -72,6 +72,10 @@ PSG_AUC_BY_KEY, PSG_AUC_AS_WRITTEN = 0, 1
 # ... and the Darling worker's state (psg_mb_darling_*)
 (PSG_MB_DARLING_DUAL, PSG_MB_DARLING_CUR_W, PSG_MB_DARLING_DELTA, PSG_MB_DARLING_ACTIVE,
  PSG_MB_DARLING_DELTA_W) = range(32, 37)
+# ... and the loaded CSR
+PSG_MB_OFFSET, PSG_MB_INDEX, PSG_MB_VALUE, PSG_MB_Y = range(24, 28)
+# psg_mb_load_text's formats (DataConfig's values)
+PSG_TEXT_ADFEA, PSG_TEXT_LIBSVM = 4, 5
 
 # Every symbol include/psg.h declares, with its ctypes signature.
 _u64 = C.c_uint64
@@ -107,6 +111,13 @@ class DarlingParam(C.Structure):
 
     _fields_ = [("eta", C.c_double), ("lambda_", C.c_double),
                 ("kkt_filter_threshold", C.c_double), ("delta_max", C.c_double)]
+
+
+class TextResult(C.Structure):
+    """psg_text_result (include/psg.h)."""
+
+    _fields_ = [("rows", _u64), ("nnz", _u64), ("consumed", _u64), ("bad_line", C.c_int64),
+                ("slow_tokens", _u64), ("parse_ms", C.c_double)]
 
 
 SIGNATURES = {
@@ -228,6 +239,10 @@ SIGNATURES = {
     "psg_mb_darling_objv": (C.c_int, [_p, C.POINTER(C.c_double), _p]),
     "psg_mb_darling_set_state": (C.c_int, [_p, _p, _p, _p, _p]),
     "psg_mb_labels": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
+    "psg_mb_load_text": (C.c_int, [_p, _p, _sz, C.c_int, _sz, C.c_int, C.POINTER(TextResult)]),
+    "psg_text_parse_host": (C.c_int, [_p, _sz, C.c_int, _sz, C.c_int, _p, _p, _p, _p, _sz, _sz,
+                                      C.POINTER(TextResult)]),
+    "psg_text_chunk": (_sz, []),
     "psg_auc_create": (C.c_int, [_p, C.c_int64, C.POINTER(_p)]),
     "psg_auc_destroy": (None, [_p]),
     "psg_auc_clear": (C.c_int, [_p]),

@@ -72,6 +72,7 @@
 #include "psg_device.h"
 #include "psg_host.h"
 #include "psg_internal.h"
+#include "psg_minibatch.h"
 #include "psg_sort.h"
 
 namespace psg {
@@ -706,58 +707,6 @@ using psg::fail;
 
 namespace {
 
-enum BufId {
-  B_OFFSET, B_INDEX, B_VALUE, B_Y, B_KEY_A, B_KEY_B, B_POS_A, B_POS_B, B_COUNTS, B_TILE_SUM,
-  B_UNIQ_KEY, B_KEY_CNT, B_RUN_START, B_RUN_OF, B_ROW_OF, B_RUN_RANK, B_REMAPPED, B_BEFORE,
-  B_NEW_OFFSET, B_NEW_INDEX, B_NEW_VALUE, B_DICT_RUN, B_CNT_POS, B_CNT_NEG, B_XW, B_TAU, B_C,
-  B_LOSS, B_PARTIAL, B_GRAD, B_TERM, B_LONG_LIST, B_SCRATCH0, B_SCRATCH1, B_SCRATCH2, B_SCRATCH3,
-  // (g): the Darling worker's state, its second term array and the rows' lists
-  B_DUAL, B_CUR_W, B_DELTA, B_ACTIVE, B_DELTA_W, B_EXP_DELTA, B_TERM2, B_RKEY_A, B_RKEY_B,
-  B_RPOS_A, B_RPOS_B, B_ROW_START, B_COL_RANGE, B_COUNT
-};
-
-// device words: [0] OR of the keys, [1] AND, [2] dictionary order violations,
-// [3] objv, [4] as two u32: n_uniq, survivors, [5] as u32: long runs; then
-// the 256 digit totals
-constexpr size_t kSmallBytes = 6 * 8 + 256 * 4;
-
-enum State { S_NEW = 0, S_LOADED, S_UNIQ, S_LOCAL, S_GRAD };
-
-}  // namespace
-
-struct psg_minibatch : psg::DeviceBlocks<B_COUNT> {
-  int state = S_NEW;
-  size_t rows = 0, nnz = 0, n_uniq = 0, ndict = 0;
-  bool binary = false;
-  uint64_t differ = 0;  // the key bits that differ between some two keys
-  const uint64_t* skey = nullptr;  // the sorted pairs (one side of the ping-pong)
-  const uint32_t* spos = nullptr;
-  // (g): set by psg_mb_darling_init, cleared by psg_mb_load and psg_mb_localize
-  bool darling = false;
-  bool xw_own = false;  // psg_mb_times has run into the minibatch's own Xw (psg_mb_labels)
-  const uint32_t* row_pair = nullptr;  // the rows' lists (one side of their ping-pong)
-  // host: pair_lo[k] = the first sorted pair of the first of keys k, k + 1, ...
-  // that has a run (nnz: none); pair_hi[k] = the end of the last run among
-  // keys 0 .. k - 1 (0: none).  Block [cb, ce) is pairs [pair_lo[cb], pair_hi[ce]).
-  std::vector<uint32_t> pair_lo, pair_hi;
-  size_t n_long = 0;  // the length of the long-run list, read at psg_mb_darling_init
-  size_t last_cb = 0, last_ce = 0;  // the columns of the last psg_mb_darling_update_dual
-  size_t scratch_len[4] = {0, 0, 0, 0};
-  // psg_mb_profile: a pair of timing events around each stage's launches
-  bool prof = false;
-  hipEvent_t tev[2 * PSG_MB_STAGES] = {};
-  bool tset[2 * PSG_MB_STAGES] = {};
-  void tick(int stage, int end, hipStream_t s) {
-    const int i = 2 * stage + end;
-    if (prof && tev[i] && hipEventRecord(tev[i], s) == hipSuccess) tset[i] = true;
-  }
-
-  uint32_t* d_u32(int word) const { return (uint32_t*)(d_small + 4) + word; }
-  uint32_t* d_dtotal() const { return (uint32_t*)(d_small + 6); }
-};
-
-namespace {
-
 using namespace psg;
 
 // the nnz keys `kin` (which may be the key_b block) stably sorted on the
@@ -796,6 +745,54 @@ size_t elem_size(int what) {
 
 }  // namespace
 
+namespace psg {
+
+int mb_load_begin(psg_minibatch* mb, size_t rows, size_t n, bool valued) {
+  HIP_TRY(hipSetDevice(mb->device));
+  if (int rc = mb->settle()) return rc;  // the previous minibatch's work
+  mb->state = S_NEW;
+  mb->darling = false;
+  mb->xw_own = false;
+  const size_t ntiles = blocks_of(n, kSortTile);
+  return mb->need_all({
+      {B_OFFSET, 8 * (rows + 1)}, {B_Y, 8 * rows}, {B_INDEX, 8 * n},
+      {B_VALUE, valued ? 8 * n : 0}, {B_KEY_A, 8 * n}, {B_KEY_B, 8 * n}, {B_POS_A, 4 * n},
+      {B_POS_B, 4 * n}, {B_COUNTS, 4 * 256 * ntiles},
+      {B_TILE_SUM, 4 * (size_t)blocks_of(n, kFlagTile) + 4}, {B_UNIQ_KEY, 8 * n},
+      {B_KEY_CNT, 4 * n}, {B_RUN_START, 4 * (n + 1)}, {B_RUN_OF, 4 * n}, {B_ROW_OF, 4 * n},
+      {B_RUN_RANK, 4 * n}, {B_REMAPPED, 4 * n}, {B_BEFORE, 4 * (n + 1)},
+      {B_NEW_OFFSET, 8 * (rows + 1)}, {B_NEW_INDEX, 4 * n}, {B_NEW_VALUE, valued ? 8 * n : 0},
+      {B_TERM, 8 * n}, {B_XW, 8 * rows}, {B_TAU, 8 * rows}, {B_C, 8 * rows}, {B_LOSS, 8 * rows},
+      {B_PARTIAL, 8 * (size_t)blocks_of(rows, 256) + 8}});
+}
+
+int mb_load_finish(psg_minibatch* mb, size_t rows, size_t n, bool valued) {
+  hipStream_t s = mb->stream;
+  mb->h_small[0] = 0;
+  mb->h_small[1] = ~0ull;
+  mb->h_small[2] = 0;
+  HIP_TRY(hipMemcpyAsync(mb->d_small, mb->h_small, 24, hipMemcpyHostToDevice, s));
+  if (n) {
+    LAUNCH(row_of_kernel, blocks_of(n, 256), s, mb->at<uint64_t>(B_OFFSET), (uint32_t)rows,
+           (uint32_t)n, mb->at<uint32_t>(B_ROW_OF));
+    const uint32_t grid = std::min<uint32_t>(blocks_of(n, 256), 2048u);
+    LAUNCH(key_bits_kernel, grid, s, mb->at<uint64_t>(B_INDEX), (uint32_t)n, mb->d_small);
+    if (int rc = launched("minibatch load")) return rc;
+  }
+  HIP_TRY(hipMemcpyAsync(mb->h_small, mb->d_small, 16, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  mb->differ = n ? mb->h_small[0] ^ mb->h_small[1] : 0;
+  mb->rows = rows;
+  mb->nnz = n;
+  mb->binary = !valued;
+  mb->n_uniq = mb->ndict = 0;
+  mb->last_s = nullptr;
+  mb->state = S_LOADED;
+  return PSG_OK;
+}
+
+}  // namespace psg
+
 extern "C" {
 
 size_t psg_mb_sort_tile(void) { return kSortTile; }
@@ -823,6 +820,8 @@ void psg_mb_destroy(psg_minibatch* mb) {
   mb->close();
   for (hipEvent_t e : mb->tev)
     if (e) (void)hipEventDestroy(e);
+  if (mb->h_text) (void)hipHostFree(mb->h_text);
+  if (mb->h_slow) (void)hipHostFree(mb->h_slow);
   delete mb;
 }
 
@@ -838,50 +837,17 @@ int psg_mb_load(psg_minibatch* mb, const uint64_t* offset, size_t rows, const ui
   for (size_t i = 0; i < rows; ++i)
     if (offset[i] > offset[i + 1]) return fail(PSG_ERR_ARG, "offset decreases at row %zu", i);
   if (nnz && !index) return fail(PSG_ERR_ARG, "null index");
-  HIP_TRY(hipSetDevice(mb->device));
-  if (int rc = mb->settle()) return rc;  // the previous minibatch's work
-  mb->state = S_NEW;
-  mb->darling = false;
-  mb->xw_own = false;
-  const size_t n = (size_t)nnz, ntiles = blocks_of(n, kSortTile);
-  if (int rc = mb->need_all({
-      {B_OFFSET, 8 * (rows + 1)}, {B_Y, 8 * rows}, {B_INDEX, 8 * n},
-      {B_VALUE, value ? 8 * n : 0}, {B_KEY_A, 8 * n}, {B_KEY_B, 8 * n}, {B_POS_A, 4 * n},
-      {B_POS_B, 4 * n}, {B_COUNTS, 4 * 256 * ntiles},
-      {B_TILE_SUM, 4 * (size_t)blocks_of(n, kFlagTile) + 4}, {B_UNIQ_KEY, 8 * n},
-      {B_KEY_CNT, 4 * n}, {B_RUN_START, 4 * (n + 1)}, {B_RUN_OF, 4 * n}, {B_ROW_OF, 4 * n},
-      {B_RUN_RANK, 4 * n}, {B_REMAPPED, 4 * n}, {B_BEFORE, 4 * (n + 1)},
-      {B_NEW_OFFSET, 8 * (rows + 1)}, {B_NEW_INDEX, 4 * n}, {B_NEW_VALUE, value ? 8 * n : 0},
-      {B_TERM, 8 * n}, {B_XW, 8 * rows}, {B_TAU, 8 * rows}, {B_C, 8 * rows}, {B_LOSS, 8 * rows},
-      {B_PARTIAL, 8 * (size_t)blocks_of(rows, 256) + 8}}))
-    return rc;
+  const size_t n = (size_t)nnz;
+  if (int rc = psg::mb_load_begin(mb, rows, n, value != nullptr)) return rc;
   hipStream_t s = mb->stream;
   HIP_TRY(hipMemcpyAsync(mb->b[B_OFFSET].p, offset, 8 * (rows + 1), hipMemcpyHostToDevice, s));
   if (rows) HIP_TRY(hipMemcpyAsync(mb->b[B_Y].p, y, 8 * rows, hipMemcpyHostToDevice, s));
-  mb->h_small[0] = 0;
-  mb->h_small[1] = ~0ull;
-  mb->h_small[2] = 0;
-  HIP_TRY(hipMemcpyAsync(mb->d_small, mb->h_small, 24, hipMemcpyHostToDevice, s));
   if (n) {
     HIP_TRY(hipMemcpyAsync(mb->b[B_INDEX].p, index, 8 * n, hipMemcpyHostToDevice, s));
     if (value)
       HIP_TRY(hipMemcpyAsync(mb->b[B_VALUE].p, value, 8 * n, hipMemcpyHostToDevice, s));
-    LAUNCH(row_of_kernel, blocks_of(n, 256), s, mb->at<uint64_t>(B_OFFSET), (uint32_t)rows,
-           (uint32_t)n, mb->at<uint32_t>(B_ROW_OF));
-    const uint32_t grid = std::min<uint32_t>(blocks_of(n, 256), 2048u);
-    LAUNCH(key_bits_kernel, grid, s, mb->at<uint64_t>(B_INDEX), (uint32_t)n, mb->d_small);
-    if (int rc = launched("minibatch load")) return rc;
   }
-  HIP_TRY(hipMemcpyAsync(mb->h_small, mb->d_small, 16, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));  // the host arrays are free on return
-  mb->differ = n ? mb->h_small[0] ^ mb->h_small[1] : 0;
-  mb->rows = rows;
-  mb->nnz = n;
-  mb->binary = value == nullptr;
-  mb->n_uniq = mb->ndict = 0;
-  mb->last_s = nullptr;
-  mb->state = S_LOADED;
-  return PSG_OK;
+  return psg::mb_load_finish(mb, rows, n, value != nullptr);  // the host arrays are free on return
 }
 
 int psg_mb_uniq(psg_minibatch* mb, const uint64_t** keys_dev, const uint32_t** cnt_dev,
@@ -1141,6 +1107,10 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
     case PSG_MB_KEY_CNT: need_state = S_UNIQ; id = B_KEY_CNT; n = mb->n_uniq; break;
     case PSG_MB_RUN_START: need_state = S_UNIQ; id = B_RUN_START; n = mb->nnz ? mb->n_uniq + 1 : 0; break;
     case PSG_MB_ROW_OF: need_state = S_LOADED; id = B_ROW_OF; n = mb->nnz; break;
+    case PSG_MB_OFFSET: need_state = S_LOADED; id = B_OFFSET; n = mb->rows + 1; break;
+    case PSG_MB_INDEX: need_state = S_LOADED; id = B_INDEX; n = mb->nnz; break;
+    case PSG_MB_VALUE: need_state = S_LOADED; id = B_VALUE; n = mb->binary ? 0 : mb->nnz; break;
+    case PSG_MB_Y: need_state = S_LOADED; id = B_Y; n = mb->rows; break;
     case PSG_MB_REMAPPED: need_state = S_LOCAL; id = B_REMAPPED; n = mb->nnz; break;
     case PSG_MB_NEW_OFFSET: need_state = S_LOCAL; id = B_NEW_OFFSET; n = mb->rows + 1; break;
     case PSG_MB_NEW_INDEX: need_state = S_LOCAL; id = B_NEW_INDEX; n = kept_unknown; break;

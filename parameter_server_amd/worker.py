@@ -42,7 +42,41 @@ ARRAYS = {
     "run_start": (_lib.PSG_MB_RUN_START, np.uint32),
     "remapped": (_lib.PSG_MB_REMAPPED, np.uint32),
     "row_of": (_lib.PSG_MB_ROW_OF, np.uint32),
+    "offset": (_lib.PSG_MB_OFFSET, np.uint64),
+    "index": (_lib.PSG_MB_INDEX, np.uint64),
+    "value": (_lib.PSG_MB_VALUE, np.float64),
+    "y": (_lib.PSG_MB_Y, np.float64),
 }
+FORMATS = {"adfea": _lib.PSG_TEXT_ADFEA, "libsvm": _lib.PSG_TEXT_LIBSVM}
+
+
+def text_chunk() -> int:
+    """Bytes of text per workgroup of the ingest kernels (psg_text_chunk)."""
+    return int(_lib.lib().psg_text_chunk())
+
+
+def _format(fmt) -> int:
+    return FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+
+
+def parse_text_host(text: bytes, fmt, max_rows=None, final: bool = True):
+    """psg_text_parse_host: (offset, index, value or None, y, result), parsed
+    serially on the host; what ``Minibatch.load_text`` loads."""
+    L = _lib.lib()
+    text = bytes(text)
+    f = _format(fmt)
+    cap = (1 << 64) - 1 if max_rows is None else int(max_rows)
+    r = _lib.TextResult()
+    _lib.check(L.psg_text_parse_host(text, len(text), f, cap, 1 if final else 0, None, None, None,
+                                     None, 0, 0, C.byref(r)))
+    offset = np.zeros(r.rows + 1, np.uint64)
+    index = np.zeros(r.nnz, np.uint64)
+    value = np.zeros(r.nnz, np.float64) if f == _lib.PSG_TEXT_LIBSVM else None
+    y = np.zeros(r.rows, np.float64)
+    _lib.check(L.psg_text_parse_host(text, len(text), f, cap, 1 if final else 0, _ptr(offset),
+                                     _ptr(index), _ptr(value) if value is not None else None,
+                                     _ptr(y), int(r.rows), int(r.nnz), C.byref(r)))
+    return offset, index, value, y, r
 
 
 def sort_tile() -> int:
@@ -95,6 +129,20 @@ class Minibatch:
                                        _ptr(value) if value is not None else None, _ptr(y)))
         self.rows, self.nnz = offset.size - 1, index.size
         self.n_uniq = self.ndict = 0
+
+    def load_text(self, text: bytes, fmt, max_rows=None, final: bool = True):
+        """psg_mb_load_text: LIBSVM / ADFEA lines (``fmt``: "libsvm", "adfea"
+        or a PSG_TEXT_* id) parsed on the device into this minibatch.  Returns
+        the psg_text_result: rows, nnz, consumed, bad_line, slow_tokens,
+        parse_ms."""
+        text = bytes(text) if not isinstance(text, bytes) else text
+        cap = (1 << 64) - 1 if max_rows is None else int(max_rows)
+        r = _lib.TextResult()
+        _lib.check(self._L.psg_mb_load_text(self._h, text, len(text), _format(fmt), cap,
+                                            1 if final else 0, C.byref(r)))
+        self.rows, self.nnz = int(r.rows), int(r.nnz)
+        self.n_uniq = self.ndict = 0
+        return r
 
     def uniq(self) -> int:
         """psg_mb_uniq: n_uniq; the device arrays are uniq_key_dev, key_cnt_dev."""
@@ -200,9 +248,18 @@ class FTRLWorker:
         (ModelEvaluation::run, model_evaluation.h:48-57): the device pointer
         of Xw[rows], also ``mb.read("xw")``.  No filter insert and no push,
         and a pull does not insert: the model is left as it was."""
+        self.mb.load(offset, index, value, y)
+        return self._predict_loaded()
+
+    def predict_text(self, text: bytes, fmt, max_rows=None, final: bool = True):
+        """``predict`` on the next minibatch of a text buffer (``load_text``
+        in place of ``load``): (the device pointer of Xw, the bytes consumed)."""
+        r = self.mb.load_text(text, fmt, max_rows, final)
+        return self._predict_loaded(), int(r.consumed)
+
+    def _predict_loaded(self) -> int:
         L, mb = self._L, self.mb
         st = mb.stream
-        mb.load(offset, index, value, y)
         n = mb.uniq()
         keys = mb.uniq_key_dev
         w = mb.scratch(self._W, 8 * n)
@@ -218,9 +275,21 @@ class FTRLWorker:
         ``AUC`` of this context that takes (y, Xw) of the minibatch before
         the push: Xw comes from weights that have not seen the minibatch, so
         the histogram is a progressive-validation AUC."""
+        self.mb.load(offset, index, value, y)
+        return self._step_loaded(auc)
+
+    def step_text(self, text: bytes, fmt, max_rows=None, final: bool = True,
+                  auc=None) -> Tuple[float, int, int]:
+        """``step`` on the next minibatch of a text buffer (``load_text`` in
+        place of ``load``): (objv, examples, bytes consumed), so a caller walks
+        a buffer minibatch by minibatch with ``text[consumed:]``."""
+        r = self.mb.load_text(text, fmt, max_rows, final)
+        objv, rows = self._step_loaded(auc)
+        return objv, rows, int(r.consumed)
+
+    def _step_loaded(self, auc=None) -> Tuple[float, int]:
         L, mb = self._L, self.mb
         st = mb.stream  # every enqueue of the step, in order
-        mb.load(offset, index, value, y)
         n = mb.uniq()                                                      # ftrl.cc:96
         if self.freq > 0 and n:                                            # :99-106
             keys = mb.scratch(self._DICT, 8 * n)
