@@ -531,6 +531,11 @@ int psg_freq_query_dev(psg_ctx* ctx, int chl, const uint64_t* keys, size_t n,
                        void* scratch, void* stream);
 /* The n_ counters as CountMin's uint8 data_ (tests, checkpoints). */
 int psg_freq_table(psg_ctx* ctx, int chl, uint8_t* out, size_t n);
+/* The inverse of psg_freq_table (restoring a checkpoint): table[n] becomes
+ * CountMin's data_, in the filter's call order.  n must be the filter's n_
+ * (PSG_ERR_SIZE otherwise); k_ is psg_freq_resize's.  Host array, free on
+ * return. */
+int psg_freq_table_assign(psg_ctx* ctx, int chl, const uint8_t* table, size_t n);
 
 /* ------------------------------------------------------------------ */
 /* Online server model: FTRLModel<uint64, double>                      */
@@ -554,8 +559,8 @@ int psg_freq_table(psg_ctx* ctx, int chl, uint8_t* out, size_t n);
  *    send countUniqIndex's sorted unique keys, ftrl.cc:93-96,143, and the
  *    model does not check).  One that is not is rejected whole by a device
  *    check that runs ahead of the update, reported once as PSG_ERR_UNSORTED
- *    by the next psg_ftrl_pull, psg_ftrl_status or psg_ftrl_export, and then
- *    cleared; later messages apply normally.  psg_ftrl_lookup is a probe
+ *    by the next psg_ftrl_pull, psg_ftrl_status, psg_ftrl_export or
+ *    psg_ftrl_export_state, and then cleared; later messages apply normally.  psg_ftrl_lookup is a probe
  *    for tests and checkpoints and neither reports nor clears it;
  *  - psg_ftrl_export's order is unspecified (as writeToFile's is, the
  *    reference's map order); the Python and C++ mirrors sort by key. */
@@ -595,6 +600,61 @@ int psg_ftrl_export(psg_ctx* ctx, uint64_t* keys, double* w, size_t cap, size_t*
  * or 0 and zeros.  Any output may be NULL. */
 int psg_ftrl_lookup(psg_ctx* ctx, const uint64_t* keys, size_t n, uint64_t* pos, uint64_t* neg,
                     double* w, double* z, uint8_t* found);
+/* Checkpoint and restore.  The reference declares the hooks and leaves them
+ * empty (setReplica / getReplica / recoverFrom, ftrl_model.h:41-44); these
+ * are what they would carry: whole entries {pos, neg, w, z} by key.
+ *
+ * psg_ftrl_import: recoverFrom / setReplica.  An upsert of n whole entries:
+ * a key already present has its entry replaced (the last one wins, as
+ * weight[k] = v does across model files, model_evaluation.h:25), an absent
+ * one is inserted.  Every bit is stored as given (-0.0, NaN payloads, counts
+ * past 2^32); entries and nnz stay exact (nnz by ftrl_model.h:106-110's
+ * comparisons: -0.0 is zero, a NaN weight is not).  Host arrays, free on
+ * return; asynchronous on the context's stream and in the model's call
+ * order, like psg_ftrl_push; the table grows by rehash when n needs it.
+ * pos == neg == z == NULL is the weights-only form, the load of `key w`
+ * model files (model_evaluation.h:16-27): the entries become
+ * (0, 0, w, +0.0) and the model is frozen (below; an empty model file too:
+ * n == 0 with w given).  Any other partly NULL
+ * combination is PSG_ERR_ARG.
+ * Defined deviations:
+ *  - sorted import only: the message must be strictly increasing, and one
+ *    that is not applies nothing and is reported once as PSG_ERR_UNSORTED by
+ *    the next synchronising call, exactly as for a push;
+ *  - after a restore the model equals the saved one entry for entry, and
+ *    entries and nnz are exact, but norm1 / norm2 of psg_ftrl_status are a
+ *    reduction in table order: they agree with the saved model's within the
+ *    bound above (entries * 2^-53 * the sum), not bit for bit. */
+int psg_ftrl_import(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint64_t* pos,
+                    const uint64_t* neg, const double* w, const double* z);
+/* The same with device arrays, enqueued on `stream`; allocates nothing and
+ * waits for nothing while the model has room (psg_ftrl_reserve). */
+int psg_ftrl_import_dev(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint64_t* pos,
+                        const uint64_t* neg, const double* w, const double* z, void* stream);
+/* getReplica(Range<Key>) (ftrl_model.h:42): every entry (those with w == +-0
+ * and the entry of key 0 included) whose key lies in the closed interval
+ * range[0] <= key <= range[1] (closed, so that key 2^64 - 1 can be named;
+ * NULL: every key; range[0] > range[1]: PSG_ERR_ARG), sorted by key on the
+ * device.  The image of a given model is the same bytes on every run,
+ * whatever the table's size and slot order.  *n = the count; PSG_ERR_SIZE
+ * (nothing copied) if that exceeds cap, or 2^32 - 1.  Any output array may be
+ * NULL.  Synchronises, and reports a rejected message as psg_ftrl_status
+ * does. */
+int psg_ftrl_export_state(psg_ctx* ctx, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                          uint64_t* neg, double* w, double* z, size_t cap, size_t* n);
+/* The same into device arrays of cap entries on `stream`; *n_dev (a device
+ * word) = the count.  The host waits once for that count (it shapes the
+ * sort's launches) and takes its work blocks from the context's pool. */
+int psg_ftrl_export_state_dev(psg_ctx* ctx, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                              uint64_t* neg, double* w, double* z, size_t cap,
+                              unsigned long long* n_dev, void* stream);
+/* *frozen = 1 after a weights-only import: the model is evaluation-only (z
+ * is unknown, and a push would recompute w from it).  psg_ftrl_push and
+ * psg_ftrl_push_dev then return PSG_ERR_ARG; pulls, status, exports, lookups
+ * and imports work.  The flag is host state, set by the weights-only call
+ * itself (also one whose message the device check then rejects).
+ * psg_ftrl_init makes a fresh, unfrozen model. */
+int psg_ftrl_frozen(psg_ctx* ctx, int* frozen);
 
 /* ------------------------------------------------------------------ */
 /* Online worker step: FTRL::updateModel's minibatch loop              */

@@ -177,6 +177,7 @@ SIGNATURES = {
     "psg_freq_query_scratch_bytes": (_sz, [_sz]),
     "psg_freq_query_dev": (C.c_int, [_p, C.c_int, _p, _sz, C.c_int, _p, _p, _p, _p]),
     "psg_freq_table": (C.c_int, [_p, C.c_int, _p, _sz]),
+    "psg_freq_table_assign": (C.c_int, [_p, C.c_int, _p, _sz]),
     "psg_comm_unique_id": (C.c_int, [_p]),
     "psg_comm_init": (C.c_int, [C.c_int, C.c_int, _p, C.c_int, C.POINTER(_p)]),
     "psg_comm_destroy": (C.c_int, [_p]),
@@ -218,6 +219,11 @@ SIGNATURES = {
     "psg_ftrl_status": (C.c_int, [_p, _psz, _psz, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "psg_ftrl_export": (C.c_int, [_p, _p, _p, _sz, _psz]),
     "psg_ftrl_lookup": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _p]),
+    "psg_ftrl_import": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p]),
+    "psg_ftrl_import_dev": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _p]),
+    "psg_ftrl_export_state": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _psz]),
+    "psg_ftrl_export_state_dev": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "psg_ftrl_frozen": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "psg_mb_create": (C.c_int, [_p, C.POINTER(_p)]),
     "psg_mb_destroy": (None, [_p]),
     "psg_mb_load": (C.c_int, [_p, _p, _sz, _p, _p, _p]),

@@ -15,6 +15,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <fstream>
+#include <istream>
+#include <map>
 #include <numeric>
 
 #include "kv_vector.h"
@@ -95,6 +98,80 @@ class FTRLModel {
     for (size_t i : order)
       std::fprintf(f, "%llu\t%g\n", (unsigned long long)k[i], (double)w[i]);
     std::fclose(f);
+  }
+
+  // The hooks the reference leaves empty (ftrl_model.h:41-44).  A model's
+  // whole entries, sorted by key.
+  struct State {
+    std::vector<Key> key;
+    std::vector<uint64_t> pos, neg;
+    std::vector<V> w, z;
+  };
+  // getReplica: every entry with first <= key <= last (psg_ftrl_export_state)
+  State exportState(Key first = 0, Key last = ~(Key)0) {
+    const uint64_t range[2] = {first, last};
+    size_t n = 0;
+    int rc = psg_ftrl_export_state(model(), range, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   0, &n);
+    if (rc != PSG_ERR_SIZE) check(rc);
+    State s;
+    s.key.resize(n);
+    s.pos.resize(n);
+    s.neg.resize(n);
+    s.w.resize(n);
+    s.z.resize(n);
+    if (n)
+      check(psg_ftrl_export_state(model(), range, s.key.data(), s.pos.data(), s.neg.data(),
+                                  s.w.data(), s.z.data(), n, &n));
+    return s;
+  }
+  // recoverFrom / setReplica: an upsert of whole entries, strictly increasing
+  // by key (psg_ftrl_import)
+  void importState(const State& s) {
+    const size_t n = s.key.size();
+    if (s.pos.size() != n || s.neg.size() != n || s.w.size() != n || s.z.size() != n)
+      throw Error(PSG_ERR_SIZE, "state array size != key count");
+    check(psg_ftrl_import(model(), s.key.data(), n, s.pos.data(), s.neg.data(), s.w.data(),
+                          s.z.data()));
+  }
+
+  // The parse of ModelEvaluation::run (model_evaluation.h:16-27): "key value"
+  // pairs as `in >> k >> v`, a later pair overriding an earlier one.  Unlike
+  // the reference's loop it does not assign weight[0] from the failed
+  // extraction after the last line; a trailing unpaired token is an error.
+  // Real: the type a weight is rounded through (the reference's is float).
+  template <typename Real = V>
+  static std::map<Key, V> parseModel(std::istream& in) {
+    std::map<Key, V> weight;
+    Key k;
+    while (in >> k) {
+      Real v;
+      if (!(in >> v)) throw Error(PSG_ERR_ARG, "model file: a key without a value");
+      weight[k] = (V)v;
+    }
+    if (!in.eof()) throw Error(PSG_ERR_ARG, "model file: a key that is no uint64");
+    return weight;
+  }
+  // ... and the load: the weights-only import.  The model is evaluation-only
+  // afterwards (psg_ftrl_frozen): pulls work, pushes are PSG_ERR_ARG.
+  template <typename Real = V>
+  void readFromFile(const std::string& path) {
+    std::ifstream in(path);
+    if (!in.good()) throw Error(PSG_ERR_ARG, "cannot open " + path);
+    const std::map<Key, V> weight = parseModel<Real>(in);
+    std::vector<Key> k;
+    std::vector<V> w;
+    for (const auto& kv : weight) {
+      k.push_back(kv.first);
+      w.push_back(kv.second);
+    }
+    if (w.empty()) w.reserve(1);  // a non-null pointer: an empty file still freezes
+    check(psg_ftrl_import(model(), k.data(), k.size(), nullptr, nullptr, w.data(), nullptr));
+  }
+  bool frozen() {
+    int f = 0;
+    check(psg_ftrl_frozen(model(), &f));
+    return f != 0;
   }
 
  private:

@@ -223,6 +223,9 @@ struct Ftrl {
   // every key pushed since.  The device's count is read (a host wait) only
   // when the bound would pass the load limit.
   size_t bound = 0;
+  // evaluation only (psg_ftrl_import's weights-only form: z is unknown, a
+  // push would recompute w from it); pushes are refused
+  bool frozen = false;
   // like a Filter's: the model's operations run in call order whatever
   // streams they are enqueued on
   hipEvent_t last = nullptr;

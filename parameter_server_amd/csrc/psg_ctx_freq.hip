@@ -195,6 +195,21 @@ int psg_freq_table(psg_ctx* c, int chl, uint8_t* out, size_t n) {
   return PSG_OK;
 }
 
+int psg_freq_table_assign(psg_ctx* c, int chl, const uint8_t* table, size_t n) {
+  if (!c || (n && !table)) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  Filter* F;
+  if (int rc = filter_of(c, chl, &F)) return rc;
+  if (n != F->n) return fail(PSG_ERR_SIZE, "table of %zu counters for a filter of %u", n, F->n);
+  if (int rc = set_dev(c->device)) return rc;
+  // in the filter's call order; the caller's array is free on return
+  if (int rc = filter_order(F, c->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(F->d_table, table, n, hipMemcpyHostToDevice, c->stream));
+  if (int rc = filter_mark(c, F, c->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return PSG_OK;
+}
+
 }  // extern "C"
 
 void psg::filter_release(psg_ctx* c, Filter& F) {

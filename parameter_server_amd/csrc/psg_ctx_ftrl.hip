@@ -80,6 +80,78 @@ int ftrl_report(psg_ctx* c, Ftrl* F, unsigned long long rejected) {
               "those messages were not applied", rejected);
 }
 
+// a push into an evaluation-only model (psg_ftrl_import's weights-only form)
+int ftrl_unfrozen(Ftrl* F) {
+  if (F->frozen)
+    return fail(PSG_ERR_ARG, "the FTRL model is frozen: it was loaded by a weights-only import "
+                "(evaluation only), z is unknown and a push would recompute w from it");
+  return PSG_OK;
+}
+
+// pos, neg and z of an import: all given, or all null (the weights-only form)
+int import_form(const void* pos, const void* neg, const void* z, bool* weights_only) {
+  const int nulls = !pos + !neg + !z;
+  if (nulls != 0 && nulls != 3)
+    return fail(PSG_ERR_ARG, "FTRL import: pos, neg and z are all given or all NULL");
+  *weights_only = nulls == 3;
+  return PSG_OK;
+}
+
+// the device words and pinned host words of a state export
+constexpr int kStateWords = 20;  // h_small[20..23]: OR, AND, count, err
+
+// Step 1 of a state export on stream s: *blk (state_count_bytes) holds the
+// three device words and, from byte 64, the scan's tile sums; the host then
+// knows the count, the key bits that differ and the rejected messages.  Waits.
+size_t state_count_bytes(Ftrl* F) { return 64 + 4 * psg::ftrl_state_count_words(F->table()); }
+int state_count(psg_ctx* c, Ftrl* F, uint64_t lo, uint64_t hi, hipStream_t s, char** blk,
+                size_t* n, uint64_t* differ, unsigned long long* rejected) {
+  if (int rc = ftrl_order(F, s)) return rc;
+  if (int rc = c->dev_get(state_count_bytes(F), (void**)blk, s)) return rc;
+  unsigned long long* small = (unsigned long long*)*blk;
+  unsigned long long* h = c->h_small + kStateWords;
+  if (int rc = psg::launch_ftrl_state_count(F->table(), lo, hi, (uint32_t*)(*blk + 64), small, s))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(h, small, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h + 3, &F->d_head->err, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n = (size_t)(h[2] & 0xffffffffull);
+  *differ = h[0] ^ h[1];
+  *rejected = h[3];
+  return PSG_OK;
+}
+
+// a block used on stream s goes back to the pool, whose release events are
+// recorded on the context's stream: that stream first waits for the model's
+// last event (recorded on s after the block's last use)
+void state_put(psg_ctx* c, Ftrl* F, hipStream_t s, void* blk, size_t bytes) {
+  if (!blk) return;
+  if (s != c->stream && F->last) (void)hipStreamWaitEvent(c->stream, F->last, 0);
+  c->dev_put(blk, bytes);
+}
+
+// Step 2: the n entries of [lo, hi] sorted by key into device arrays.
+int state_emit(psg_ctx* c, Ftrl* F, uint64_t lo, uint64_t hi, size_t n, uint64_t differ,
+               const char* count_blk, uint64_t* keys, uint64_t* pos, uint64_t* neg, double* w,
+               double* z, hipStream_t s) {
+  if (n == 0) return PSG_OK;
+  const size_t wb = psg::ftrl_state_work_bytes(n);
+  void* work = nullptr;
+  if (int rc = c->dev_get(wb, &work, s)) return rc;
+  int rc = psg::launch_ftrl_state(F->table(), lo, hi, n, differ,
+                                  (const uint32_t*)(count_blk + 64), work, keys, pos, neg, w, z, s);
+  const int rm = ftrl_mark(c, F, s);
+  state_put(c, F, s, work, wb);
+  return rc ? rc : rm;
+}
+
+int state_range(const uint64_t* range, uint64_t* lo, uint64_t* hi) {
+  *lo = range ? range[0] : 0;
+  *hi = range ? range[1] : ~0ull;
+  if (*lo > *hi) return fail(PSG_ERR_ARG, "FTRL state export: range[0] > range[1]");
+  return PSG_OK;
+}
+
 }  // namespace
 
 int psg_ftrl_init(psg_ctx* c, const psg_ftrl_param* p, size_t capacity_hint) {
@@ -121,6 +193,7 @@ int psg_ftrl_push_dev(psg_ctx* c, const uint64_t* keys, size_t n, const uint32_t
   std::lock_guard<std::mutex> l(c->mu);
   Ftrl* F;
   if (int rc = ftrl_of(c, &F)) return rc;
+  if (int rc = ftrl_unfrozen(F)) return rc;
   if (n == 0) return PSG_OK;
   if (int rc = set_dev(c->device)) return rc;
   if (int rc = ftrl_room(c, F, n)) return rc;
@@ -135,6 +208,7 @@ int psg_ftrl_push(psg_ctx* c, const uint64_t* keys, size_t n, const uint32_t* po
   std::lock_guard<std::mutex> l(c->mu);
   Ftrl* F;
   if (int rc = ftrl_of(c, &F)) return rc;
+  if (int rc = ftrl_unfrozen(F)) return rc;
   if (n == 0) return PSG_OK;
   if (int rc = set_dev(c->device)) return rc;
   if (int rc = ftrl_room(c, F, n)) return rc;
@@ -245,6 +319,147 @@ int psg_ftrl_export(psg_ctx* c, uint64_t* keys, double* w, size_t cap, size_t* n
     HIP_TRY(hipMemcpyAsync(w, d_w, 8 * need, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
+  return ftrl_report(c, F, rejected);
+}
+
+int psg_ftrl_import_dev(psg_ctx* c, const uint64_t* keys, size_t n, const uint64_t* pos,
+                        const uint64_t* neg, const double* w, const double* z, void* stream) {
+  if (!c || (n && (!keys || !w))) return fail(PSG_ERR_ARG, "null argument");
+  bool weights_only;
+  if (int rc = import_form(pos, neg, z, &weights_only)) return rc;
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrl* F;
+  if (int rc = ftrl_of(c, &F)) return rc;
+  if (n == 0) {  // an empty weights-only import (w given) still freezes
+    if (weights_only && w) F->frozen = true;
+    return PSG_OK;
+  }
+  if (int rc = set_dev(c->device)) return rc;
+  if (int rc = ftrl_room(c, F, n)) return rc;
+  if (int rc = ftrl_order(F, (hipStream_t)stream)) return rc;
+  HIP_TRY(psg::launch_ftrl_import(F->table(), keys, pos, neg, w, z, n, (hipStream_t)stream));
+  if (weights_only) F->frozen = true;
+  return ftrl_mark(c, F, (hipStream_t)stream);
+}
+
+int psg_ftrl_import(psg_ctx* c, const uint64_t* keys, size_t n, const uint64_t* pos,
+                    const uint64_t* neg, const double* w, const double* z) {
+  if (!c || (n && (!keys || !w))) return fail(PSG_ERR_ARG, "null argument");
+  bool weights_only;
+  if (int rc = import_form(pos, neg, z, &weights_only)) return rc;
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrl* F;
+  if (int rc = ftrl_of(c, &F)) return rc;
+  if (n == 0) {  // an empty weights-only import (w given) still freezes
+    if (weights_only && w) F->frozen = true;
+    return PSG_OK;
+  }
+  if (int rc = set_dev(c->device)) return rc;
+  if (int rc = ftrl_room(c, F, n)) return rc;
+  // one staging block for the arrays, back to the pool after the kernels
+  const size_t kb = align_up(8 * n, 256), b = (weights_only ? 2 : 5) * kb;
+  char* blk = nullptr;
+  if (int rc = c->dev_get(b, (void**)&blk, c->copy)) return rc;
+  int rc = c->h2d(blk, keys, 8 * n);
+  if (rc == PSG_OK) rc = c->h2d(blk + kb, w, 8 * n);
+  if (rc == PSG_OK && !weights_only) rc = c->h2d(blk + 2 * kb, pos, 8 * n);
+  if (rc == PSG_OK && !weights_only) rc = c->h2d(blk + 3 * kb, neg, 8 * n);
+  if (rc == PSG_OK && !weights_only) rc = c->h2d(blk + 4 * kb, z, 8 * n);
+  if (rc == PSG_OK) rc = c->join_copy();
+  if (rc == PSG_OK) rc = ftrl_order(F, c->stream);
+  if (rc == PSG_OK) {
+    const hipError_t e = psg::launch_ftrl_import(
+        F->table(), (const uint64_t*)blk, weights_only ? nullptr : (const uint64_t*)(blk + 2 * kb),
+        weights_only ? nullptr : (const uint64_t*)(blk + 3 * kb), (const double*)(blk + kb),
+        weights_only ? nullptr : (const double*)(blk + 4 * kb), n, c->stream);
+    if (e != hipSuccess) rc = fail(PSG_ERR_DEVICE, "ftrl import: %s", hipGetErrorString(e));
+  }
+  if (rc == PSG_OK && weights_only) F->frozen = true;
+  if (rc == PSG_OK) rc = ftrl_mark(c, F, c->stream);
+  c->dev_put(blk, b);
+  const int rf = c->h2d_finish();
+  return rc ? rc : rf;
+}
+
+int psg_ftrl_frozen(psg_ctx* c, int* frozen) {
+  if (!c || !frozen) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrl* F;
+  if (int rc = ftrl_of(c, &F)) return rc;
+  *frozen = F->frozen ? 1 : 0;
+  return PSG_OK;
+}
+
+int psg_ftrl_export_state_dev(psg_ctx* c, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                              uint64_t* neg, double* w, double* z, size_t cap,
+                              unsigned long long* n_dev, void* stream) {
+  if (!c || !n_dev) return fail(PSG_ERR_ARG, "null argument");
+  uint64_t lo, hi;
+  if (int rc = state_range(range, &lo, &hi)) return rc;
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrl* F;
+  if (int rc = ftrl_of(c, &F)) return rc;
+  if (int rc = set_dev(c->device)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* cb = nullptr;
+  const size_t cbytes = state_count_bytes(F);
+  size_t n = 0;
+  uint64_t differ = 0;
+  unsigned long long rejected = 0;
+  int rc = state_count(c, F, lo, hi, s, &cb, &n, &differ, &rejected);
+  if (rc == PSG_OK && hipMemcpyAsync(n_dev, cb + 16, 8, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    rc = fail(PSG_ERR_DEVICE, "ftrl state export: count copy");
+  if (rc == PSG_OK && n > cap)
+    rc = fail(PSG_ERR_SIZE, "FTRL state export: %zu entries, room for %zu", n, cap);
+  else if (rc == PSG_OK)
+    rc = state_emit(c, F, lo, hi, n, differ, cb, keys, pos, neg, w, z, s);
+  const int rm = ftrl_mark(c, F, s);
+  state_put(c, F, s, cb, cbytes);
+  return rc ? rc : rm;
+}
+
+int psg_ftrl_export_state(psg_ctx* c, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                          uint64_t* neg, double* w, double* z, size_t cap, size_t* n_out) {
+  if (!c || !n_out) return fail(PSG_ERR_ARG, "null argument");
+  uint64_t lo, hi;
+  if (int rc = state_range(range, &lo, &hi)) return rc;
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrl* F;
+  if (int rc = ftrl_of(c, &F)) return rc;
+  if (int rc = set_dev(c->device)) return rc;
+  *n_out = 0;
+  hipStream_t s = c->stream;
+  char* cb = nullptr;
+  const size_t cbytes = state_count_bytes(F);
+  size_t n = 0;
+  uint64_t differ = 0;
+  unsigned long long rejected = 0;
+  int rc = state_count(c, F, lo, hi, s, &cb, &n, &differ, &rejected);
+  if (rc == PSG_OK) *n_out = n;
+  if (rc == PSG_OK && n > cap)
+    rc = fail(PSG_ERR_SIZE, "FTRL state export: %zu entries, room for %zu", n, cap);
+  void* const dst[5] = {keys, pos, neg, w, z};
+  const bool any = keys || pos || neg || w || z;
+  if (rc == PSG_OK && n && any) {
+    const size_t kb = align_up(8 * n, 256);
+    char* ob = nullptr;
+    rc = c->dev_get(5 * kb, (void**)&ob, s);
+    if (rc == PSG_OK) {
+      void* d[5];
+      for (int i = 0; i < 5; ++i) d[i] = dst[i] ? ob + i * kb : nullptr;
+      rc = state_emit(c, F, lo, hi, n, differ, cb, (uint64_t*)d[0], (uint64_t*)d[1],
+                      (uint64_t*)d[2], (double*)d[3], (double*)d[4], s);
+      for (int i = 0; i < 5 && rc == PSG_OK; ++i)
+        if (dst[i] &&
+            hipMemcpyAsync(dst[i], d[i], 8 * n, hipMemcpyDeviceToHost, s) != hipSuccess)
+          rc = fail(PSG_ERR_DEVICE, "ftrl state export: copy to the host");
+      if (hipStreamSynchronize(s) != hipSuccess && rc == PSG_OK)
+        rc = fail(PSG_ERR_DEVICE, "ftrl state export: wait");
+      c->dev_put(ob, 5 * kb);
+    }
+  }
+  c->dev_put(cb, cbytes);
+  if (rc != PSG_OK) return rc;
   return ftrl_report(c, F, rejected);
 }
 

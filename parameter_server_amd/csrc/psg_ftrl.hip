@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "psg_internal.h"
+#include "psg_sort.h"
 
 namespace psg {
 
@@ -398,9 +399,232 @@ __global__ __launch_bounds__(256) void ftrl_export_kernel(FtrlTable T, uint64_t*
   }
 }
 
-inline uint32_t blocks_of(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
+// ---- whole-entry import -----------------------------------------------------
+// Upsert of (key, pos, neg, w, z), one key per lane: the update kernel's
+// bucket walk and claim, then the entry replaced by plain stores (the order
+// check ran ahead on the same stream: one owner lane per entry).  pos, neg, z
+// null: the weights-only form, the entry becomes (0, 0, w, +0.0).  nnz moves
+// by (w_new != 0) - (w_old != 0) with ftrl_model.h:106-110's comparisons:
+// -0.0 is zero, a NaN weight is not.
+__global__ __launch_bounds__(256) void ftrl_import_kernel(FtrlTable T,
+                                                          const uint64_t* __restrict__ keys,
+                                                          const uint64_t* __restrict__ pos,
+                                                          const uint64_t* __restrict__ neg,
+                                                          const double* __restrict__ w,
+                                                          const double* __restrict__ z,
+                                                          uint64_t n) {
+  FtrlHead* head = T.head;
+  if (head->verdict) return;  // the message is rejected whole
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  long long d_entries = 0, d_nnz = 0;
+  if (i < n) {
+    const uint64_t key = keys[i];
+    FtrlEntry* e;
+    bool fresh;
+    if (key == 0) {  // at most one lane of the launch: the keys are unique
+      e = &head->side;
+      fresh = head->side_present == 0;
+      if (fresh) head->side_present = 1;
+    } else {
+      const uint64_t b = fmix64(key) & T.mask;
+      uint64_t k0[3];
+#pragma unroll
+      for (int s = 0; s < 3; ++s) k0[s] = T.b[b].e[s].key;
+      e = ftrl_claim(T, key, b, k0, &fresh);
+      if (!e) atomicAdd(&head->overflow, 1ull);
+    }
+    if (e) {
+      const double w_old = fresh ? 0.0 : e->w;
+      const double w_new = w[i];
+      e->pos = pos ? pos[i] : 0;
+      e->neg = neg ? neg[i] : 0;
+      e->w = w_new;
+      e->z = z ? z[i] : 0.0;
+      d_entries = fresh ? 1 : 0;
+      d_nnz = (w_new != 0 ? 1 : 0) - (w_old != 0 ? 1 : 0);
+    }
+  }
+  d_entries = wave_sum(d_entries);
+  d_nnz = wave_sum(d_nnz);
+  __shared__ long long part[4][2];
+  if ((threadIdx.x & 63) == 0) {
+    part[threadIdx.x >> 6][0] = d_entries;
+    part[threadIdx.x >> 6][1] = d_nnz;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int j = 1; j < 4; ++j) {
+      d_entries += part[j][0];
+      d_nnz += part[j][1];
+    }
+    unsigned long long* slot = head->slots + (blockIdx.x % kFtrlSlots) * 8;
+    if (d_entries)
+      __hip_atomic_fetch_add(slot, (unsigned long long)d_entries, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+    if (d_nnz)  // two's complement: the slots' sum is the signed total
+      __hip_atomic_fetch_add(slot + 1, (unsigned long long)d_nnz, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---- whole-state export -----------------------------------------------------
+// Element i < 3 * buckets of the flag scans is a table slot, element
+// 3 * buckets the side entry (key 0).  Flagged: occupied and lo <= key <= hi.
+struct StateFlag {
+  FtrlTable T;
+  uint64_t lo, hi;
+  uint32_t nslots;
+  __device__ bool key_of(uint32_t i, uint64_t* key) const {
+    if (i < nslots) {
+      *key = T.b[i / 3].e[i % 3].key;
+      return *key != 0;
+    }
+    *key = 0;
+    return T.head->side_present != 0;
+  }
+  __device__ bool operator()(uint32_t i) const {
+    uint64_t k;
+    return key_of(i, &k) && k >= lo && k <= hi;
+  }
+};
+
+// the compacted (key, slot id) of the flagged slots, in slot order
+struct StateEmit {
+  StateFlag f;
+  uint64_t* ckey;
+  uint32_t* cslot;
+  uint32_t cap;
+  __device__ void operator()(uint32_t i, uint32_t ex, bool flagged, uint32_t) const {
+    if (!flagged || ex >= cap) return;  // ex < cap always, by the count
+    uint64_t k;
+    (void)f.key_of(i, &k);
+    ckey[ex] = k;
+    cslot[ex] = i;
+  }
+};
+
+// orand[0] |= every flagged key, orand[1] &= every flagged key
+__global__ __launch_bounds__(256) void ftrl_state_bits_kernel(
+    StateFlag f, uint32_t n, unsigned long long* __restrict__ orand) {
+  uint64_t o = 0, a = ~0ull;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n;
+       i += (uint64_t)gridDim.x * 256u) {
+    uint64_t k;
+    if (f.key_of((uint32_t)i, &k) && k >= f.lo && k <= f.hi) {
+      o |= k;
+      a &= k;
+    }
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    o |= __shfl_xor(o, s, 64);
+    a &= __shfl_xor(a, s, 64);
+  }
+  if ((threadIdx.x & 63u) == 0 && (o | ~a)) {
+    atomicOr(orand, (unsigned long long)o);
+    atomicAnd(orand + 1, (unsigned long long)a);
+  }
+}
+
+// out[j] = the entry of the j-th key in key order: slot cslot[spos[j]]
+__global__ __launch_bounds__(256) void ftrl_state_gather_kernel(
+    FtrlTable T, uint32_t nslots, const uint64_t* __restrict__ skey,
+    const uint32_t* __restrict__ spos, const uint32_t* __restrict__ cslot, uint32_t n,
+    uint64_t* __restrict__ keys, uint64_t* __restrict__ pos, uint64_t* __restrict__ neg,
+    double* __restrict__ w, double* __restrict__ z) {
+  const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  if (j >= n) return;
+  const uint32_t at = spos[j];
+  if (at >= n) return;  // never: a permutation of 0 .. n-1
+  const uint32_t i = cslot[at];
+  if (i > nslots) return;  // never
+  const FtrlEntry* e = i < nslots ? &T.b[i / 3].e[i % 3] : &T.head->side;
+  if (keys) keys[j] = skey[j];
+  if (pos) pos[j] = e->pos;
+  if (neg) neg[j] = e->neg;
+  if (w) w[j] = e->w;
+  if (z) z[j] = e->z;
+}
+
+constexpr uint32_t kStateGridCap = 2048;
+
+// the blocks of launch_ftrl_state's work area for n entries
+struct StateWork {
+  size_t ckey, key_a, key_b, cslot, pos_a, pos_b, counts, dtotal, end;
+  explicit StateWork(uint64_t n) {
+    const size_t k8 = (size_t)(8 * n + 255) & ~(size_t)255, k4 = (size_t)(4 * n + 255) & ~(size_t)255;
+    ckey = 0;
+    key_a = ckey + k8;
+    key_b = key_a + k8;
+    cslot = key_b + k8;
+    pos_a = cslot + k4;
+    pos_b = pos_a + k4;
+    counts = pos_b + k4;
+    dtotal = counts + 4 * 256 * (size_t)blocks_of(n, kSortTile);
+    end = dtotal + 4 * 256;
+  }
+};
 
 }  // namespace
+
+hipError_t launch_ftrl_import(const FtrlTable& T, const uint64_t* keys, const uint64_t* pos,
+                              const uint64_t* neg, const double* w, const double* z, uint64_t n,
+                              hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(&T.head->verdict, 0, 8, s);
+  if (e != hipSuccess) return e;
+  if (n > 1)
+    hipLaunchKernelGGL(ftrl_check_kernel, dim3(blocks_of(n - 1, 256)), dim3(256), 0, s, keys, n,
+                       T.head);
+  hipLaunchKernelGGL(ftrl_import_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, T, keys, pos,
+                     neg, w, z, n);
+  return hipGetLastError();
+}
+
+size_t ftrl_state_count_words(const FtrlTable& T) {
+  return blocks_of(3 * (T.mask + 1) + 1, kFlagTile);
+}
+
+int launch_ftrl_state_count(const FtrlTable& T, uint64_t lo, uint64_t hi, uint32_t* tile_sum,
+                            unsigned long long* small, hipStream_t s) {
+  const uint64_t nel = 3 * (T.mask + 1) + 1;
+  if (nel > 0xffffffffull) return fail(PSG_ERR_SIZE, "FTRL state export: %llu slots >= 2^32",
+                                        (unsigned long long)nel);
+  const StateFlag f{T, lo, hi, (uint32_t)(nel - 1)};
+  const unsigned long long init[3] = {0, ~0ull, 0};
+  HIP_TRY(hipMemcpyAsync(small, init, sizeof init, hipMemcpyHostToDevice, s));
+  const uint32_t nt = blocks_of(nel, kFlagTile);
+  LAUNCH(flag_count_kernel<StateFlag>, nt, s, f, (uint32_t)nel, tile_sum);
+  LAUNCH(row_scan_kernel, 1, s, tile_sum, nt, (uint32_t*)(small + 2));
+  LAUNCH(ftrl_state_bits_kernel, std::min(blocks_of(nel, 256), kStateGridCap), s, f,
+         (uint32_t)nel, small);
+  return launched("ftrl state count");
+}
+
+size_t ftrl_state_work_bytes(uint64_t n) { return StateWork(n).end; }
+
+int launch_ftrl_state(const FtrlTable& T, uint64_t lo, uint64_t hi, uint64_t n, uint64_t differ,
+                      const uint32_t* tile_base, void* work, uint64_t* keys, uint64_t* pos,
+                      uint64_t* neg, double* w, double* z, hipStream_t s) {
+  if (n == 0) return PSG_OK;
+  const uint64_t nel = 3 * (T.mask + 1) + 1;
+  const StateWork W(n);
+  char* base = (char*)work;
+  uint64_t* ckey = (uint64_t*)(base + W.ckey);
+  uint32_t* cslot = (uint32_t*)(base + W.cslot);
+  const StateFlag f{T, lo, hi, (uint32_t)(nel - 1)};
+  const StateEmit em{f, ckey, cslot, (uint32_t)n};
+  LAUNCH((flag_emit_kernel<StateFlag, StateEmit>), blocks_of(nel, kFlagTile), s, f, em,
+         (uint32_t)nel, tile_base);
+  const SortBuffers sb{(uint64_t*)(base + W.key_a), (uint64_t*)(base + W.key_b),
+                       (uint32_t*)(base + W.pos_a), (uint32_t*)(base + W.pos_b),
+                       (uint32_t*)(base + W.counts), (uint32_t*)(base + W.dtotal)};
+  const uint64_t* skey = nullptr;
+  const uint32_t* spos = nullptr;
+  if (int rc = enqueue_radix_sort(ckey, (uint32_t)n, differ, sb, &skey, &spos, s)) return rc;
+  LAUNCH(ftrl_state_gather_kernel, blocks_of(n, 256), s, T, (uint32_t)(nel - 1), skey, spos,
+         cslot, (uint32_t)n, keys, pos, neg, w, z);
+  return launched("ftrl state export");
+}
 
 hipError_t launch_ftrl_push(const FtrlTable& T, const uint64_t* keys, const uint32_t* pos,
                             const uint32_t* neg, const double* grad, uint64_t n,

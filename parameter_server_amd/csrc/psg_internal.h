@@ -322,6 +322,26 @@ hipError_t launch_ftrl_norm(const FtrlTable& T, hipStream_t stream);
 // cap of them; head->res[4] = their count
 hipError_t launch_ftrl_export(const FtrlTable& T, uint64_t* keys, double* w, uint64_t cap,
                               hipStream_t stream);
+// one import message: order check, then the upsert of whole entries, which
+// applies nothing unless the check passed (a rejected message also counts in
+// head->err).  pos, neg, z all null: the entries become (0, 0, w, +0.0).
+hipError_t launch_ftrl_import(const FtrlTable& T, const uint64_t* keys, const uint64_t* pos,
+                              const uint64_t* neg, const double* w, const double* z, uint64_t n,
+                              hipStream_t stream);
+// Whole-state export, in two steps with a host read between them (the sort's
+// launch shape needs the count).  Both return a psg status.
+// step 1: small[0] / small[1] = OR / AND of the keys of the occupied slots
+// with lo <= key <= hi (0 / ~0 if none), the low half of small[2] = their
+// count; tile_sum (ftrl_state_count_words(T) words) is kept for step 2.
+size_t ftrl_state_count_words(const FtrlTable& T);
+int launch_ftrl_state_count(const FtrlTable& T, uint64_t lo, uint64_t hi, uint32_t* tile_sum,
+                            unsigned long long* small, hipStream_t stream);
+// step 2: those n entries sorted by key into the five arrays (any may be
+// null); differ = small[0] ^ small[1]; work: ftrl_state_work_bytes(n) bytes
+size_t ftrl_state_work_bytes(uint64_t n);
+int launch_ftrl_state(const FtrlTable& T, uint64_t lo, uint64_t hi, uint64_t n, uint64_t differ,
+                      const uint32_t* tile_sum, void* work, uint64_t* keys, uint64_t* pos,
+                      uint64_t* neg, double* w, double* z, hipStream_t stream);
 
 // snappy raw-format decompression (psg_snappy.hip), one wave per message:
 // part i -> dst + doff[i], of dcap[i] bytes (dcap NULL: doff[i+1] - doff[i]).

@@ -7,6 +7,12 @@ src/linear_method/ftrl_model.h:12-69) method for method --
 ``psg_ftrl_*`` (include/psg.h, which also lists the defined deviations: a
 pull does not insert, the norms are a reduction, a message must be strictly
 increasing, the dump is sorted by key).
+
+Checkpoint and restore fill the hooks the reference leaves empty
+(``setReplica`` / ``getReplica`` / ``recoverFrom``, ftrl_model.h:41-44):
+``state`` / ``restore`` move whole entries, ``save`` / ``load`` keep them in
+one ``.npz``, and ``read_model_text`` / ``readFromFile`` are the model load of
+``ModelEvaluation::run`` (model_evaluation.h:16-27).
 """
 from __future__ import annotations
 
@@ -25,6 +31,86 @@ def format_weight(w: float) -> str:
     """A double as the reference's ``out << w`` prints it (default ostream
     precision: printf %g, 6 significant digits)."""
     return "%g" % w
+
+
+def read_model_text(paths, real=np.float64):
+    """The model files ``ModelEvaluation::run`` loads (reference
+    src/linear_method/model_evaluation.h:16-27), on the host: whitespace
+    separated ``key value`` pairs read as ``in >> k >> v``, a later pair
+    overriding an earlier one within a file and across files (``weight[k] =
+    v``).  Returns (sorted unique keys as uint64, their weights as float64).
+    ``real=np.float32`` rounds each weight through ``float`` first, as the
+    reference's ``Real`` does.  A trailing unpaired token, a key that is no
+    uint64 and a value that is no number are errors.
+
+    Defined deviation: after the last line of a file the reference's loop
+    runs once more with a failed extraction and assigns ``weight[0]`` from it
+    (model_evaluation.h:22-26: ``in.good()`` is still true after the last
+    newline), so every loaded model there holds a key 0.  We do not add it."""
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        paths = [paths]
+    real = np.dtype(real)
+    if real not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError(f"real must be float64 or float32, not {real}")
+    keys, vals = [], []
+    for path in paths:
+        with open(path, "r") as f:
+            toks = f.read().split()
+        if len(toks) % 2:
+            raise ValueError(f"{path}: a key without a value ({toks[-1]!r})")
+        for k in toks[0::2]:
+            v = int(k) if k.isascii() and k.isdigit() else -1
+            if not 0 <= v < (1 << 64):
+                raise ValueError(f"{path}: {k!r} is no uint64 key")
+            keys.append(v)
+        try:
+            vals.extend(float(v) for v in toks[1::2])
+        except ValueError:
+            raise ValueError(f"{path}: a value that is no number") from None
+    k = np.array(keys, dtype=np.uint64)
+    w = np.array(vals, dtype=np.float64).astype(real).astype(np.float64)
+    # the last pair of each key: the first of the reversed list
+    u, first = np.unique(k[::-1], return_index=True)
+    return u, np.ascontiguousarray(w[::-1][first])
+
+
+STATE_VERSION = 1
+_STATE_ARRAYS = (("keys", np.uint64), ("pos", np.uint64), ("neg", np.uint64),
+                 ("w", np.float64), ("z", np.float64))
+_STATE_PARAMS = ("alpha", "beta", "lambda1", "lambda2")
+
+
+def save_state(path, keys, pos, neg, w, z, alpha, beta, lambda1, lambda2, frozen=False,
+               **extra) -> None:
+    """One ``.npz`` at exactly ``path``: the five arrays of a model's image
+    (``FTRLModel.state``), its four parameters as float64, ``frozen``, the
+    format version, and the caller's ``extra`` arrays."""
+    arrays = {name: np.ascontiguousarray(a, dtype=dt)
+              for (name, dt), a in zip(_STATE_ARRAYS, (keys, pos, neg, w, z))}
+    if len({a.size for a in arrays.values()}) != 1:
+        raise ValueError("the five arrays of a model image have one length")
+    for name, v in zip(_STATE_PARAMS, (alpha, beta, lambda1, lambda2)):
+        arrays[name] = np.array(v, dtype=np.float64)
+    arrays["frozen"] = np.array(1 if frozen else 0, dtype=np.int64)
+    arrays["format_version"] = np.array(STATE_VERSION, dtype=np.int64)
+    for name, v in extra.items():
+        if name in arrays:
+            raise ValueError(f"{name} is a field of the format")
+        arrays[name] = np.asarray(v)
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def load_state(path) -> dict:
+    """The fields ``save_state`` wrote, by name; rejects any other version."""
+    with np.load(path, allow_pickle=False) as f:
+        if "format_version" not in f.files:
+            raise ValueError(f"{path}: no FTRL model image (no format_version)")
+        version = int(f["format_version"])
+        if version != STATE_VERSION:
+            raise ValueError(f"{path}: format version {version}, this reader knows "
+                             f"{STATE_VERSION}")
+        return {name: f[name] for name in f.files}
 
 
 class FTRLModel:
@@ -154,6 +240,81 @@ class FTRLModel:
             _lib.check(self._L.psg_ftrl_lookup(self._model(), _ptr(k), k.size, _ptr(pos),
                                                _ptr(neg), _ptr(w), _ptr(z), _ptr(found)))
         return pos, neg, w, z, found
+
+    # -- checkpoint: the hooks ftrl_model.h:41-44 leaves empty ----------------
+    def state(self, range=None):
+        """getReplica: (keys, pos, neg, w, z) of every entry whose key lies in
+        the closed interval ``range = (first, last)`` (None: all), sorted by
+        key on the device (psg_ftrl_export_state)."""
+        r = None
+        if range is not None:
+            r = (C.c_uint64 * 2)(int(range[0]), int(range[1]))
+        n = C.c_size_t()
+        rc = self._L.psg_ftrl_export_state(self._model(), r, None, None, None, None, None, 0,
+                                           C.byref(n))
+        if rc not in (_lib.PSG_OK, _lib.PSG_ERR_SIZE):
+            _lib.check(rc)
+        out = [np.empty(n.value, dt) for _, dt in _STATE_ARRAYS]
+        if n.value:
+            _lib.check(self._L.psg_ftrl_export_state(self._h, r, *[_ptr(a) for a in out],
+                                                     n.value, C.byref(n)))
+        return tuple(out)
+
+    def restore(self, keys, pos=None, neg=None, w=None, z=None) -> None:
+        """recoverFrom / setReplica: an upsert of whole entries, strictly
+        increasing by key (psg_ftrl_import).  ``pos``, ``neg`` and ``z`` all
+        None: the weights-only form, which freezes the model."""
+        if w is None:
+            raise _lib.PSGError(_lib.PSG_ERR_ARG, "restore needs the weights")
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        rest = [None if a is None else np.ascontiguousarray(a, dtype=dt)
+                for a, dt in ((pos, np.uint64), (neg, np.uint64), (z, np.float64))]
+        for a in [w] + [a for a in rest if a is not None]:
+            if a.size != keys.size:
+                raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"{a.size} values for {keys.size} keys")
+        p = [None if a is None else _ptr(a) for a in rest]
+        _lib.check(self._L.psg_ftrl_import(self._model(), _ptr(keys), keys.size, p[0], p[1],
+                                           _ptr(w), p[2]))
+
+    @property
+    def frozen(self) -> bool:
+        """Evaluation only: loaded by a weights-only import (psg_ftrl_frozen)."""
+        f = C.c_int()
+        _lib.check(self._L.psg_ftrl_frozen(self._model(), C.byref(f)))
+        return bool(f.value)
+
+    def save(self, path, **extra) -> None:
+        """The model's image, parameters and ``extra`` arrays in one ``.npz``
+        (``save_state``)."""
+        frozen = self.frozen
+        save_state(path, *self.state(), self._alpha, self._beta, self._lambda1, self._lambda2,
+                   frozen=frozen, **extra)
+
+    @classmethod
+    def from_state(cls, st: dict, device: int = 0, flags: int = 0) -> "FTRLModel":
+        """A model holding what ``load_state`` read.  The parameters come back
+        by bits; a frozen model comes back through the weights-only import,
+        frozen."""
+        m = cls(device, capacity_hint=int(st["keys"].size), flags=flags)
+        m._alpha, m._beta, m._lambda1, m._lambda2 = (float(st[k]) for k in _STATE_PARAMS)
+        if int(st["frozen"]):
+            m.restore(st["keys"], w=st["w"])
+        else:
+            m.restore(st["keys"], st["pos"], st["neg"], st["w"], st["z"])
+        m._model()
+        return m
+
+    @classmethod
+    def load(cls, path, device: int = 0) -> "FTRLModel":
+        return cls.from_state(load_state(path), device)
+
+    def readFromFile(self, paths, real=np.float64) -> None:
+        """The first half of ModelEvaluation::run (model_evaluation.h:16-27):
+        ``read_model_text`` of the files, then the weights-only import.  The
+        model is evaluation-only afterwards: pulls work, pushes are refused."""
+        keys, w = read_model_text(paths, real)
+        self.restore(keys, w=w)
 
     def writeToFile(self, path: str) -> None:
         """One ``key\\tw`` line per nonzero weight, sorted by key (the

@@ -21,7 +21,8 @@ from typing import Tuple
 import numpy as np
 
 from . import _lib
-from .ftrl import FTRLModel
+from .auc import exact_auc
+from .ftrl import FTRLModel, load_state
 from .kv_vector import _ptr
 
 # psg_mb_read's arrays: name -> (id, dtype)
@@ -232,6 +233,9 @@ class FTRLWorker:
         self._ctx = model._model()
         self.freq = int(tail_feature_freq)
         self.chl = chl
+        # CountMin::resize's n_ and k_ (countmin.h:14-19)
+        self.countmin_n = max(int(countmin_n), 64)
+        self.countmin_k = min(30, max(1, int(countmin_k)))
         if self.freq > 0:
             _lib.check(self._L.psg_freq_resize(self._ctx, chl, countmin_n, countmin_k))
         self.mb = Minibatch(self._ctx)
@@ -324,3 +328,79 @@ class FTRLWorker:
 
     def last_w(self) -> np.ndarray:
         return self.mb.read_scratch(self._W, np.float64, self.ndict).copy()
+
+    # -- checkpoint ----------------------------------------------------------
+    def freq_table(self) -> np.ndarray:
+        """The tail filter's CountMin counters (psg_freq_table)."""
+        out = np.zeros(self.countmin_n, np.uint8)
+        _lib.check(self._L.psg_freq_table(self._ctx, self.chl, _ptr(out), out.size))
+        return out
+
+    def save(self, path) -> None:
+        """Everything the next step depends on, in one ``.npz``
+        (``ftrl.save_state``): the model's image and parameters, ``objv`` and
+        ``num_ex``, and with the tail filter on its threshold and the CountMin
+        table with its ``n`` and ``k``."""
+        extra = dict(objv=np.array(self.objv, np.float64), num_ex=np.array(self.num_ex, np.int64),
+                     tail_feature_freq=np.array(self.freq, np.int64))
+        if self.freq > 0:
+            extra.update(countmin_n=np.array(self.countmin_n, np.int64),
+                         countmin_k=np.array(self.countmin_k, np.int64),
+                         countmin_table=self.freq_table())
+        self.model.save(path, **extra)
+
+    @classmethod
+    def load(cls, path, device: int = 0, chl: int = 0) -> "FTRLWorker":
+        """A worker, with a model of its own, that goes on where ``save``
+        stopped: the same steps give the same bits."""
+        st = load_state(path)
+        if "tail_feature_freq" not in st:
+            raise ValueError(f"{path}: a model image without a worker's state")
+        freq = int(st["tail_feature_freq"])
+        model = FTRLModel.from_state(st, device)
+        if freq > 0:
+            wk = cls(model, freq, int(st["countmin_n"]), int(st["countmin_k"]), chl)
+            table = np.ascontiguousarray(st["countmin_table"], dtype=np.uint8)
+            _lib.check(wk._L.psg_freq_table_assign(wk._ctx, chl, _ptr(table), table.size))
+        else:
+            wk = cls(model, chl=chl)
+        wk.objv = float(st["objv"])
+        wk.num_ex = int(st["num_ex"])
+        return wk
+
+
+def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device: int = 0,
+                   real=np.float32):
+    """ModelEvaluation::run (reference src/linear_method/model_evaluation.h):
+    the ``key w`` model files loaded into a frozen model (``readFromFile``;
+    ``real``: the reference's ``Real`` is float), the text walked minibatch by
+    minibatch of ``max_rows`` examples (:42: 100000) with ``predict_text``,
+    ``y`` and ``Xw`` of each appended (:44,59), then the exact AUC of all of
+    them (:66).  Returns (auc, labels, predictions).
+
+    Defined deviation: a prediction is accumulated in double by the ordered
+    product (one row's terms in the row's order), where the reference adds
+    floats (``Real re``, :49-57)."""
+    model = FTRLModel(device)
+    wk = None
+    try:
+        model.readFromFile(model_paths, real=real)
+        wk = FTRLWorker(model)
+        text = bytes(text)
+        labels, predictions = [], []
+        at = 0
+        while at < len(text):
+            _, consumed = wk.predict_text(text[at:], fmt, max_rows)
+            if wk.mb.rows:
+                labels.append(wk.mb.read("y"))
+                predictions.append(wk.mb.read("xw"))
+            if consumed == 0:
+                break
+            at += consumed
+        y = np.concatenate(labels) if labels else np.zeros(0, np.float64)
+        xw = np.concatenate(predictions) if predictions else np.zeros(0, np.float64)
+        return exact_auc(model._h, y, xw), y, xw
+    finally:
+        if wk is not None:
+            wk.close()
+        model.close()
