@@ -85,6 +85,7 @@ typedef enum psg_dtype { PSG_F32 = 0, PSG_F64 = 1 } psg_dtype;
 #define PSG_NO_INDEX 0x100000u    /* plan: no resident bucket index (tables built per run) */
 #define PSG_FORM_CURSOR 0x400000u /* plan: a cursor form (no partition pass) where it applies */
 #define PSG_NO_CURSOR 0x800000u   /* plan: never a cursor form (the default) */
+#define PSG_NO_HINTS 0x1000000u   /* plan: the search partition never tries the last run's cuts first */
 /* Plan option (psg_plan_create): the caller promises that the push KEYS at
  * the job's device pointers stay as they were at creation for the plan's
  * lifetime (values may change between runs).  Only then may the plan take
@@ -289,7 +290,11 @@ typedef struct psg_plan psg_plan;
  * are misplaced and show up as unmatched in psg_plan_matched.  To merge
  * against a different D, create a new plan (or pass PSG_NO_INDEX, which
  * rebuilds the tables from D in every run).  Push keys and values may
- * change between runs (see PSG_STATIC_KEYS for the one exception). */
+ * change between runs (see PSG_STATIC_KEYS for the one exception).  A run
+ * whose push keys repeat the previous run's is cheaper: the search partition
+ * first checks the cuts that run left behind, each against its two
+ * neighbouring keys, and searches only where one no longer holds (off:
+ * PSG_NO_HINTS; the results are the same either way). */
 int psg_plan_create(int device, int dtype, int m, unsigned flags,
                     const psg_merge_job* jobs, int njobs, psg_plan** out);
 int psg_plan_max_push(void);
@@ -318,6 +323,14 @@ int psg_plan_bytes(psg_plan* plan, uint64_t* bytes, uint64_t* kv_pairs);
  * server slot of every tile, and the tiles whose table is not stored (a
  * bucket of more than 14 keys), which the kernels build on every run. */
 int psg_plan_index_info(psg_plan* plan, uint64_t* index_bytes, uint64_t* marked_tiles);
+/* How the search partition's waves stand after the plan's last run
+ * (synchronises it): counts[0] waves whose last run searched and whose next
+ * run tests the cuts it left, counts[1] waves that search without testing
+ * (most of their cuts failed the test; they test again once a search returns
+ * the old cuts), counts[2] waves whose last run kept every cut, counts[3]
+ * waves that have not run.  All zero for a plan without hints (PSG_NO_HINTS,
+ * no search-mode job). */
+int psg_plan_hint_state(psg_plan* plan, uint64_t counts[4]);
 int psg_plan_destroy(psg_plan* plan);
 
 /* Device-resident gather (pull reply) over resident keys/values. */

@@ -56,6 +56,7 @@ PSG_NO_INDEX = 0x100000
 PSG_STATIC_KEYS = 0x200000
 PSG_FORM_CURSOR = 0x400000
 PSG_NO_CURSOR = 0x800000
+PSG_NO_HINTS = 0x1000000
 # psg_plan_form: the aggregate kernel a plan runs
 (PSG_KERNEL_TILE, PSG_KERNEL_TILE64, PSG_KERNEL_PACKED, PSG_KERNEL_DENSE, PSG_KERNEL_CURSOR,
  PSG_KERNEL_PACKED_CURSOR) = range(6)
@@ -160,6 +161,7 @@ SIGNATURES = {
     "psg_plan_bytes": (C.c_int, [_p, _pu64, _pu64]),
     "psg_plan_form": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "psg_plan_index_info": (C.c_int, [_p, _pu64, _pu64]),
+    "psg_plan_hint_state": (C.c_int, [_p, _pu64]),
     "psg_plan_destroy": (C.c_int, [_p]),
     "psg_gather_dev": (C.c_int, [C.c_int, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     "psg_key_union_dev": (C.c_int, [_p, _u64, _p, _u64, _p, _pu64, _p]),

@@ -120,9 +120,17 @@ struct DenseCheck {
 // items (u64: job << 37 | push << 24 | boundary group or chunk)
 // xcd: deal the items to the XCDs in contiguous runs (launches whose jobs are
 // all search mode)
+// hstate (plans; null: every cut is searched): one u32 per item, kHintFresh
+// at the build; the search-mode jobs' seg arrays then hold defined values
+// (zeroes, or the cuts of an earlier launch), tried before searching
+// (psg_partition.hip search_item)
+// a wave's state: its last run searched / it searches without testing / its
+// last run kept every cut / it has not run yet
+enum : uint32_t { kHintSearched = 0, kHintOff = 1, kHintKept = 2, kHintFresh = 3 };
 hipError_t launch_partition(const JobDev* d_jobs, const uint32_t* d_split_item_job,
                             uint32_t nsplit_items, const uint64_t* d_items,
-                            uint32_t nitems, hipStream_t stream, bool xcd = false);
+                            uint32_t nitems, hipStream_t stream, bool xcd = false,
+                            uint32_t* hstate = nullptr);
 // aggregate: one workgroup per tile of kTileSlots slots.  psg_tile.hip:
 // every round holds one push (long pieces); psg_tile_packed.hip: rounds may
 // hold several pushes (many short pieces)

@@ -233,6 +233,8 @@ void JobImage::layout(const JobSpec* jobs, uint32_t iw) {
     o.dpos = off;
     if (jobs[j].dense) off = align_up(off + 8 * np, 256);
   }
+  L.hstate = off;
+  if (hints) off = align_up(off + 4 * (size_t)nitems, 256);
   L.total = off;
 }
 
@@ -269,10 +271,14 @@ int JobImage::fill(const JobSpec* jobs, char* img, const void* dev, bool same) {
   const size_t njobs = h.size();
   // only the region the kernels expect zeroed (fail counters, cursor
   // boundary words): every other field of the image is written below, or
-  // (seg, splitters, bucket index) by a kernel before any read.  Zeroing
+  // (seg, splitters, bucket index) by a kernel before any read -- but for
+  // the seg of a hinted plan's search-mode jobs, which the first run reads
+  // as the cuts to try (zeroed per job below, once per plan).  Zeroing
   // the whole image cost ~0.1 ms per flush of a 16.8 M-slot aggregate
   if (L.zero_end > L.zero) memset(img + L.zero, 0, L.zero_end - L.zero);
   if (use_index()) memset(img + L.marked, 0, 8);
+  if (hints)
+    for (uint32_t i = 0; i < nitems; ++i) ((uint32_t*)(img + L.hstate))[i] = kHintFresh;
   TileDesc* htiles = (TileDesc*)(img + L.tiles);
   uint32_t* hsitems = (uint32_t*)(img + L.sitems);
   uint64_t* hitems = (uint64_t*)(img + L.items);
@@ -307,6 +313,8 @@ int JobImage::fill(const JobSpec* jobs, char* img, const void* dev, bool same) {
     }
     memcpy(img + o.out, s.out.data(), 8 * m);
     JobDev& d = h[j];
+    if (hints && nt && !s.dense && d.mode == kSearch)
+      memset(img + o.seg, 0, 4 * ((size_t)nt + 1) * np);
     d.dkeys = s.keys;
     d.pkeys = (const uint64_t* const*)(base + o.pk);
     d.pn = (const uint64_t*)(base + o.pn);

@@ -60,6 +60,7 @@ struct JobLayout {
   size_t zero = 0, bx = 0, zero_end = 0;
   struct Job { size_t pk, pv, pn, out, fail, seg, split, dpos; };
   std::vector<Job> job;
+  size_t hstate = 0;                 // hinted plans: one u32 per partition item (kHint*)
   size_t total = 0;
   uint32_t iw = 0;                   // bucket index words per tile
 };
@@ -85,6 +86,10 @@ struct JobImage {
   uint32_t ckr = 3;            // rounds per push per tile (max over the jobs)
   uint32_t ntiles = 0, nitems = 0, nsplit = 0;
   bool all_search = false;  // every job's partition searches (launch_partition xcd)
+  // plans (seg lives as long as the plan, zeroed at the build): the search
+  // partition tries the cuts the last run left before it searches
+  // (psg_partition.hip search_item; off: PSG_NO_HINTS)
+  bool hints = false;
   std::vector<JobDev> h;
   std::vector<JobInfo> info;
   JobLayout lay;

@@ -32,6 +32,7 @@ struct JobTable : JobImage {
   CursorJob* d_cjobs = nullptr;
   CursorChunk* d_chunks = nullptr;
   uint32_t* d_bx = nullptr;   // chunk boundary words
+  uint32_t* d_hstate = nullptr;  // hinted plans: the waves' hint states (psg_internal.h kHint*)
   void* d_zero = nullptr;     // fail counters of every job + boundary words: zeroed per run
   size_t zero_bytes = 0;
   // pinned host images of the blob, used alternately: a build fills one

@@ -160,6 +160,7 @@ int JobTable::build(int dev, int dt, int mm, const std::vector<JobSpec>& jobs, h
   d_cjobs = cursor ? (CursorJob*)(base + lay.cjobs) : nullptr;
   d_chunks = chunked ? (CursorChunk*)(base + lay.chunks) : nullptr;
   d_bx = chunked ? (uint32_t*)(base + lay.bx) : nullptr;
+  d_hstate = hints && nitems ? (uint32_t*)(base + lay.hstate) : nullptr;
   d_zero = base + lay.zero;
   zero_bytes = lay.zero_end - lay.zero;
   if (int rc = upload(ib, same, strm)) return rc;
@@ -192,7 +193,7 @@ int JobTable::run_stage(int stage, hipStream_t s) const {
       HIP_TRY(hipMemsetAsync(d_zero, 0, zero_bytes, s));
     else if (!dense)
       HIP_TRY(launch_partition(d_jobs, d_split_items, split_once ? 0u : nsplit, d_items, nitems, s,
-                               all_search));
+                               all_search, d_hstate));
   } else if (cursor)
     HIP_TRY(launch_aggregate_cursor(dtype, m, (int)ckr, d_cjobs, d_chunks, nchunks, d_bx, s));
   else if (dense)

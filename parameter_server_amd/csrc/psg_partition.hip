@@ -60,35 +60,77 @@ using dev::bracket_lower_bound;
 // A wave holds 64 consecutive boundaries of one push.  Every 16th lane and
 // the last search the whole push; the lanes between start from the bracket
 // their neighbours' answers give (about 16 tiles' worth of the push instead
-// of all of it), which saves probe lines per boundary (the partition is
-// bound by the random lines it reads).  A bracket that does
-// not hold (an unsorted push) falls back to the whole push.
-__device__ __forceinline__ void search_item(const JobDev& J, uint32_t p, uint32_t g, int lane) {
+// of all of it), which shortens their chain of dependent probes (the
+// partition is bound by the length of each lane's chain of dependent loads,
+// not by the lines it touches).  A bracket that does not hold
+// (an unsorted push) falls back to the whole push.
+//
+// Hints (`ws` non-null: plans, whose seg outlives a run): the cut the
+// previous run left in seg is tried first.  c == lower_bound(S, x) for a
+// sorted push exactly when (c == 0 || S[c-1] < x) && (c == n || S[c] >= x),
+// so a lane whose old cut passes that test keeps it, and a wave whose lanes
+// all pass is done after the header loads and one round of key loads -- the
+// usual case where a push's key list repeats from run to run.  The old cut
+// is loaded with the header and S[c-1], S[c] with S[0], S[n-1], so a wave
+// that misses searches as before, no dependent round trip later.  Whatever
+// seg held (zeroes after the build, a cut of other keys), the cuts of a
+// sorted push come out the same; of an unsorted push a kept cut may differ
+// from the search's, which the aggregate kernel's own order check does not
+// depend on.
+//
+// A miss costs one more random line per boundary, so every wave keeps a
+// word of its own in the plan (*ws, read with the item; one owner, so plain
+// loads and stores): kHintFresh (the build) and kHintOff skip the test and
+// its loads and search; a tested run in which more than half of the wave's
+// boundaries missed goes to kHintOff; a kHintOff run whose searched cuts all
+// equal the old ones (the keys repeat again) goes back to testing.
+// (the states: psg_internal.h)
+
+__device__ __forceinline__ void search_item(const JobDev& J, uint32_t p, uint32_t g, int lane,
+                                            uint32_t* ws) {
+  const uint32_t st = ws ? uni(*ws) : 0u;
+  const bool test = ws && (st == kHintSearched || st == kHintKept);
   const uint32_t b = (g << 6) + (uint32_t)lane;
   const bool valid = b <= J.ntiles;
   const uint64_t* S = J.pkeys[p];
   const uint64_t n = J.pn[p];
   const uint32_t bc = valid ? b : J.ntiles;
   const bool up = bc == J.ntiles;
+  uint32_t* sg = J.seg + ((size_t)p * J.segq + (size_t)bc * J.segb);
+  // the old cut: tested, or (kHintOff) only compared with the new one
+  const uint64_t old = ws && st != kHintFresh ? (uint64_t)*sg : ~0ull;
   // boundary key: lower_bound(D[bc * tile]); past the last tile
   // upper_bound(D[nslots - 1]) == lower_bound(D[nslots - 1] + 1) (D never
   // holds 2^64-1) -- exactly the splitter array a plan writes once
   const uint64_t xl = J.split ? J.split[bc]
                       : up ? J.dkeys[J.nslots - 1] + 1ull : J.dkeys[(uint64_t)bc * J.tile];
   const uint64_t k0 = S[0], kn = S[n - 1];
+  // the old cut's two neighbours, in the round trip of S[0] and S[n-1]
+  // (old > n: not a cut of this push, nothing is read)
+  const bool inb = test && old <= n;
+  const uint64_t kl = inb && old > 0 ? S[old - 1] : 0ull;
+  const uint64_t kh = inb && old < n ? S[old] : 0ull;
+  const bool hit = inb && (old == 0 || kl < xl) && (old == n || kh >= xl);
+  if (test && __all(hit)) {  // seg already holds every cut of the wave
+    if (valid && b == 0) J.fail[p] = 0ull;
+    if (st != kHintKept && lane == 0) *ws = kHintKept;
+    return;
+  }
   // the wave's last valid lane (invalid lanes repeat boundary ntiles)
   const int last = (int)((J.ntiles - (g << 6)) < 63u ? (J.ntiles - (g << 6)) : 63u);
   // bracketing lanes: every 16th and the last valid one
   const bool edge = (lane & 15) == 0 || lane == last;
   const int lo_l = lane & ~15;
   const int hi_l = lo_l + 16 < last ? lo_l + 16 : last;
-  uint64_t res = 0;
-  if (edge) {
+  // lanes whose old cut held sit the searches out; edge lanes among them
+  // still supply it to the shuffles
+  uint64_t res = hit ? old : 0;
+  if (edge && !hit) {
     res = xl <= k0 ? 0 : (xl > kn ? n : bracket_lower_bound(S, xl, 0, n - 1, k0, kn));
   }
   const uint64_t r0 = (uint64_t)__shfl((long long)res, lo_l, 64);
   const uint64_t r1 = (uint64_t)__shfl((long long)res, hi_l, 64);
-  if (!edge) {
+  if (!edge && !hit) {
     if (xl <= k0) {
       res = 0;
     } else if (xl > kn) {
@@ -106,8 +148,18 @@ __device__ __forceinline__ void search_item(const JobDev& J, uint32_t p, uint32_
     }
   }
   if (valid) {
-    J.seg[(size_t)p * J.segq + (size_t)b * J.segb] = (uint32_t)res;
+    if (!hit) *sg = (uint32_t)res;
     if (b == 0) J.fail[p] = 0ull;  // the aggregate launch follows in-stream
+  }
+  if (ws) {
+    uint32_t nw = kHintSearched;  // after the first run: test the next one
+    if (test) {
+      const uint32_t missed = (uint32_t)__popcll(__ballot(valid && !hit));
+      nw = 2u * missed > (uint32_t)last + 1u ? kHintOff : kHintSearched;
+    } else if (st == kHintOff) {
+      nw = __all(!valid || res == old) ? kHintSearched : kHintOff;
+    }
+    if (nw != st && lane == 0) *ws = nw;
   }
 }
 
@@ -254,7 +306,7 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
 
 __global__ __launch_bounds__(256) void partition_kernel(const JobDev* __restrict__ jobs,
                                                         const uint64_t* __restrict__ items,
-                                                        uint32_t nitems, int xcd) {
+                                                        uint32_t nitems, int xcd, uint32_t* hstate) {
   __shared__ uint64_t ck[4][kStreamChunk];
   const uint32_t blk = xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
   const uint32_t item = uni((blk * 256u + threadIdx.x) >> 6);
@@ -268,20 +320,20 @@ __global__ __launch_bounds__(256) void partition_kernel(const JobDev* __restrict
   if (J.mode == kStream)
     stream_item(J, p, x, lane, ck[threadIdx.x >> 6]);
   else
-    search_item(J, p, x, lane);
+    search_item(J, p, x, lane, hstate ? hstate + item : nullptr);
 }
 
 }  // namespace
 
 hipError_t launch_partition(const JobDev* d_jobs, const uint32_t* d_split_item_job,
                             uint32_t nsplit_items, const uint64_t* d_items, uint32_t nitems,
-                            hipStream_t stream, bool xcd) {
+                            hipStream_t stream, bool xcd, uint32_t* hstate) {
   if (nsplit_items)
     hipLaunchKernelGGL(splitter_kernel, dim3(nsplit_items), dim3(256), 0, stream, d_jobs,
                        d_split_item_job, nsplit_items);
   if (nitems)
     hipLaunchKernelGGL(partition_kernel, dim3((nitems + 3) / 4), dim3(256), 0, stream, d_jobs,
-                       d_items, nitems, xcd ? 1 : 0);
+                       d_items, nitems, xcd ? 1 : 0, hstate);
   return hipGetLastError();
 }
 

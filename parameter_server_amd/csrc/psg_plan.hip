@@ -51,6 +51,7 @@ int psg_plan_create(int device, int dtype, int m, unsigned flags,
     if (int rc = detect_dense(specs)) return rc;
   psg_plan* p = new psg_plan();
   p->table.read_knobs(flags);
+  p->table.hints = !(flags & PSG_NO_HINTS);
   int rc = p->table.build(device, dtype, m, specs, nullptr, false, !(flags & PSG_NO_INDEX));
   if (rc) {
     p->table.release();
@@ -101,6 +102,22 @@ int psg_plan_index_info(psg_plan* plan, uint64_t* index_bytes, uint64_t* marked_
   if (!plan) return fail(PSG_ERR_ARG, "null plan");
   if (index_bytes) *index_bytes = plan->table.index_bytes;
   if (marked_tiles) *marked_tiles = plan->table.marked_tiles;
+  return PSG_OK;
+}
+
+int psg_plan_hint_state(psg_plan* plan, uint64_t counts[4]) {
+  if (!plan || !counts) return fail(PSG_ERR_ARG, "null argument");
+  const JobTable& T = plan->table;
+  for (int i = 0; i < 4; ++i) counts[i] = 0;
+  if (!T.d_hstate) return PSG_OK;
+  if (int rc = set_dev(T.device)) return rc;
+  HIP_TRY(hipStreamSynchronize(plan->last));
+  std::vector<uint32_t> st(T.nitems);
+  HIP_TRY(hipMemcpy(st.data(), T.d_hstate, 4 * (size_t)T.nitems, hipMemcpyDeviceToHost));
+  size_t i = 0;  // a job's items are consecutive
+  for (size_t j = 0; j < T.h.size(); ++j)
+    for (uint32_t k = 0; k < T.info[j].nitems; ++k, ++i)
+      if (T.h[j].mode == psg::kSearch) counts[st[i] & 3u]++;
   return PSG_OK;
 }
 

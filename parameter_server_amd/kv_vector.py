@@ -287,6 +287,13 @@ class MergePlan:
         """0 = partition, 1 = aggregate (the dominant kernel)."""
         _lib.check(self._L.psg_plan_run_stage(self._h, stage, stream or None))
 
+    def hint_state(self) -> List[int]:
+        """Search-partition waves by state after the last run: [searched,
+        searching without the test, kept every cut, not run yet]."""
+        c = (C.c_uint64 * 4)()
+        _lib.check(self._L.psg_plan_hint_state(self._h, c))
+        return list(c)
+
     def matched(self) -> np.ndarray:
         out = np.zeros(max(1, self.npush_total), np.uint64)
         _lib.check(self._L.psg_plan_matched(

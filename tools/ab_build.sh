@@ -14,9 +14,10 @@ if [ -n "$REV" ]; then
 else
   SRC=$R/parameter_server_amd/csrc
 fi
-for f in $SRC/*.hip; do
+for f in $SRC/*.hip $SRC/*.cc; do  # the .cc are host-only sources of the library (csrc/Makefile)
+  o=$(basename $f); o=${o%.hip}; o=${o/%.cc/.host}
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-flush-denormals-to-zero \
-    -ffp-contract=off $F -c $f -o $O/$(basename $f .hip).o &
+    -ffp-contract=off $F -c $f -o $O/$o.o &
 done
 wait
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $O/libpsg.so $O/*.o -L/opt/rocm/lib -lrccl
