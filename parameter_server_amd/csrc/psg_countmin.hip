@@ -128,13 +128,10 @@ __host__ __device__ constexpr uint32_t ins_block_keys(int k) {
   return k <= 4 ? 8192u : k <= 8 ? 4096u : k <= 16 ? 2048u : 1024u;
 }
 
-// XCD-contiguous runs of consecutive indices (blocks b and b + 8 share an
-// XCD: observed dispatch, speed only): neighbouring regions' record runs
-// share lines, read once per XCD this way
-__device__ __forceinline__ uint32_t xcd_index(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
+// XCD-contiguous runs of consecutive regions: neighbouring regions' record
+// runs share lines, read once per XCD this way
+using dev::u32x4;
+using dev::xcd_index;
 
 // bin: block b's keys [b*KB, ...): their probes' records (offset | count
 // << 15) region-sorted at R[b*KB*k ...), region starts S[b*(nreg+1) + r]
@@ -531,7 +528,6 @@ __global__ __launch_bounds__(kQNT) void cm_qlook_kernel(const uint8_t* __restric
   const uint32_t r0 = r * kQRegBytes;
   const uint32_t rbytes = tb - r0 < kQRegBytes ? tb - r0 : kQRegBytes;  // a multiple of 4
   {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const uint32_t nq = rbytes / 16u;
     const u32x4* src = (const u32x4*)(table + r0);
     for (uint32_t i = t; i < nq; i += kQNT) *(u32x4*)&tab[4 * i] = __builtin_nontemporal_load(src + i);

@@ -20,7 +20,7 @@
 namespace psg {
 namespace {
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+using dev::u32x4;
 
 template <typename T>
 __device__ __forceinline__ void copy_elems(const char* __restrict__ s, char* __restrict__ d,
@@ -45,10 +45,10 @@ __global__ __launch_bounds__(256) void intake_kernel(IntakeArgs a) {
     const uint64_t n16 = vec ? len / 16 : 0, done = 16 * n16;
     if (a.esz[c] == 8) copy_elems<uint64_t>(s + done, d + done, (len - done) / 8, tid, stride);
     else copy_elems<uint32_t>(s + done, d + done, (len - done) / 4, tid, stride);
-    const u32x4_t* __restrict__ sv = (const u32x4_t*)s;
-    u32x4_t* __restrict__ dv = (u32x4_t*)d;
+    const u32x4* __restrict__ sv = (const u32x4*)s;
+    u32x4* __restrict__ dv = (u32x4*)d;
     for (uint64_t u = tid; u < n16; u += 4 * stride) {
-      u32x4_t v[4];
+      u32x4 v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (u + j * stride < n16) v[j] = __builtin_nontemporal_load(sv + u + j * stride);

@@ -32,14 +32,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psg_device.h"
 #include "psg_internal.h"
 
 namespace psg {
 
 namespace {
 
-__device__ __forceinline__ double dmin(double a, double b) { return b < a ? b : a; }  // std::min
-__device__ __forceinline__ double dmax(double a, double b) { return a < b ? b : a; }  // std::max
+using dev::std_max;
+using dev::std_min;
 
 __device__ __forceinline__ unsigned long long wave_max(unsigned long long v) {
   for (int s = 32; s >= 1; s >>= 1) {
@@ -94,8 +95,8 @@ __global__ __launch_bounds__(256) void darling_kernel(const double* __restrict__
         d = -g_neg / u;
       }
       const double dk = delta[k];
-      d = dmin(dk, dmax(-dk, d));
-      delta[k] = dmin(P.delta_max, 2 * fabs(d) + .1);
+      d = std_min(dk, std_max(-dk, d));
+      delta[k] = std_min(P.delta_max, 2 * fabs(d) + .1);
       wk += d;
       w[k] = wk;
     }

@@ -1,10 +1,117 @@
-// psg_device.h -- device helpers shared by the gfx950 kernels.
+// psg_device.h -- device helpers shared by the gfx950 kernels: the one
+// definition of each leaf primitive.  Kernel files pull
+// the names in inside their anonymous namespace and do not redefine them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#define AS1 __attribute__((address_space(1)))
+
 namespace psg {
 namespace dev {
+
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// global (not flat) accesses: a flat access also counts on lgkmcnt, so a
+// kernel's LDS waits would wait for its loads in flight too
+template <typename T>
+__device__ __forceinline__ const AS1 T* G(const T* p) {
+  return (const AS1 T*)p;
+}
+template <typename T>
+__device__ __forceinline__ AS1 T* GW(T* p) {
+  return (AS1 T*)p;
+}
+
+// a wave-uniform value into scalar registers
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+  return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
+}
+
+// the lane index recomputed from nothing (mbcnt over a full mask), so a value
+// needed late in the kernel does not keep the thread-id register live (at 64
+// VGPRs it is the value that would be spilled to scratch: HBM writes)
+__device__ __forceinline__ uint32_t lane_id() {
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+}
+
+// std::min(a, b) / std::max(a, b) as <algorithm> defines them: b < a ? b : a
+// and a < b ? b : a.  Not fmin / fmax: a NaN first argument stays a NaN, as
+// in the reference.
+__device__ __forceinline__ double std_min(double a, double b) { return b < a ? b : a; }
+__device__ __forceinline__ double std_max(double a, double b) { return a < b ? b : a; }
+
+// blocks b and b+8 share an XCD (observed dispatch, speed only): block b of n
+// takes index xcd_index(b, n), which gives each XCD a contiguous run of
+// indices (tiles, chunks), so the cache lines two neighbours share are read
+// once.  A permutation of [0, n).
+__host__ __device__ constexpr __forceinline__ uint32_t xcd_index(uint32_t b, uint32_t n) {
+  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
+  return x * q + (x < r ? x : r) + j;
+}
+constexpr bool xcd_index_permutes(uint32_t n) {  // n <= 64
+  uint64_t seen = 0;
+  for (uint32_t b = 0; b < n; ++b) {
+    const uint32_t i = xcd_index(b, n);
+    if (i >= n || (seen >> i & 1u)) return false;
+    seen |= 1ull << i;
+  }
+  return true;
+}
+// every remainder edge r = n & 7
+static_assert(xcd_index_permutes(1) && xcd_index_permutes(7) && xcd_index_permutes(8) &&
+                  xcd_index_permutes(9) && xcd_index_permutes(15) && xcd_index_permutes(16) &&
+                  xcd_index_permutes(17) && xcd_index_permutes(64),
+              "xcd_index: a permutation of [0, n)");
+
+// inclusive 64-lane prefix sum by DPP (row shifts, then row broadcasts):
+// immediate lane controls, so no per-lane shuffle addresses stay live (the
+// __shfl_up form kept six address VGPRs alive across the kernel and spilled
+// them at 8 waves/SIMD)
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);  // row_shr:1
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);  // row_shr:2
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);  // row_shr:4
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);  // row_shr:8
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
+  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
+  return x;
+}
+
+// 16 B per lane from global memory straight into LDS (gfx950 LDS-DMA): lane l
+// writes lds + 16 l; nontemporal (the tile kernels' D is read by one tile)
+// Issued by inline asm (M0 saved and restored, as the compiler reserves it):
+// the builtin form made the compiler's wait-count pass wait for the DMA at
+// the next reuse of its address registers, i.e. right after issuing it.  The
+// compiler does not see these loads, so readers of the LDS they fill wait
+// for them explicitly (dma_wait); its own vmcnt waits stay correct, only
+// more conservative (the DMAs are older than its loads).
+typedef __attribute__((address_space(3))) void* LdsPtr;
+__device__ __forceinline__ void dma16(const void* g, void* lds) {
+  const uint32_t la = (uint32_t)(uintptr_t)(LdsPtr)lds;
+  uint32_t keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+      "global_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(g), "s"(la)
+      : "memory");
+}
+__device__ __forceinline__ void dma_wait() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+// a workgroup barrier that makes LDS writes visible but leaves vector-memory
+// operations (LDS-DMA, loads) in flight: __syncthreads() would wait for them
+// (its release fence waits vmcnt(0) while an LDS-DMA is pending)
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0); vmcnt and expcnt not waited for
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
 
 // ----------------------------------------------------------------------
 // wave-cooperative k-ary search: first index i in [0, n) whose key
@@ -188,33 +295,19 @@ struct BucketIndexWords {
 
 template <int kNB>
 __device__ __forceinline__ BucketIndexWords<kNB> bucket_index_load(const uint32_t* ix, int lane) {
-  typedef uint32_t v2 __attribute__((ext_vector_type(2)));
-  typedef uint32_t v4 __attribute__((ext_vector_type(4)));
   BucketIndexWords<kNB> r;
   if constexpr (kNB == 1024) {
-    const v2 a = __builtin_nontemporal_load(
-        (const __attribute__((address_space(1))) v2*)ix + lane);
+    const u32x2 a = __builtin_nontemporal_load((const AS1 u32x2*)ix + lane);
     r.x[0] = a.x; r.x[1] = a.y;
   } else {
 #pragma unroll
     for (int i = 0; i < kNB / 2048; ++i) {
-      const v4 a = __builtin_nontemporal_load(
-          (const __attribute__((address_space(1))) v4*)ix + lane * (kNB / 2048) + i);
+      const u32x4 a =
+          __builtin_nontemporal_load((const AS1 u32x4*)ix + lane * (kNB / 2048) + i);
       r.x[4 * i] = a.x; r.x[4 * i + 1] = a.y; r.x[4 * i + 2] = a.z; r.x[4 * i + 3] = a.w;
     }
   }
   return r;
-}
-
-// inclusive 64-lane prefix sum by DPP (row shifts, then row broadcasts)
-__device__ __forceinline__ uint32_t wave_scan_incl_dpp(uint32_t x) {
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);  // row_shr:1
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);  // row_shr:2
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);  // row_shr:4
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);  // row_shr:8
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return x;
 }
 
 // Called by every lane of ONE wave with the words of bucket_index_load:
@@ -227,7 +320,6 @@ __device__ __forceinline__ uint32_t wave_scan_incl_dpp(uint32_t x) {
 template <int kNB>
 __device__ __forceinline__ void bucket_index_decode(const BucketIndexWords<kNB>& ix,
                                                     uint32_t* bt32, uint32_t nt, int lane) {
-  typedef uint32_t v4 __attribute__((ext_vector_type(4)));
   constexpr int W = kNB / 512;
   const bool marked = ((uint32_t)__builtin_amdgcn_readfirstlane((int)ix.x[0]) & 15u) == 15u;
   // per word, on packed bytes (8 counts <= 14: sums below 256): ev/od byte j
@@ -242,17 +334,17 @@ __device__ __forceinline__ void bucket_index_decode(const BucketIndexWords<kNB>&
     before[i] = tot;
     tot += s >> 24;
   }
-  const uint32_t off = wave_scan_incl_dpp(tot) - tot;
+  const uint32_t off = wave_scan_incl(tot) - tot;
 #pragma unroll
   for (int i = 0; i < W; ++i) {
     const uint32_t base = (off + before[i]) * 0x00010001u;  // starts <= nt < 2^16: no carry
-    v4 o;
+    u32x4 o;
     o.x = ((ev[i] & 0xffu) | (od[i] & 0xffu) << 16) + base;
     o.y = ((ev[i] >> 8 & 0xffu) | (od[i] >> 8 & 0xffu) << 16) + base;
     o.z = ((ev[i] >> 16 & 0xffu) | (od[i] >> 16 & 0xffu) << 16) + base;
     o.w = ((ev[i] >> 24) | (od[i] >> 24) << 16) + base;
-    if (marked) o = v4{0u, 0u, 0u, 0u};
-    *(v4*)&bt32[4 * (lane * W + i)] = o;
+    if (marked) o = u32x4{0u, 0u, 0u, 0u};
+    *(u32x4*)&bt32[4 * (lane * W + i)] = o;
   }
   if (lane == 0) bt32[kNB / 2] = nt | (marked ? 0x10000u : 0u);
 }
@@ -277,7 +369,6 @@ __device__ __forceinline__ V fold_step(V acc, int lp, int p, V v,
   }
   return acc + v;
 }
-
 
 }  // namespace dev
 }  // namespace psg

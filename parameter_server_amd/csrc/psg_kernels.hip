@@ -197,15 +197,14 @@ __global__ __launch_bounds__(256) void pull_kernel(
 // a DMA copy's fixed cost (tools/calib/hostbw.py: 1 MB 47 vs 38 GB/s,
 // 512 KB 40 vs 28 GB/s), and one launch carries a flush's worth of them.
 // Both ends 16-B aligned (the runtime checks).
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void host_copy_kernel(HostCopyBatch b) {
   const uint64_t stride = (uint64_t)gridDim.x * 256u;
   for (uint32_t c = 0; c < b.n; ++c) {
-    const u32x4_t* __restrict__ s = (const u32x4_t*)b.d[c].src;
-    u32x4_t* __restrict__ d = (u32x4_t*)b.d[c].dst;
+    const u32x4* __restrict__ s = (const u32x4*)b.d[c].src;
+    u32x4* __restrict__ d = (u32x4*)b.d[c].dst;
     const uint64_t n16 = b.d[c].len / 16;
     for (uint64_t u = (uint64_t)blockIdx.x * 256u + threadIdx.x; u < n16; u += 4 * stride) {
-      u32x4_t v[4];
+      u32x4 v[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (u + j * stride < n16) v[j] = __builtin_nontemporal_load(s + u + j * stride);
@@ -234,7 +233,6 @@ __global__ __launch_bounds__(256) void check_sorted_kernel(
 // or, for lane 0, from one 8-B load.  Keys 16-B aligned (the runtime checks).
 __global__ __launch_bounds__(256) void check_sorted_host_kernel(
     const uint64_t* __restrict__ k, uint64_t n, unsigned long long* bad) {
-  typedef unsigned long long u64x2_t __attribute__((ext_vector_type(2)));
   const uint64_t n2 = n / 2;  // whole units
   const uint64_t stride = (uint64_t)gridDim.x * 256u;
   const int lane = threadIdx.x & 63;
@@ -242,8 +240,8 @@ __global__ __launch_bounds__(256) void check_sorted_host_kernel(
   // every lane of a wave runs the same iterations (u0 is wave-uniform)
   for (uint64_t u0 = (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u); u0 < n2; u0 += stride) {
     const uint64_t u = u0 + (uint64_t)lane;
-    u64x2_t v = {0ull, 0ull};
-    if (u < n2) v = __builtin_nontemporal_load((const u64x2_t*)k + u);
+    u64x2 v = {0ull, 0ull};
+    if (u < n2) v = __builtin_nontemporal_load((const u64x2*)k + u);
     uint64_t prev = (uint64_t)__shfl_up((long long)v.y, 1, 64);
     if (lane == 0 && u > 0) prev = k[2 * u - 1];
     if (u < n2) cnt += (v.x < v.y ? 0u : 1u) + ((u > 0 && !(prev < v.x)) ? 1u : 0u);

@@ -63,19 +63,11 @@ constexpr int kPer = 8;             // merged elements per thread
 constexpr int kCap = kNT * kPer;    // elements per tile (LDS)
 constexpr int kMaxRuns = 64;        // pushes per merge (runs per tile)
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// global (not flat) accesses: a flat access also counts on lgkmcnt, so the
-// LDS waits of the rank and tile stages would wait for loads in flight too
-#define AS1 __attribute__((address_space(1)))
-template <typename T>
-__device__ __forceinline__ const AS1 T* G(const T* p) {
-  return (const AS1 T*)p;
-}
-template <typename T>
-__device__ __forceinline__ AS1 T* GW(T* p) {
-  return (AS1 T*)p;
-}
+// G / GW: global (not flat) accesses, so the LDS waits of the rank and tile
+// stages do not wait for loads in flight too
+using dev::G;
+using dev::GW;
+using dev::uni;
 
 struct NwArgs {
   const uint64_t* const* keys;  // [K] push keys

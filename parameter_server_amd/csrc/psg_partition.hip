@@ -31,10 +31,9 @@ namespace psg {
 
 namespace {
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
-}
+using dev::uni;
+using dev::uni64;
+using dev::xcd_index;
 
 // ---- kStream jobs: splitters and the reset of the job's fail counters ----
 __global__ __launch_bounds__(256) void splitter_kernel(const JobDev* __restrict__ jobs,
@@ -293,22 +292,16 @@ __device__ __forceinline__ void stream_item(const JobDev& J, uint32_t p, uint32_
   if (c == 0 && lane == 0) J.fail[p] = 0ull;
 }
 
-// blocks b and b+8 share an XCD (observed dispatch, speed only).  `xcd`: each
-// XCD takes a contiguous run of items, so neighbouring boundary groups of one
-// push, whose probes touch the same lines, share one L2 -- for launches of
-// search-mode jobs only (r06: cfg2 / cfg3 partition -2..-4 %; stream-mode
-// chunks read their keys once and lost 5 % that way,
-// profiles/r06_ab_partition_xcd.txt)
-__device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
-
+// `xcd` (dev::xcd_index): each XCD takes a contiguous run of items, so
+// neighbouring boundary groups of one push, whose probes touch the same
+// lines, share one L2 -- for launches of search-mode jobs only (r06: cfg2 /
+// cfg3 partition -2..-4 %; stream-mode chunks read their keys once and lost
+// 5 % that way, profiles/r06_ab_partition_xcd.txt)
 __global__ __launch_bounds__(256) void partition_kernel(const JobDev* __restrict__ jobs,
                                                         const uint64_t* __restrict__ items,
                                                         uint32_t nitems, int xcd, uint32_t* hstate) {
   __shared__ uint64_t ck[4][kStreamChunk];
-  const uint32_t blk = xcd ? xcd_block(blockIdx.x, gridDim.x) : blockIdx.x;
+  const uint32_t blk = xcd ? xcd_index(blockIdx.x, gridDim.x) : blockIdx.x;
   const uint32_t item = uni((blk * 256u + threadIdx.x) >> 6);
   const int lane = threadIdx.x & 63;
   if (item >= nitems) return;

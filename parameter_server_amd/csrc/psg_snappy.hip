@@ -39,9 +39,9 @@
 #include <stdint.h>
 
 #include "../../include/psg.h"
+#include "psg_device.h"
 #include "psg_internal.h"
 
-#define AS1 __attribute__((address_space(1)))
 #ifndef PSG_SNAPPY_IR
 #define PSG_SNAPPY_IR 2  // few-part launches: 2 = the table form, 1 = the streamed form (A/B), 0 = snappy_kernel
 #endif
@@ -52,6 +52,8 @@
 namespace psg {
 
 namespace {
+
+using dev::u32x4;
 
 #ifdef PSG_SNAPPY_PROF
 // diagnostic build only (tools/snappy_prof.py): per part, shader clocks in
@@ -241,7 +243,6 @@ __global__ __launch_bounds__(64) void snappy_kernel(const uint8_t* __restrict__ 
     // flight at once; bytes at the ends one per lane
     const bool out16 = ((uintptr_t)out & 15u) == 0u;
     auto flush_range = [&](uint32_t a, uint32_t b) {
-      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
       uint32_t a16 = a, b16 = a;
       if (out16 && b - a >= 256u) {
         a16 = (a + 15u) & ~15u;
@@ -471,12 +472,12 @@ constexpr uint32_t kSB = 16u << 10;     // output stage bytes
 constexpr uint32_t kMaxSt = 512;        // staged elements
 constexpr uint32_t kIRBigLit = 512;     // literals deferred to the copy kernel
 
-typedef __attribute__((address_space(3))) void* LdsPtr;
 // 16 B per lane from global memory into LDS: lane l writes lds + 16 l (M0
 // saved and restored; the compiler does not see the load, every reader
 // waits for it explicitly)
+// a near copy of dev::dma16 (no nt, a readfirstlane): sharing that one changes this file's code
 __device__ __forceinline__ void ir_dma16(const void* g, const void* lds) {
-  const uint32_t la = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(LdsPtr)lds);
+  const uint32_t la = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(dev::LdsPtr)lds);
   uint32_t keep;
   asm volatile(
       "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
@@ -905,13 +906,12 @@ constexpr uint32_t kTabPend = 64;
 constexpr uint32_t kTabBigLit = 512;
 constexpr int kTabDepth = 4;
 constexpr uint32_t kCopyBit = 0x80000000u;
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 struct TabLds {
   // element i: x = output position (rec[nel].x = the part's length), y =
   // literal: input position / copy: offset, z = length (| kCopyBit for a
   // copy), w = literal: deferred index (~0: moved in step 2) / copy: 1 =
   // unresolved
-  u32x4_t rec[kTabMax + 1];
+  u32x4 rec[kTabMax + 1];
   uint32_t nel, verdict, base, npend;
 };
 union SnappyTabLds {
@@ -1032,7 +1032,7 @@ __global__ __launch_bounds__(256) void snappy_tab_kernel(const uint8_t* __restri
       // 64 at a time
       uint32_t rx = 0, ry = 0, rz = 0, rw = 0;
       auto flush_recs = [&](uint32_t n0, uint32_t cnt) {
-        if (lane < cnt) *(u32x4_t*)&T.rec[n0 + lane] = u32x4_t{rx, ry, rz, rw};
+        if (lane < cnt) *(u32x4*)&T.rec[n0 + lane] = u32x4{rx, ry, rz, rw};
       };
       while (!st && p < e) {
         if (n == kTabMax) {
@@ -1321,13 +1321,12 @@ __global__ __launch_bounds__(256) void snappy_lit_kernel(const SnappyLit* __rest
         uint32_t xw[5];
 #pragma unroll
         for (int i = 0; i < 5; ++i) xw[i] = wp[i];
-        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-        u4 v;
+        u32x4 v;
         v.x = __builtin_amdgcn_alignbyte(xw[1], xw[0], sh);
         v.y = __builtin_amdgcn_alignbyte(xw[2], xw[1], sh);
         v.z = __builtin_amdgcn_alignbyte(xw[3], xw[2], sh);
         v.w = __builtin_amdgcn_alignbyte(xw[4], xw[3], sh);
-        *(u4*)ua = v;
+        *(u32x4*)ua = v;
       } else {
         for (uintptr_t b = b0b; b < b1; ++b) *(uint8_t*)b = L.src[b - (uintptr_t)L.dst];
       }

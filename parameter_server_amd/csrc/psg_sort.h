@@ -2,15 +2,16 @@
 // psg_auc.hip: the stable 8-bit LSD radix passes over 64-bit keys with a
 // 32-bit payload (DESIGN.md 4.8 a), the count / scan / emit of a flag over a
 // sorted array (4.8 b), the binary search and the wave's fold of a run's
-// labels.  It stands alone: the sort's shape is defined here, once, and
-// psg_mb_sort_tile() reports it; tests/worker_ref.py mirrors it.  Kernels
-// are file-local in each translation unit that includes this (anonymous
-// namespace).
+// labels.  It stands alone (but for psg_device.h's block map): the sort's
+// shape is defined here, once, and psg_mb_sort_tile() reports it;
+// tests/worker_ref.py mirrors it.  Kernels are file-local in each
+// translation unit that includes this (anonymous namespace).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/psg.h"
+#include "psg_device.h"
 #include "psg_host.h"
 
 #ifndef PSG_SORT_KPT
@@ -25,13 +26,10 @@ constexpr uint32_t kSortTile = 256 * kSortKPT;   // pairs per workgroup
 constexpr uint32_t kWaveSpan = 64 * kSortKPT;    // pairs per wave
 constexpr uint32_t kFlagTile = 2048;             // elements per workgroup of the flag scans
 
-// XCD-contiguous runs of consecutive tiles (as psg_countmin.hip): tiles next
-// to each other write next to each other in every digit's output range, and
-// their partial lines meet in one XCD's L2
-__device__ __forceinline__ uint32_t xcd_index(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
+// XCD-contiguous runs of consecutive tiles: tiles next to each other write
+// next to each other in every digit's output range, and their partial lines
+// meet in one XCD's L2
+using dev::xcd_index;
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
   for (uint32_t s = 1; s < 64; s <<= 1) {

@@ -43,7 +43,6 @@
 #include "psg_device.h"
 #include "psg_internal.h"
 
-#define AS1 __attribute__((address_space(1)))
 #ifndef KCAP64
 #define KCAP64 7
 #endif
@@ -67,14 +66,7 @@ __device__ uint32_t g_phase[kPhTiles][8];
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ const AS1 T* G(const T* p) {
-  return (const AS1 T*)p;
-}
-template <typename T>
-__device__ __forceinline__ AS1 T* GW(T* p) {
-  return (AS1 T*)p;
-}
+using namespace dev;
 
 // Two forms, by pushes per group (one lane of wave 0 each):
 //   32 pushes: 1024-slot tiles, 256 threads;
@@ -90,74 +82,12 @@ constexpr int nb_of(int g) { return ts_of(g); }
 constexpr int cb_of(int g) { return ts_of(g) / 64 > 16 ? 5 : 4; }  // round-chunk bits
 static_assert(ts_of(64) <= 0x7ffe, "u16 positions");
 
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
-}
-
 #ifndef PSG_FUSECNT
 #define PSG_FUSECNT 1  // A/B builds: 0 = sums and contributor counts in separate arrays
 #endif
 #ifndef PSG_DDMA
-#define PSG_DDMA 1  // A/B builds: 0 = D through registers
+#define PSG_DDMA 1  // A/B builds: 0 = D through registers (else dev::dma16, LDS-DMA)
 #endif
-// 16 B per lane from global memory straight into LDS (gfx950 LDS-DMA): lane l
-// writes lds + 16 l; nontemporal (D is read by one tile)
-// Issued by inline asm (M0 saved and restored, as the compiler reserves it):
-// the builtin form made the compiler's wait-count pass wait for the DMA at
-// the next reuse of its address registers, i.e. right after issuing it.  The
-// compiler does not see these loads, so readers of the LDS they fill wait
-// for them explicitly (dma_wait); its own vmcnt waits stay correct, only
-// more conservative (the DMAs are older than its loads).
-typedef __attribute__((address_space(3))) void* LdsPtr;
-__device__ __forceinline__ void dma16(const void* g, void* lds) {
-  const uint32_t la = (uint32_t)(uintptr_t)(LdsPtr)lds;
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g), "s"(la)
-      : "memory");
-}
-__device__ __forceinline__ void dma_wait() {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-// a workgroup barrier that makes LDS writes visible but leaves vector-memory
-// operations (LDS-DMA, loads) in flight: __syncthreads() would wait for them
-// (its release fence waits vmcnt(0) while an LDS-DMA is pending)
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0); vmcnt and expcnt not waited for
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// blocks b and b+8 share an XCD (observed dispatch, speed only): give each
-// XCD a contiguous run of tiles
-__device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
-
-// inclusive 64-lane prefix sum by DPP (row shifts, then row broadcasts):
-// immediate lane controls, so no per-lane shuffle addresses stay live (the
-// __shfl_up form kept six address VGPRs alive across the kernel and spilled
-// them at 8 waves/SIMD)
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);  // row_shr:1
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);  // row_shr:2
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);  // row_shr:4
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);  // row_shr:8
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return x;
-}
-
 
 // workgroups per CU the LDS allows (8 for the f32, m = 1 headline case):
 // the register budget follows it through __launch_bounds__
@@ -218,7 +148,7 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
   const uint32_t w = uni((uint32_t)threadIdx.x >> 6);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const uint32_t ti = xcd_tile(blockIdx.x, gridDim.x);
+  const uint32_t ti = xcd_index(blockIdx.x, gridDim.x);
   if (ti >= ntiles) return;
 #ifdef PSG_PHASES
   unsigned long long ph_t = clock64();

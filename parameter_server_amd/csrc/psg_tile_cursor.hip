@@ -38,20 +38,11 @@
 #include "psg_device.h"
 #include "psg_internal.h"
 
-#define AS1 __attribute__((address_space(1)))
-
 namespace psg {
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ const AS1 T* G(const T* p) {
-  return (const AS1 T*)p;
-}
-template <typename T>
-__device__ __forceinline__ AS1 T* GW(T* p) {
-  return (AS1 T*)p;
-}
+using namespace dev;
 
 constexpr int kTS = kTileSlots;  // 1024 slots per tile
 constexpr int kNT = kTS / 4;     // 256 threads, thread t owns slots 4t..4t+3
@@ -61,22 +52,6 @@ constexpr int kPPW = 2;          // pushes per wave per group
 constexpr int kGP = kNW * kPPW;  // pushes per group
 constexpr int kRR = 3;           // rounds per push at most
 constexpr int kCap = kPPW * kRR; // rounds a wave holds
-
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return (uint64_t)uni((uint32_t)v) | (uint64_t)uni((uint32_t)(v >> 32)) << 32;
-}
-
-// blocks b and b+8 share an XCD (observed dispatch, speed only): neighbouring
-// chunks (which share the cache lines at their boundary) on one XCD
-__device__ __forceinline__ uint32_t xcd_map(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
 
 template <typename V, int M>
 constexpr int occupancy() {
@@ -100,7 +75,8 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void cursor_kernel(
   const uint32_t w = uni((uint32_t)threadIdx.x >> 6);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const uint32_t ci = xcd_map(blockIdx.x, gridDim.x);
+  // neighbouring chunks (which share the cache lines at their boundary) on one XCD
+  const uint32_t ci = xcd_index(blockIdx.x, gridDim.x);
   if (ci >= nchunks) return;
   const CursorChunk C = chunks[ci];
   const CursorJob& J = jobs[C.job];
@@ -296,7 +272,7 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void cursor_kernel(
             tot += c;
           }
           uint32_t* const wsum = cnt;  // zeroed again below
-          const uint32_t x = dev::wave_scan_incl_dpp(tot);
+          const uint32_t x = wave_scan_incl(tot);
           if (lane == 63) wsum[w] = x;
           __syncthreads();
           uint32_t off = x - tot;

@@ -21,30 +21,18 @@
 #include "psg_device.h"
 #include "psg_internal.h"
 
-#define AS1 __attribute__((address_space(1)))
-
 namespace psg {
 
 namespace {
 
+using namespace dev;
+
 constexpr int kNT = 256;
-
-template <typename T>
-__device__ __forceinline__ const AS1 T* G(const T* p) {
-  return (const AS1 T*)p;
-}
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
 
 template <typename V, int M>
 __global__ __launch_bounds__(kNT) void dense_kernel(const TileDesc* __restrict__ tiles,
                                                     uint32_t ntiles) {
-  const uint32_t ti = xcd_tile(blockIdx.x, gridDim.x);
+  const uint32_t ti = xcd_index(blockIdx.x, gridDim.x);
   if (ti >= ntiles) return;
   const TileDesc& T = tiles[ti];
   const uint32_t np = T.np, nt = T.nt;

@@ -63,20 +63,11 @@
 #include "psg_device.h"
 #include "psg_internal.h"
 
-#define AS1 __attribute__((address_space(1)))
-
 namespace psg {
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ const AS1 T* G(const T* p) {
-  return (const AS1 T*)p;
-}
-template <typename T>
-__device__ __forceinline__ AS1 T* GW(T* p) {
-  return (AS1 T*)p;
-}
+using namespace dev;
 
 #ifndef PSG_SKELETON
 #define PSG_SKELETON 0  // diagnostic A/B builds: 1 = loads and stores only
@@ -102,64 +93,9 @@ constexpr uint64_t kPtrMask = (1ull << 48) - 1;  // cursor form: pointer bits of
 #define PSG_PC_TOUCH 1  // A/B builds: 0 = the cursor phase does not touch the value lines
 #endif
 
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-  return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v);
-}
-
 #ifndef PSG_DDMA
-#define PSG_DDMA 1  // A/B builds: 0 = D through registers
+#define PSG_DDMA 1  // A/B builds: 0 = D through registers (else dev::dma16, LDS-DMA)
 #endif
-// 16 B per lane from global memory straight into LDS (gfx950 LDS-DMA), as
-// in psg_tile.hip: inline asm (the builtin made the compiler wait for it at
-// the next reuse of its address registers); readers wait with dma_wait()
-typedef __attribute__((address_space(3))) void* LdsPtr;
-__device__ __forceinline__ void dma16(const void* g, void* lds) {
-  const uint32_t la = (uint32_t)(uintptr_t)(LdsPtr)lds;
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g), "s"(la)
-      : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// a barrier for LDS writes that leaves vector-memory operations in flight
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-// the lane index recomputed from nothing (mbcnt over a full mask), so a value
-// needed late in the kernel does not keep the thread-id register live (at 64
-// VGPRs it is the value that would be spilled to scratch: HBM writes)
-__device__ __forceinline__ uint32_t lane_id() {
-  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-}
-
-// blocks b and b+8 share an XCD (observed dispatch, speed only): give each
-// XCD a contiguous run of tiles
-__device__ __forceinline__ uint32_t xcd_tile(uint32_t b, uint32_t n) {
-  const uint32_t x = b & 7u, j = b >> 3, q = n >> 3, r = n & 7u;
-  return x * q + (x < r ? x : r) + j;
-}
-
-// inclusive 64-lane prefix sum by DPP (row shifts, then row broadcasts):
-// immediate lane controls, so no per-lane shuffle addresses stay live
-__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);  // row_shr:1
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);  // row_shr:2
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);  // row_shr:4
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);  // row_shr:8
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return x;
-}
 
 // waves per SIMD the LDS allows (8 for the f32, m = 1 case: 4 workgroups per CU):
 // the register budget follows it through __launch_bounds__
@@ -212,12 +148,12 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
   // the tiles of this workgroup: one (partition form), or a chunk (cursor form)
   uint32_t tb, te, ci = 0;
   if constexpr (CUR) {
-    ci = xcd_tile(blockIdx.x, gridDim.x);
+    ci = xcd_index(blockIdx.x, gridDim.x);
     if (ci >= nchunks) return;
     tb = chunks[ci].t0;
     te = chunks[ci].t1;
   } else {
-    tb = xcd_tile(blockIdx.x, gridDim.x);
+    tb = xcd_index(blockIdx.x, gridDim.x);
     if (tb >= ntiles) return;
     te = tb + 1u;
   }

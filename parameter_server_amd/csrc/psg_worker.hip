@@ -399,9 +399,7 @@ __global__ __launch_bounds__(256) void objv_kernel(const double* __restrict__ pa
 }
 
 // ---- (g) ------------------------------------------------------------------------
-// std::min(a, b) as <algorithm> defines it: b < a ? b : a.  Not fmin: a NaN
-// first argument stays a NaN, as in the reference.
-__device__ __forceinline__ double std_min(double a, double b) { return b < a ? b : a; }
+using dev::std_min;  // std::min as <algorithm> defines it, not fmin
 
 __device__ __forceinline__ double inactive_value() {  // kInactiveValue_, darling.cc:13-15
   return __longlong_as_double(-1ll);
