@@ -970,11 +970,15 @@ int psg_mb_labels(psg_minibatch* mb, const double** y_dev, const double** xw_dev
  * Defined deviations from the reference:
  *  - a product predict * goodness that is NaN or of magnitude >= 2^63 has no
  *    defined conversion in C++; it gets the key INT64_MIN, which is what the
- *    reference's x86-64 build produces;
+ *    reference's x86-64 build produces (recorded from it, one prediction
+ *    at a time, in tests/golden/reference_pin/auc.npz);
  *  - n == 0 is a legal no-op (the reference CHECKs it, auc.h:71);
  *    n >= 2^32 - 1 is PSG_ERR_SIZE (positions are uint32);
- *  - psg_auc_merge drops entries whose count is 0 (the reference's map keeps
- *    the key with a count of 0, which changes no result);
+ *  - psg_auc_merge drops entries whose count is 0.  The reference's map keeps
+ *    the key with a count of 0, which adds 0 to every sum and changes no
+ *    accuracy, and no evaluate but one: a side that holds zero counts only is
+ *    not empty() there, so its evaluate (auc.h:43) goes on to 0 / 0 = NaN
+ *    where this one returns .5, as for a side with no entry;
  *  - an add reads the batch's smallest and largest key (16 bytes) back before
  *    it sorts, to choose the radix digits: it waits for its own key kernel,
  *    as psg_mb_load waits for its OR / AND reduction;

@@ -14,6 +14,10 @@ template <typename V> class SArray {
   SArray() {}
   explicit SArray(size_t n)
       : p_(new std::vector<char>(n * sizeof(V))), off_(0), n_(n) {}
+  SArray(size_t n, V fill)
+      : p_(new std::vector<char>(n * sizeof(V))), off_(0), n_(n) {
+    std::fill(begin(), end(), fill);
+  }
   // the same bytes seen as another element type
   template <typename W> explicit SArray(const SArray<W>& o)
       : p_(o.p_), off_(o.off_), n_(o.n_ * sizeof(W) / sizeof(V)) {}
@@ -27,6 +31,7 @@ template <typename V> class SArray {
   V* begin() const { return data(); }
   V* end() const { return data() + n_; }
   V& operator[](size_t i) const { return data()[i]; }
+  V& back() const { return data()[n_ - 1]; }
 
   void clear() { p_.reset(); off_ = 0; n_ = 0; }
   void resize(size_t n) {

@@ -1,10 +1,13 @@
 """CPU restatements of the reference's evaluation, for the AUC tests.
 
-This is a RESTATEMENT, not the reference's compiled code: auc.h includes
-proto/evaluation.pb.h and needs protobuf, which is not in the image, so this
-row of the oracle is unpinned.  As in worker_ref.py
-there are two independent forms that must agree bit for bit
-(tests/test_auc.py):
+This is a RESTATEMENT, held to the reference's compiled code: auc.h and
+evaluation.h are compiled in place into oracle/_ref/libref_auc.so, what they
+return is recorded in tests/golden/reference_pin/{auc,auc_merge,exact_auc}.npz,
+and tests/test_reference_pin.py holds both forms below to those recordings
+bit for bit.  What has no reference stays unpinned, on
+the two forms' agreement alone (tests/test_auc.py): evaluate by key, and the
+exact AUC where predictions tie across the two classes.  As in worker_ref.py
+there are two independent forms that must agree bit for bit:
 
 ``scalar_*``  dicts, Python ints and floats (IEEE binary64, one correctly
               rounded operation per operator), the reference's own loops;
@@ -105,8 +108,16 @@ def scalar_evaluate(data, as_written=False):
     while t < len(tk):
         tp_sum += float(tc[t])
         t += 1
-    auc = auc / tp_sum / fp_sum
+    auc = _div(_div(auc, tp_sum), fp_sum)
     return 1 - auc if auc < .5 else auc
+
+
+def _div(a, b):
+    """a / b as IEEE 754 has it (Python raises where b is 0): the sums are 0
+    when a side holds nothing but zero counts, which the reference's map may."""
+    if b != 0:
+        return a / b
+    return math.nan if a == 0 or a != a else math.copysign(math.inf, a)
 
 
 def scalar_exact(y, predict):
@@ -184,7 +195,8 @@ def vector_evaluate(data, as_written=False):
     else:
         taken = np.searchsorted(tk, fk, side="right")
     auc = _fold(cum[taken] * fc.astype(F64))[-1]
-    auc = auc / cum[-1] / _fold(fc.astype(F64))[-1]
+    with np.errstate(all="ignore"):  # 0 / 0 where a side holds only zero counts
+        auc = auc / cum[-1] / _fold(fc.astype(F64))[-1]
     return float(1 - auc if auc < .5 else auc)
 
 

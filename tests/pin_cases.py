@@ -16,7 +16,11 @@ What the inputs avoid, and why: two NaNs never meet in one add (which
 payload survives is not fixed by IEEE 754) and +inf never meets -inf, nor
 0 an infinity in a product (the default NaN's sign differs between x86 and
 the GPU).  Everything else -- -0.0, single NaNs quiet and signalling, +-inf,
-denormals, 0xFFFFFFFF counts -- is in.
+denormals, 0xFFFFFFFF counts -- is in.  The AUC and localizer cases add no
+float arithmetic of their own to what is recorded: keys, counts and indices
+are integers, values are copied, and a 0 / 0 result is compared as "a NaN".
+An output of more than ARRAY_CAP bytes is recorded as its SHA-256 only
+(record_output / same_output).
 """
 import hashlib
 import json
@@ -397,6 +401,345 @@ def cm_case(n, k, seed=0):
         batches.append((np.ascontiguousarray(uni[idx]), counts))
     query = np.ascontiguousarray(uni[(splitmix64(s + 30, 3000) % _u(uni.size)).astype(np.int64)])
     return CmCase(n, k, batches, query)
+
+
+# ------------------------------------------------------------------ AUC cases
+# Inputs of auc.npz, auc_merge.npz and exact_auc.npz (reference src/base/auc.h,
+# src/base/evaluation.h).  The sizes sit around the device sort's tile
+# (psg_mb_sort_tile(), 256 * PSG_SORT_KPT pairs): PIN_TILE is its value when
+# the fixtures were recorded and is stored in their meta; the GPU tests assert
+# that the library still has it.
+PIN_TILE = 2048
+AUC_GOODNESS = (1, 10, 100, 1000, 100000, -1000)
+AUC_LABELS = np.array([1.0, -1.0, 0.0, -0.0, 0.5, 2.0, np.nan])  # > 0 is a positive: 1, 0.5, 2
+AUC_THRESHOLDS = (0.0, 0.5, -0.25)
+ARRAY_CAP = 8192  # a recorded output of more bytes is stored as its SHA-256 only
+# decimals whose product with a power of ten rounds onto an integer or just
+# below one (0.29 * 100 = 28.999999999999996 -> key 28, 0.57 * 100 =
+# 56.99999999999999, 4.35 * 100 = 434.99999999999994; 0.7 * 10 = 7 and
+# 0.1 * 10 = 1 exactly, though neither factor is)
+_DECIMALS = (0.29, 0.7, 0.1, 0.029, 0.007, 0.001, 0.00029, 0.00007, 0.00001, 0.57, 0.58, 4.35,
+             1.15, 8.2, 2.675, 0.3, 0.6, 0.9, 1.1, 16.08, 0.0003, 0.019999999999999997)
+
+
+def pin_sizes(tile=PIN_TILE):
+    return (1, tile - 1, tile, tile + 1, 3 * tile + 5)
+
+
+def spread20(x):
+    """Draws as doubles in [-20, 20): an integer / 2^30."""
+    return ((x % _u(40 << 30)).astype(np.int64) - (20 << 30)).astype(np.float64) / np.float64(1 << 30)
+
+
+def auc_labels(seed, n):
+    return AUC_LABELS[(splitmix64(seed, n) % _u(AUC_LABELS.size)).astype(np.int64)]
+
+
+def _place(seed, base, special):
+    """base with the first min(n, m) of `special` at drawn positions."""
+    at = np.argsort(splitmix64(seed, base.size), kind="stable")[:min(base.size, special.size)]
+    base[at] = special[:at.size]
+    return base
+
+
+def auc_specials(g):
+    """Predictions whose key under goodness g is DEFINED and easy to get
+    wrong: decimals around an integer product, negatives in (-1/|g|, 0)
+    (truncation toward zero gives key 0, not -1), both zeros, denormals, and
+    +-1e18 / |g| (exact, so the product is +-1e18 < 2^63).  With g = 1 also the
+    largest doubles below 2^63 in magnitude."""
+    a = float(abs(g))
+    dec = np.array(_DECIMALS)
+    inside = np.array([-0.5, -0.999, -(2.0 ** -30)]) / a
+    out = [dec[:1], -dec[:1], inside, -inside, dec[1:], -dec[1:],
+           np.array([0.0, -0.0, 5e-324, -5e-324, 1e-310, -1e-310, 1e18 / a, -1e18 / a])]
+    if g == 1:
+        out.append(np.array([2.0 ** 63 - 1024, -(2.0 ** 63 - 1024), 2.0 ** 62, -(2.0 ** 62)]))
+    return np.concatenate(out)
+
+
+def auc_undefined(g):
+    """Predictions whose product with g has no defined conversion to int64 in
+    C++ (NaN, or of magnitude >= 2^63; -2^63 itself is counted here too, as
+    psg.h counts it)."""
+    a = float(abs(g))
+    return np.array([np.nan, np.inf, -np.inf, 1e300, -1e300, 9.3e18 / a, -9.3e18 / a, 1e19 / a,
+                     -1e19 / a, 2.0 ** 63 / a, -(2.0 ** 63) / a, 1.7976931348623157e308])
+
+
+class AucCase:
+    def __init__(self, name, y, p, g):
+        self.name, self.y, self.p, self.g = name, y, p, g
+
+    def digest(self):
+        return sha256([fbits(self.y), fbits(self.p), np.array([self.g], np.int64)])
+
+
+def auc_cases():
+    """[AucCase]: every size with every goodness, defined conversions only;
+    then one case per goodness (257 examples) that also holds the undefined
+    ones, kept apart so that the defined cases stay clean."""
+    out = []
+    for i, n in enumerate(pin_sizes()):
+        for j, g in enumerate(AUC_GOODNESS):
+            s = 50000 + 100 * i + 10 * j
+            p = _place(s + 2, spread20(splitmix64(s, n)), auc_specials(g))
+            out.append(AucCase("n%d_g%d" % (n, g), auc_labels(s + 1, n), p, g))
+    for j, g in enumerate(AUC_GOODNESS):
+        s = 51000 + 10 * j
+        p = _place(s + 2, spread20(splitmix64(s, 257)),
+                   np.concatenate([auc_undefined(g), auc_specials(g)[:20]]))
+        out.append(AucCase("undefined_g%d" % g, auc_labels(s + 1, 257), p, g))
+    return out
+
+
+def _auc_side(seed, n, universe, unique, shift=14):
+    """n draws as (keys in [-universe/2, universe/2), counts below 2^(64 -
+    shift)): with shift = 14 a few hundred counts sum past 2^53, so the order
+    of accuracy's and evaluate's double sums shows."""
+    k = (splitmix64(seed, n) % _u(universe)).astype(np.int64) - universe // 2
+    if unique:
+        k = np.unique(k)
+    c = (splitmix64(seed + 1, k.size) >> _u(shift)) + _u(1)
+    return np.ascontiguousarray(k), np.ascontiguousarray(c)
+
+
+def auc_merge_sequences():
+    """name -> (goodness, [AUCData]): what a root merges, then accuracy at
+    AUC_THRESHOLDS and evaluate()."""
+    seq = {}
+    z64, zu = np.zeros(0, np.int64), np.zeros(0, np.uint64)
+    # three workers' AUCData as compute writes them: ascending distinct keys
+    seq["three_workers"] = (10, [_auc_side(52000 + 10 * w, 300, 400, True)
+                                 + _auc_side(52005 + 10 * w, 300, 400, True) for w in range(3)])
+    # unsorted lists that repeat keys, small counts among the large
+    rep = []
+    for w in range(2):
+        tk, tc = _auc_side(52100 + 10 * w, 500, 60, False)
+        fk, fc = _auc_side(52105 + 10 * w, 500, 60, False, shift=60)
+        rep.append((tk, tc, fk, fc))
+    seq["repeated_keys"] = (1000, rep)
+    # zero counts: on keys that other entries also hit, and on keys (+-777777)
+    # that only ever get a zero; both sides keep non-zero entries
+    zc = []
+    for w in range(3):
+        tk, tc = _auc_side(52200 + 10 * w, 200, 300, w != 1, shift=50)
+        fk, fc = _auc_side(52205 + 10 * w, 200, 300, w != 1, shift=50)
+        tc[chance(splitmix64(52208 + 10 * w, tc.size), 0.3)] = 0
+        fc[chance(splitmix64(52209 + 10 * w, fc.size), 0.3)] = 0
+        only = np.array([777777, -777777], np.int64)
+        zc.append((np.concatenate([tk, only]), np.concatenate([tc, np.zeros(2, np.uint64)]),
+                   np.concatenate([fk, -only]), np.concatenate([fc, np.zeros(2, np.uint64)])))
+    seq["zero_counts"] = (100, zc)
+    # the boundary of "dropping zero counts changes no result": a side that
+    # holds nothing but zero counts is not empty() in the reference
+    tk, tc = _auc_side(52300, 50, 40, True, shift=60)
+    seq["zero_only_negatives"] = (10, [(tk, tc, np.array([3, -7, 3], np.int64), np.zeros(3, np.uint64))])
+    seq["zero_only_both"] = (10, [(np.array([1, 2], np.int64), np.zeros(2, np.uint64),
+                                   np.array([0], np.int64), np.zeros(1, np.uint64))])
+    # one side empty: evaluate is .5
+    seq["no_negatives"] = (1000, [_auc_side(52400 + w, 100, 90, True) + (z64, zu) for w in range(2)])
+    seq["no_positives"] = (-1000, [(z64, zu) + _auc_side(52450, 100, 90, True)])
+    # accuracy compares (double)key with x = threshold * goodness: goodness
+    # 2^55 puts x at 0, 2^54 and -2^53, where key +- 1 rounds onto x
+    e54, e53 = 1 << 54, 1 << 53
+    seq["keys_past_2p53"] = (1 << 55, [
+        (np.array([-e53 - 1, -e53, -e53 + 1, e54 - 1, e54, e54 + 1, e54 + 3, 0, -1], np.int64),
+         np.array([1, 2, 4, 8, 16, 32, 64, 128, 256], np.uint64),
+         np.array([-e53 - 1, -e53, -e53 + 1, e54 - 1, e54, e54 + 1, e54 + 3, 0, -1,
+                   -(1 << 63), (1 << 63) - 1], np.int64),
+         np.array([3, 5, 7, 11, 13, 17, 19, 23, 29, 31, 37], np.uint64))])
+    return seq
+
+
+def auc_sequence_digest(goodness, datas):
+    return sha256([np.array([goodness], np.int64)] + [a for d in datas for a in d])
+
+
+def auc_without_zeros(data):
+    """An AUCData without its zero-count entries: what psg_auc_merge keeps
+    (include/psg.h, defined deviation)."""
+    tk, tc, fk, fc = data
+    return tk[tc != 0], tc[tc != 0], fk[fc != 0], fc[fc != 0]
+
+
+def auc_data_digest(data):
+    tk, tc, fk, fc = data
+    return sha256([np.asarray(tk, np.int64), np.asarray(tc, np.uint64), np.asarray(fk, np.int64),
+                   np.asarray(fc, np.uint64)])
+
+
+class ExactCase:
+    def __init__(self, name, y, p):
+        self.name, self.y, self.p = name, y, p
+
+    def digest(self):
+        return sha256([fbits(self.y), fbits(self.p)])
+
+
+def exact_auc_cases():
+    """[ExactCase] whose result does not depend on how a sort orders equal
+    predictions (the reference's std::sort leaves that open): all predictions
+    distinct, negatives among them; or ties only among examples of one class
+    (the class is a function of the prediction), -0.0 and +0.0 among them."""
+    pos_l, neg_l = np.array([1.0, 0.5, 2.0]), np.array([-1.0, 0.0, -0.0, np.nan])
+    out = []
+    for i, n in enumerate(pin_sizes()):
+        s = 53000 + 100 * i
+        perm = np.argsort(splitmix64(s, n), kind="stable")
+        out.append(ExactCase("distinct_n%d" % n, auc_labels(s + 1, n),
+                             (perm - n // 2).astype(np.float64) * 0.5 + 0.25))
+        v = (splitmix64(s + 2, n) % _u(37)).astype(np.int64) - 18
+        d = splitmix64(s + 3, n)
+        p = v.astype(np.float64) / 4.0
+        p[(v == 0) & chance(d, 0.5)] = -0.0
+        positive = ((v // 3) % 2 == 0)
+        y = np.where(positive, pos_l[(d % _u(3)).astype(np.int64)], neg_l[(d % _u(4)).astype(np.int64)])
+        out.append(ExactCase("ties_in_one_class_n%d" % n, y, p))
+    return out
+
+
+# ------------------------------------------------------------ localizer cases
+# Inputs of localizer.npz (reference src/base/localizer.h over
+# src/util/parallel_sort.h).  L40000 is past parallelSort's grain of 16,384
+# pairs: with 4 threads the split into threads and std::inplace_merge run.
+LOC_NAMES = ("L1", "Tm1", "T", "Tp1", "3Tp5", "L40000", "D40000")
+LOC_THREADS = (1, 4)
+
+
+def power_law(x, universe):
+    """Draws as ranks in [0, universe), P(rank < r) = (r / universe)^(1/3), in
+    integer arithmetic: rank 0 takes universe^(-1/3) of the draws."""
+    r = x >> _u(32)
+    q = (r * r) >> _u(32)
+    q = (q * r) >> _u(32)
+    return ((q * _u(universe)) >> _u(32)).astype(np.int64)
+
+
+def csr_offsets(seed, n, rows):
+    """rows + 1 offsets over n entries; with 5 rows or more the first, the
+    middle and the last row are empty."""
+    empty = {0, rows // 2, rows - 1} if rows >= 5 else set()
+    live = [r for r in range(rows) if r not in empty]
+    cuts = np.sort((splitmix64(seed, len(live) - 1) % _u(n + 1)).astype(np.int64))
+    lens = np.zeros(rows, np.int64)
+    lens[live] = np.diff(np.concatenate([[0], cuts, [n]]))
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+
+
+class LocCase:
+    def __init__(self, name, offset, index, value, dicts):
+        self.name, self.offset, self.index, self.value, self.dicts = name, offset, index, value, dicts
+
+    def digest(self):
+        arrs = [self.offset, self.index] + ([] if self.value is None else [fbits(self.value)])
+        for d in sorted(self.dicts):
+            arrs.append(self.dicts[d])
+        return sha256(arrs)
+
+
+def loc_dicts(uniq, edges):
+    """The dictionaries of a case whose ids are uniq (ascending).  edges:
+    there is room below the smallest id and above the largest."""
+    between = uniq[::2] + _u(1)
+    between = between[~np.isin(between, uniq)]
+    lo, hi = uniq[0], uniq[-1]
+    absent = [between]
+    d = {"all": uniq.copy(), "third": uniq[::3].copy(), "one": uniq[uniq.size // 2:uniq.size // 2 + 1].copy(),
+         "empty": np.zeros(0, np.uint64)}
+    if edges:
+        below = np.array([lo - _u(900), lo - _u(2), lo - _u(1)], np.uint64)
+        above = np.array([hi + _u(1), hi + _u(2), hi + _u(900)], np.uint64)
+        d["below"], d["above"] = below, above  # matched = 0: a matrix of zero entries
+        absent += [below, above]
+    d["absent"] = np.unique(np.concatenate([uniq] + absent))
+    return {k: np.ascontiguousarray(v) for k, v in d.items()}
+
+
+def loc_case(name):
+    """L1: one entry, one row.  Tm1 / T / Tp1 / 3Tp5: around the sort tile.
+    L40000 / D40000: past parallelSort's grain, long runs / all distinct."""
+    T = PIN_TILE
+    n, kind, rows, binary = {"L1": (1, "one", 1, False), "Tm1": (T - 1, "zipf", 60, False),
+                             "T": (T, "distinct", 41, True), "Tp1": (T + 1, "zipf", 1, True),
+                             "3Tp5": (3 * T + 5, "edges", 200, False),
+                             "L40000": (40000, "zipf", 1500, False),
+                             "D40000": (40000, "distinct", 700, True)}[name]
+    s = 54000 + 100 * LOC_NAMES.index(name)
+    # ids that use the high digits (above 2^32, above 2^63), with room at both ends
+    table = unique_keys(s, 3000 if kind != "distinct" else n)
+    table = table[(table > _u(1 << 10)) & (table < _u(U64 - (1 << 10)))]
+    if kind == "one":
+        index = np.array([(1 << 63) + 12345], np.uint64)
+    elif kind == "distinct":
+        assert table.size >= n - 8
+        index = np.concatenate([table, np.arange(5, 5 + n - table.size, dtype=np.uint64) << _u(33)])
+        index = index[np.argsort(splitmix64(s + 1, n), kind="stable")]
+    else:
+        table = table[np.argsort(splitmix64(s + 2, table.size), kind="stable")]  # rank is not id order
+        if kind == "edges":
+            table[5], table[9] = 0, U64 - 1  # 0 and 2^64 - 2 among the frequent ids
+        index = table[power_law(splitmix64(s + 1, n), table.size)]
+    index = np.ascontiguousarray(index)
+    assert index.size == n
+    value = None if binary else scaled(splitmix64(s + 3, n), np.float64)
+    if value is not None and n > 3:
+        value[[0, 1, 2]] = [-0.0, 5e-324, np.nan]
+    return LocCase(name, csr_offsets(s + 4, n, rows), index, value,
+                   loc_dicts(np.unique(index), kind != "edges"))
+
+
+def random_loc_case(seed):
+    """Seeded cases beyond the fixtures (live tests)."""
+    n = [1, 7, 300, 2049, 5000, 20000, 33000, 70000][seed % 8]
+    rows = [1, 3, 10, 1, 77, 300, 2, 1000][seed % 8]
+    s = 55000 + 100 * seed
+    table = unique_keys(s, [1, 5, 40, 3000, 200, 19000, 9, 50000][seed % 8])
+    table = table[(table > _u(1 << 10)) & (table < _u(U64 - (1 << 10)))]
+    table = table[np.argsort(splitmix64(s + 2, table.size), kind="stable")]
+    index = np.ascontiguousarray(table[power_law(splitmix64(s + 1, n), table.size)])
+    value = None if seed % 2 else scaled(splitmix64(s + 3, n), np.float64)
+    return LocCase("R%d" % seed, csr_offsets(s + 4, n, rows), index, value,
+                   loc_dicts(np.unique(index), True))
+
+
+def random_auc_case(seed):
+    g = [1, 10, 100, 1000, 100000, -1000, 7, -3][seed % 8]
+    n = [1, 2, 100, 2049, 5000, 333, 64, 4097][seed % 8]
+    s = 56000 + 100 * seed
+    p = _place(s + 2, spread20(splitmix64(s, n)), np.concatenate([auc_undefined(g), auc_specials(g)]))
+    return AucCase("R%d" % seed, auc_labels(s + 1, n), p, g)
+
+
+def record_output(arrays, sha, key, a):
+    """Recorder only: every output's SHA-256, and the array itself when it is
+    at most ARRAY_CAP bytes.  Doubles are passed as their bits."""
+    a = np.ascontiguousarray(a)
+    assert a.dtype.kind in "iub"
+    sha[key] = sha256([a])
+    if a.nbytes <= ARRAY_CAP:
+        arrays[key] = a
+
+
+def same_output(arrays, sha, key, got):
+    """got (same dtype as recorded; doubles as their bits) against a recorded
+    output: the array where the fixture holds it, and its SHA-256 always."""
+    got = np.ascontiguousarray(got)
+    if key in arrays:
+        want = arrays[key]
+        if want.dtype != got.dtype or want.shape != got.shape or not np.array_equal(want, got):
+            return False
+    return sha256([got]) == sha[key]
+
+
+def remapped_from_tagged(n, new_index, new_value):
+    """remapped_idx (localizer.h:123-136) is a local of remapIndex.  Run with
+    value[j] = j, the returned matrix says which positions survived (new_value)
+    and what each was mapped to (new_index): remapped_idx[j] = new_index[k] + 1
+    for the k-th survivor j, and 0 for every dropped position."""
+    r = np.zeros(n, np.uint32)
+    r[np.asarray(new_value, np.float64).astype(np.int64)] = np.asarray(new_index, np.uint32) + np.uint32(1)
+    return r
 
 
 # --------------------------------------------------------------- snappy cases

@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE: ctypes binding of the reference's own code compiled in
-place (oracle/_ref/libref_match.so, libref_ftrl.so, libref_countmin.so; see
-oracle/ref_*_shim.cc and oracle/Makefile).  Only tools/record_reference.py
+place (oracle/_ref/libref_match.so, libref_ftrl.so, libref_countmin.so,
+libref_auc.so, libref_localizer.so; see oracle/ref_*_shim.cc and
+oracle/Makefile).  Only tools/record_reference.py
 and the live tests of tests/test_reference_pin.py load it; no GPU test does.
 """
 import ctypes as C
@@ -11,7 +12,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
-LIBS = {"match": "libref_match.so", "ftrl": "libref_ftrl.so", "countmin": "libref_countmin.so"}
+LIBS = {"match": "libref_match.so", "ftrl": "libref_ftrl.so", "countmin": "libref_countmin.so",
+        "auc": "libref_auc.so", "localizer": "libref_localizer.so"}
 
 _p, _sz, _u64, _psz = C.c_void_p, C.c_size_t, C.c_uint64, C.POINTER(C.c_size_t)
 _pu64 = C.POINTER(C.c_uint64)
@@ -65,6 +67,23 @@ _SIG = {
         "ref_ff_insert_keys": (None, [_p, _p, _p, _sz]),
         "ref_ff_query_keys": (_sz, [_p, _p, _sz, C.c_int, _p]),
         "ref_ff_table": (None, [_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _p]),
+    },
+    "auc": {
+        "ref_auc_compute": (None, [C.c_int64, _p, _p, _sz, _p, _p, _psz, _p, _p, _psz]),
+        "ref_auc_create": (_p, [C.c_int64]),
+        "ref_auc_destroy": (None, [_p]),
+        "ref_auc_merge": (None, [_p, _p, _p, _sz, _p, _p, _sz]),
+        "ref_auc_accuracy": (C.c_double, [_p, C.c_double]),
+        "ref_auc_evaluate": (C.c_double, [_p]),
+        "ref_auc_maps": (None, [_p, _psz, _psz, _p, _p, _p, _p]),
+        "ref_eval_auc": (C.c_double, [_p, _p, _sz]),
+    },
+    "localizer": {
+        "ref_loc_create": (_p, []),
+        "ref_loc_destroy": (None, [_p]),
+        "ref_loc_count_uniq": (_sz, [_p, _p, _sz, C.c_int, _p, _p]),
+        "ref_loc_remap": (C.c_int, [_p, _p, _sz, _p, _sz, _p, _p, _sz, C.c_int, _p, _p, _psz, _p,
+                                    _psz]),
     },
 }
 
@@ -260,3 +279,100 @@ class RefFilter:
         out = np.zeros(max(1, n.value), np.uint8)
         self._L.ref_ff_table(self._h, C.byref(n), C.byref(k), _a(out))
         return n.value, k.value, out[: n.value]
+
+
+# ------------------------------------------------------- auc.h, evaluation.h
+def _f64(x):
+    return np.ascontiguousarray(x, np.float64)
+
+
+def auc_compute(y, predict, goodness):
+    """AUC::compute<double>: the AUCData (tp_key, tp_count, fp_key, fp_count)."""
+    y, p = _f64(y), _f64(predict)
+    assert y.size == p.size >= 1  # the reference CHECKs both
+    tk, fk = np.zeros(y.size, np.int64), np.zeros(y.size, np.int64)
+    tc, fc = np.zeros(y.size, np.uint64), np.zeros(y.size, np.uint64)
+    nt, nf = C.c_size_t(), C.c_size_t()
+    lib("auc").ref_auc_compute(int(goodness), _a(y), _a(p), y.size, _a(tk), _a(tc), C.byref(nt),
+                               _a(fk), _a(fc), C.byref(nf))
+    return (tk[:nt.value].copy(), tc[:nt.value].copy(), fk[:nf.value].copy(), fc[:nf.value].copy())
+
+
+class RefAUC:
+    """The reference's AUC as the root uses it: merge, accuracy, evaluate."""
+
+    def __init__(self, goodness):
+        self._L = lib("auc")
+        self._h = self._L.ref_auc_create(int(goodness))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.ref_auc_destroy(self._h)
+            self._h = None
+
+    def merge(self, tp_key, tp_count, fp_key, fp_count):
+        tk, fk = (np.ascontiguousarray(a, np.int64) for a in (tp_key, fp_key))
+        tc, fc = (np.ascontiguousarray(a, np.uint64) for a in (tp_count, fp_count))
+        assert tk.size == tc.size and fk.size == fc.size  # the reference CHECKs both
+        self._L.ref_auc_merge(self._h, _a(tk), _a(tc), tk.size, _a(fk), _a(fc), fk.size)
+
+    def accuracy(self, threshold):
+        return self._L.ref_auc_accuracy(self._h, float(threshold))
+
+    def evaluate(self):
+        return self._L.ref_auc_evaluate(self._h)
+
+    def maps(self):
+        """The two maps as an AUCData, zero counts included."""
+        nt, nf = C.c_size_t(), C.c_size_t()
+        self._L.ref_auc_maps(self._h, C.byref(nt), C.byref(nf), None, None, None, None)
+        tk, fk = np.zeros(max(1, nt.value), np.int64), np.zeros(max(1, nf.value), np.int64)
+        tc, fc = np.zeros(max(1, nt.value), np.uint64), np.zeros(max(1, nf.value), np.uint64)
+        self._L.ref_auc_maps(self._h, C.byref(nt), C.byref(nf), _a(tk), _a(tc), _a(fk), _a(fc))
+        return tk[:nt.value], tc[:nt.value], fk[:nf.value], fc[:nf.value]
+
+
+def exact_auc(y, predict):
+    """Evaluation<double>::auc."""
+    y, p = _f64(y), _f64(predict)
+    assert y.size == p.size
+    return lib("auc").ref_eval_auc(_a(y), _a(p), y.size)
+
+
+# ---------------------------------------------------------------- localizer.h
+class RefLocalizer:
+    """The reference's Localizer<uint64, double>: count_uniq, then remap
+    against any number of dictionaries (it keeps the sorted pairs)."""
+
+    def __init__(self):
+        self._L = lib("localizer")
+        self._h = self._L.ref_loc_create()
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.ref_loc_destroy(self._h)
+            self._h = None
+
+    def count_uniq(self, index, threads=1):
+        """(uniq_idx, idx_frq)."""
+        idx = u64(index)
+        assert idx.size >= 1
+        uniq, frq = np.zeros(idx.size, np.uint64), np.zeros(idx.size, np.uint32)
+        n = self._L.ref_loc_count_uniq(self._h, _a(idx), idx.size, threads, _a(uniq), _a(frq))
+        return uniq[:n].copy(), frq[:n].copy()
+
+    def remap(self, offset, index, value, dic, threads=1):
+        """(new_offset, new_index, new_value), or None where the reference
+        returns a null pointer.  value None: a binary matrix."""
+        off, idx, d = u64(offset), u64(index), u64(dic)
+        assert idx.size == 0 or d.size == 0 or int(off[-1]) == idx.size  # CHECKed
+        val = None if value is None else _f64(value)
+        no = np.zeros(off.size, np.uint64)
+        ni, nv = np.zeros(max(1, idx.size), np.uint32), np.zeros(max(1, idx.size), np.float64)
+        nni, nnv = C.c_size_t(), C.c_size_t()
+        rc = self._L.ref_loc_remap(self._h, _a(off), off.size, _a(idx), idx.size,
+                                   None if val is None else _a(val), _a(d), d.size, threads,
+                                   _a(no), _a(ni), C.byref(nni), _a(nv), C.byref(nnv))
+        if rc != 0:
+            return None
+        return no, ni[:nni.value].copy(), nv[:nnv.value].copy()

@@ -1,6 +1,9 @@
 """CPU: the two forms of tests/auc_ref.py agree bit for bit, hand-worked
 answers, and the library's pure host functions psg_auc_accuracy_data /
-psg_auc_evaluate_data against the restatement (no device calls)."""
+psg_auc_evaluate_data against the restatement (no device calls).  The
+restatement is pinned to the reference's compiled auc.h / evaluation.h in
+tests/test_reference_pin.py; evaluate by key (PSG_AUC_BY_KEY) and exact-AUC
+ties across the classes have no reference and are held here alone."""
 import ctypes as C
 import math
 

@@ -8,6 +8,10 @@ form is forced by its flag (PSG_GROUP32 / PSG_GROUP64 / PSG_NO_INDEX /
 PSG_NO_ZERO_COPY among them) and, on the plan path, the kernel that ran is
 asserted.  The inputs are rebuilt by tests/pin_cases.py and their SHA-256
 checked against the fixture first.
+
+Below them, the device evaluation (psg_auc_*) and the worker's localizer
+(psg_mb_uniq / psg_mb_localize) against the recorded AUC, Evaluation and
+Localizer of the reference, in the same way.
 """
 import numpy as np
 import pytest
@@ -152,3 +156,176 @@ def test_gather_and_slice_against_the_recorded(torch_cuda, name, r):
     assert np.array_equal(pos[1:][ok], fx["slice_end"][ok])
     # an invalid piece (outside the key range) is empty
     assert np.array_equal(pos[:-1][~ok], pos[1:][~ok])
+
+
+# ------------------------------------------------- evaluation and localizer
+# psg_auc_* / psg_auc_exact_dev (psg_auc.hip) and psg_mb_uniq / psg_mb_localize
+# (psg_worker.hip over psg_sort.h) against what the reference's own AUC,
+# Evaluation<double>::auc and Localizer returned (auc.npz, auc_merge.npz,
+# exact_auc.npz, localizer.npz): only the fixtures and tests/pin_cases.py are
+# read here, never the reference tree or oracle/_ref.
+AUC_PARTS = ("tp_key", "tp_count", "fp_key", "fp_count")
+ZERO_ONLY = {"zero_only_negatives", "zero_only_both"}  # see tests/test_reference_pin.py
+
+
+def dev(torch, a):
+    """A host array as a device tensor (its bytes, whatever the dtype)."""
+    a = np.ascontiguousarray(a)
+    t = torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to("cuda:0")
+    if t.numel() == 0:
+        t = torch.zeros(8, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    return t
+
+
+def fb(v):
+    """A double's bits as the fixtures spell them; every NaN is one value."""
+    return "nan" if np.isnan(v) else "%016x" % int(P.fbits(np.array([v], np.float64))[0])
+
+
+def recorded_double(hexbits):
+    return fb(float(np.array([int(hexbits, 16)], np.uint64).view(np.float64)[0]))
+
+
+@pytest.fixture(scope="module")
+def f64_ctx(torch_cuda):
+    import ctypes as C
+    from parameter_server_amd import _lib
+    L = _lib.lib()
+    h = C.c_void_p()
+    _lib.check(L.psg_create(0, _lib.PSG_F64, 0, C.byref(h)))
+    yield h
+    L.psg_destroy(h)
+
+
+@pytest.fixture(scope="module")
+def auc(f64_ctx):
+    """One handle for all the cases: clear and set_goodness between them."""
+    from parameter_server_amd.auc import AUC
+    a = AUC(f64_ctx, 1000)
+    yield a
+    a.close()
+
+
+@pytest.fixture(scope="module")
+def mb(f64_ctx):
+    from parameter_server_amd.worker import Minibatch
+    m = Minibatch(f64_ctx)
+    yield m
+    m.close()
+
+
+def fresh(auc, goodness):
+    auc.clear()
+    auc.setGoodness(goodness)
+    return auc
+
+
+def auc_case(name):
+    if "auc" not in _cache:
+        _cache["auc"] = {c.name: c for c in P.auc_cases()}
+    return _cache["auc"][name]
+
+
+def same_aucdata(fx, sha, name, data):
+    return all(P.same_output(fx, sha, "%s.%s" % (name, part), a) for part, a in zip(AUC_PARTS, data))
+
+
+def test_the_sort_tile_is_the_recorded_one():
+    from parameter_server_amd.worker import sort_tile
+    for name in ("auc", "exact_auc", "localizer"):
+        assert P.load_fixture(name)[0]["tile"] == sort_tile() == P.PIN_TILE
+
+
+@pytest.mark.parametrize("name", [c.name for c in P.auc_cases()])
+def test_auc_add_dev_against_the_recorded(torch_cuda, auc, name):
+    """One add over the whole case, and two adds split at T - 1 | rest (an
+    empty rest where the case is shorter): the reference's AUCData both
+    times.  The undefined_* cases hold what psg.h says of NaN and of products
+    of magnitude >= 2^63."""
+    c = auc_case(name)
+    meta, fx = P.load_fixture("auc")
+    assert meta["cases"][name]["input_sha256"] == c.digest()
+    ty, tp = dev(torch_cuda, c.y), dev(torch_cuda, c.p)
+    cut = min(meta["tile"] - 1, c.y.size)
+    for pieces in ([(0, c.y.size)], [(0, cut), (cut, c.y.size)]):
+        fresh(auc, c.g)
+        for a, b in pieces:
+            auc.add_dev(ty.data_ptr() + 8 * a, tp.data_ptr() + 8 * a, b - a)
+        data = auc.data()  # waits
+        assert (data[0].size, data[2].size) == (meta["cases"][name]["ntp"], meta["cases"][name]["nfp"])
+        assert same_aucdata(fx, meta["sha256"], name, data), pieces
+
+
+@pytest.mark.parametrize("name", sorted(P.auc_merge_sequences()))
+def test_auc_merge_against_the_recorded(auc, name):
+    """psg_auc_merge of each sequence, then the histogram, accuracy at the
+    three thresholds and evaluate() as written (PSG_AUC_AS_WRITTEN; PSG_AUC_BY_KEY
+    is a defined deviation with no reference and stays on the restatements)."""
+    g, datas = P.auc_merge_sequences()[name]
+    meta, fx = P.load_fixture("auc_merge")
+    info = meta["sequences"][name]
+    assert info["input_sha256"] == P.auc_sequence_digest(g, datas)
+    maps = tuple(fx["%s.%s" % (name, part)] for part in AUC_PARTS)
+    assert same_aucdata(fx, meta["sha256"], name, maps)
+    fresh(auc, g)
+    for d in datas:
+        auc.merge(*d)
+    got = auc.data()
+    # defined deviation: the zero-count entries of the reference's maps are dropped
+    want = P.auc_without_zeros(maps)
+    assert all(a.dtype == b.dtype and np.array_equal(a, b) for a, b in zip(got, want))
+    assert (info["zero_count_entries"] > 0) == name.startswith("zero_")
+    for th, bits in zip(P.AUC_THRESHOLDS, info["accuracy_bits"]):
+        assert fb(auc.accuracy(th)) == recorded_double(bits), th
+    ev = fb(auc.evaluate(as_written=True))
+    if name in ZERO_ONLY:
+        # ... which shows where a side holds zero counts only: the reference's
+        # map is not empty() and its evaluate is 0 / 0; the product's is .5
+        assert recorded_double(info["evaluate_bits"]) == "nan" and ev == fb(0.5)
+    else:
+        assert ev == recorded_double(info["evaluate_bits"])
+
+
+@pytest.mark.parametrize("name", [c.name for c in P.exact_auc_cases()])
+def test_exact_auc_dev_against_the_recorded(torch_cuda, f64_ctx, name):
+    """Tie-free inputs only (all predictions distinct, or ties within one
+    class): ties across the classes are a defined deviation and not pinned."""
+    from parameter_server_amd.auc import exact_auc_dev
+    cases = P.exact_auc_cases()
+    i = [c.name for c in cases].index(name)
+    c = cases[i]
+    meta, fx = P.load_fixture("exact_auc")
+    assert meta["cases"][name]["input_sha256"] == c.digest()
+    ty, tp = dev(torch_cuda, c.y), dev(torch_cuda, c.p)
+    got = exact_auc_dev(f64_ctx, ty.data_ptr(), tp.data_ptr(), c.y.size)
+    assert fb(got) == recorded_double("%016x" % int(fx["bits"][i]))
+
+
+@pytest.mark.parametrize("name", P.LOC_NAMES)
+def test_localizer_against_the_recorded(torch_cuda, mb, name):
+    """psg_mb_load -> psg_mb_uniq -> psg_mb_localize per dictionary.  The
+    order of positions inside a run of equal ids (PSG_MB_SORTED_POS) is not
+    pinned: the reference's sort leaves it open, the product defines it as
+    stable (tests/test_worker_gpu.py)."""
+    if name not in _cache:
+        _cache[name] = P.loc_case(name)
+    c = _cache[name]
+    meta, fx = P.load_fixture("localizer")
+    info, sha = meta["cases"][name], meta["sha256"]
+    assert info["input_sha256"] == c.digest()
+    mb.load(c.offset, c.index, c.value, np.ones(c.offset.size - 1))
+    assert mb.uniq() == info["n_uniq"]
+    assert P.same_output(fx, sha, name + ".uniq_idx", mb.read("uniq_key"))
+    assert P.same_output(fx, sha, name + ".idx_frq", mb.read("key_cnt"))
+    for dname in sorted(c.dicts):
+        if dname == "empty":  # the reference returns null; the product's Z is its own deviation
+            assert info["matched"][dname] is None
+            continue
+        d = dev(torch_cuda, c.dicts[dname])
+        mb.localize(d.data_ptr(), c.dicts[dname].size)
+        got = {"remapped_idx": mb.read("remapped"), "new_offset": mb.read("new_offset"),
+               "new_index": mb.read("new_index"), "new_value": P.fbits(mb.read("new_value"))}
+        assert got["new_index"].size == info["matched"][dname], dname
+        for k, a in got.items():
+            assert P.same_output(fx, sha, "%s.%s.%s" % (name, dname, k), a), (dname, k)

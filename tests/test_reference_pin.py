@@ -4,12 +4,13 @@ The chain behind every bit-exactness claim is GPU kernel == CPU restatement
 == reference.  This file tests the second link:
 
 recorded  tests/golden/reference_pin/*.npz hold what the reference's own
-          match / oldMatch / sliceKeyOrderedMsg / evenDivide, FTRLModel and
-          FreqencyFilter (compiled in place, oracle/ref_*_shim.cc) returned
+          match / oldMatch / sliceKeyOrderedMsg / evenDivide, FTRLModel,
+          FreqencyFilter, AUC, Evaluation<double>::auc and Localizer
+          (compiled in place, oracle/ref_*_shim.cc) returned
           on the fixed inputs of tests/pin_cases.py, written by
           tools/record_reference.py.  Every restatement must reproduce them
           bit for bit.  These tests always run.
-live      where oracle/_ref holds the three libraries (the reference tree was
+live      where oracle/_ref holds the libraries (the reference tree was
           present when `make -C oracle` ran), seeded cases beyond the
           fixtures run the reference's code and the restatement side by side.
           Elsewhere they skip, naming the library.
@@ -20,10 +21,12 @@ import os
 import numpy as np
 import pytest
 
+import auc_ref as A
 import ftrl_ref as F
 import oracle_py as O
 import pin_cases as P
 import ref_py as R
+import worker_ref as W
 from test_freq_filter import py_insert, py_query
 
 
@@ -49,8 +52,9 @@ def test_unmix64_inverts_fmix64():
 
 def test_fixtures_are_small_and_say_their_source():
     names = sorted(os.listdir(P.GOLDEN))
-    assert names == ["countmin.npz", "even_divide.npz", "fold_F1_r0.npz", "fold_F2_r0.npz",
-                     "fold_F2_r1.npz", "fold_F3_r0.npz", "ftrl_parity.npz", "ftrl_steep.npz"]
+    assert names == ["auc.npz", "auc_merge.npz", "countmin.npz", "even_divide.npz",
+                     "exact_auc.npz", "fold_F1_r0.npz", "fold_F2_r0.npz", "fold_F2_r1.npz",
+                     "fold_F3_r0.npz", "ftrl_parity.npz", "ftrl_steep.npz", "localizer.npz"]
     for n in names:
         assert os.path.getsize(os.path.join(P.GOLDEN, n)) <= 128 * 1024, n
         meta, arrays = P.load_fixture(n[:-4])
@@ -213,7 +217,312 @@ def test_countmin_recorded(n, k):
         assert np.array_equal(py_query(tp, nn, kk, c.query.tolist(), freq), want)
 
 
+# ----------------------------------------------------------------------- AUC
+AUC_PARTS = ("tp_key", "tp_count", "fp_key", "fp_count")
+_auc_cache = {}
+
+
+def auc_cases():
+    if not _auc_cache:
+        _auc_cache.update({c.name: c for c in P.auc_cases()})
+    return _auc_cache
+
+
+def fb(v):
+    """A double's bits as the fixtures spell them; every NaN is one value
+    (0 / 0 carries no payload worth keeping, and its sign differs by platform)."""
+    return "nan" if math.isnan(v) else "%016x" % int(P.fbits(np.array([v], np.float64))[0])
+
+
+def recorded_double(hexbits):
+    return fb(float(np.array([int(hexbits, 16)], np.uint64).view(np.float64)[0]))
+
+
+def same_aucdata(fx, sha, name, data):
+    return all(P.same_output(fx, sha, "%s.%s" % (name, part), a) for part, a in zip(AUC_PARTS, data))
+
+
+def test_auc_cases_cover_what_they_claim():
+    cases = auc_cases()
+    assert len(cases) == len(P.pin_sizes()) * len(P.AUC_GOODNESS) + len(P.AUC_GOODNESS)
+    assert {1, 10, 1000, 100000, -1000} <= set(P.AUC_GOODNESS)
+    assert P.pin_sizes() == (1, P.PIN_TILE - 1, P.PIN_TILE, P.PIN_TILE + 1, 3 * P.PIN_TILE + 5)
+    for c in cases.values():
+        with np.errstate(all="ignore"):
+            prod = c.p * np.float64(c.g)
+        undefined = ~(np.abs(prod) < 2.0 ** 63)
+        assert undefined.any() == c.name.startswith("undefined"), c.name
+        if c.y.size > 100:
+            assert {b for b in P.fbits(c.y).tolist()} == {b for b in P.fbits(P.AUC_LABELS).tolist()}
+            assert ((prod > -1) & (prod < 0)).any()
+            if not c.name.startswith("undefined"):
+                assert (P.fbits(c.p) == np.uint64(1 << 63)).any() and (np.abs(prod) == 1e18).sum() == 2
+                assert ((np.abs(c.p) < 2.3e-308) & (c.p != 0)).sum() == 4  # the denormals
+    # the decimals do what their comment says, at the goodness that shows it
+    assert 0.29 * 100 < 29 and 0.57 * 100 < 57 and 0.1 * 10 == 1 == 0.7 * 10 / 7 and 4.35 * 100 < 435
+    assert 0.58 * 100 < 58 and 1.15 * 100 < 115 and 16.08 * 100 < 1608 and 0.029 * 1000 == 29
+
+
+@pytest.mark.parametrize("name", [c.name for c in P.auc_cases()])
+def test_auc_compute_recorded(name):
+    c = auc_cases()[name]
+    meta, fx = P.load_fixture("auc")
+    info = meta["cases"][name]
+    assert meta["tile"] == P.PIN_TILE and info["input_sha256"] == c.digest()
+    for compute in (A.scalar_compute, A.vector_compute):
+        data = compute(c.y, c.p, c.g)
+        assert (data[0].size, data[2].size) == (info["ntp"], info["nfp"])
+        assert same_aucdata(fx, meta["sha256"], name, data), compute.__name__
+
+
+def test_auc_probe_of_the_issue():
+    """0.29 * 100 -> 28, 0.7 * 100 -> 70, -0.005 * 100 -> 0; the restatement's
+    rule is held to the recorded cases above, this is the rule by hand."""
+    assert [A.scalar_key(p, 100) for p in (0.29, 0.7, -0.005)] == [28, 70, 0]
+    assert A.vector_keys(np.array([0.29, 0.7, -0.005]), 100).tolist() == [28, 70, 0]
+
+
+def test_auc_undefined_conversions_recorded():
+    """include/psg.h: a product that is NaN or of magnitude >= 2^63 "gets the
+    key INT64_MIN, which is what the reference's x86-64 build produces".  The
+    fixture holds what the reference's compiled compute returned for each such
+    prediction on its own."""
+    _, fx = P.load_fixture("auc")
+    for g in P.AUC_GOODNESS:
+        want = fx["undefined_g%d.single_keys" % g]
+        bad = P.auc_undefined(g)
+        assert want.size == bad.size and (want == A.INT64_MIN).all()
+        assert [A.scalar_key(p, g) for p in bad.tolist()] == want.tolist()
+        assert np.array_equal(A.vector_keys(bad, g), want)
+
+
+MERGE_NAMES = sorted(P.auc_merge_sequences())
+# sequences in which a side holds zero counts only: the reference's map is not
+# empty() there and evaluate divides 0 by 0, the product has dropped the
+# entries and returns .5 (include/psg.h, defined deviation)
+ZERO_ONLY = {"zero_only_negatives", "zero_only_both"}
+
+
+def merged_maps(name):
+    """(goodness, the merge's inputs, the reference's two maps as recorded --
+    zero counts included --, meta of the sequence)."""
+    g, datas = P.auc_merge_sequences()[name]
+    meta, fx = P.load_fixture("auc_merge")
+    info = meta["sequences"][name]
+    assert info["input_sha256"] == P.auc_sequence_digest(g, datas) and info["goodness"] == g
+    assert meta["thresholds"] == list(P.AUC_THRESHOLDS)
+    maps = tuple(fx["%s.%s" % (name, part)] for part in AUC_PARTS)  # all small enough to be held
+    assert same_aucdata(fx, meta["sha256"], name, maps)
+    return g, datas, maps, info
+
+
+@pytest.mark.parametrize("name", MERGE_NAMES)
+def test_auc_merge_recorded(name):
+    from parameter_server_amd.auc import accuracy_data, evaluate_data
+    g, datas, maps, info = merged_maps(name)
+    kept = P.auc_without_zeros(maps)
+    assert info["zero_count_entries"] == sum(m.size for m in maps[::2]) - sum(k.size for k in kept[::2])
+    assert (info["zero_count_entries"] > 0) == name.startswith("zero_")
+    # merge: the restatements drop zero counts as the product does, and are
+    # the reference's maps in everything else
+    for merge in (A.scalar_merge, A.vector_merge):
+        assert A.same_data(merge(datas), kept), merge.__name__
+    # accuracy and evaluate() as written: on the reference's own maps (the
+    # zero counts in) the restatements and the library's host functions are
+    # the reference's bits ...
+    for th, want in zip(P.AUC_THRESHOLDS, info["accuracy_bits"]):
+        for data in (maps, kept):  # ... and a zero count adds 0 to both sums
+            assert recorded_double(want) == fb(A.scalar_accuracy(data, g, th)) \
+                == fb(A.vector_accuracy(data, g, th)) == fb(accuracy_data(g, *data, threshold=th))
+    want = recorded_double(info["evaluate_bits"])
+    assert want == fb(A.scalar_evaluate(maps, True)) == fb(A.vector_evaluate(maps, True)) \
+        == fb(evaluate_data(*maps, as_written=True))
+    # PSG_AUC_BY_KEY has no reference: it stays on the two restatements
+    # (tests/test_auc.py)
+    dropped = [fb(f(kept, True)) for f in (A.scalar_evaluate, A.vector_evaluate)] \
+        + [fb(evaluate_data(*kept, as_written=True))]
+    if name in ZERO_ONLY:  # both sides of the boundary
+        assert want == "nan" and dropped == [fb(0.5)] * 3
+        assert kept[0].size == 0 or kept[2].size == 0
+    else:
+        assert dropped == [want] * 3
+        assert want != "nan"
+
+
+def test_auc_merge_sequences_cover_what_they_claim():
+    seq = P.auc_merge_sequences()
+    assert len(seq["three_workers"][1]) == 3
+    tk = np.concatenate([d[0] for d in seq["repeated_keys"][1]])
+    assert np.unique(tk).size < tk.size and np.any(np.diff(tk) < 0)
+    assert any((d[1] == 0).any() and (d[3] == 0).any() for d in seq["zero_counts"][1])
+    assert all(d[2].size == 0 for d in seq["no_negatives"][1])
+    assert all(d[0].size == 0 for d in seq["no_positives"][1])
+    # the double sums are order-sensitive: the counts add up past 2^53
+    assert sum(int(d[1].sum()) for d in seq["three_workers"][1]) > 1 << 53
+    # (double)key rounds onto x = threshold * goodness on both sides of it
+    g, (d,) = seq["keys_past_2p53"]
+    x = 0.5 * g
+    assert float(int(x) - 1) == x == float(int(x) + 1) and int(x) - 1 in d[0].tolist()
+
+
+@pytest.mark.parametrize("name", [c.name for c in P.exact_auc_cases()])
+def test_exact_auc_recorded(name):
+    cases = P.exact_auc_cases()
+    meta, fx = P.load_fixture("exact_auc")
+    i = [c.name for c in cases].index(name)
+    c = cases[i]
+    assert meta["cases"][name]["input_sha256"] == c.digest() and list(meta["cases"]) == sorted(
+        x.name for x in cases)
+    want = recorded_double("%016x" % int(fx["bits"][i]))
+    assert (want == "nan") == (c.y.size == 1)  # one class absent: 0 / 0
+    assert want == fb(A.scalar_exact(c.y, c.p)) == fb(A.vector_exact(c.y, c.p))
+    # the result must not depend on how equal predictions are ordered: every
+    # run of equal predictions (-0.0 == +0.0) is of one class
+    o = np.argsort(c.p, kind="stable")
+    p, pos = c.p[o], c.y[o] > 0
+    tie = p[1:] == p[:-1]
+    assert np.array_equal(pos[1:][tie], pos[:-1][tie])
+    assert tie.any() == name.startswith("ties") or c.y.size == 1
+    assert (c.p < 0).any() or c.y.size == 1
+
+
+# ----------------------------------------------------------------- localizer
+LOC_OUT = ("new_offset", "new_index", "new_value", "remapped_idx")
+_loc_cache = {}
+
+
+def loc(name):
+    if name not in _loc_cache:
+        _loc_cache[name] = P.loc_case(name)
+    return _loc_cache[name]
+
+
+def restated_localizer(c, form):
+    """{key: array} as tools/record_reference.py names the outputs."""
+    count, remap = {"scalar": (W.scalar_count_uniq, W.scalar_remap),
+                    "vector": (W.vector_count_uniq, W.vector_remap)}[form]
+    skey, spos, uniq, cnt = count(c.index)
+    out = {"uniq_idx": uniq, "idx_frq": cnt}
+    for dname, dic in c.dicts.items():
+        no, ni, nv, rm = remap(c.offset, c.index, c.value, dic, skey, spos)
+        for k, a in zip(LOC_OUT, (no, ni, P.fbits(np.asarray(nv, np.float64)), rm)):
+            out["%s.%s" % (dname, k)] = a
+    return out
+
+
+@pytest.mark.parametrize("form", ("scalar", "vector"))
+@pytest.mark.parametrize("name", P.LOC_NAMES)
+def test_localizer_recorded(name, form):
+    c = loc(name)
+    meta, fx = P.load_fixture("localizer")
+    info = meta["cases"][name]
+    assert meta["tile"] == P.PIN_TILE and info["input_sha256"] == c.digest()
+    assert (info["nnz"], info["rows"], info["binary"]) == (c.index.size, c.offset.size - 1,
+                                                           c.value is None)
+    got = restated_localizer(c, form)
+    assert got["uniq_idx"].size == info["n_uniq"]
+    for k in ("uniq_idx", "idx_frq"):
+        assert P.same_output(fx, meta["sha256"], "%s.%s" % (name, k), got[k]), k
+    assert sorted(info["matched"]) == sorted(c.dicts)
+    for dname, matched in info["matched"].items():
+        if dname == "empty":
+            # the reference returns a null pointer (localizer.h:114); an empty
+            # Z is the product's own defined deviation (include/psg.h)
+            assert matched is None and got["empty.new_index"].size == 0
+            assert not any(k.startswith("%s.empty." % name) for k in meta["sha256"])
+            continue
+        assert matched == got[dname + ".new_index"].size
+        for k in LOC_OUT:
+            assert P.same_output(fx, meta["sha256"], "%s.%s.%s" % (name, dname, k),
+                                 got["%s.%s" % (dname, k)]), (dname, k)
+
+
+def test_localizer_cases_cover_what_they_claim():
+    meta, _ = P.load_fixture("localizer")
+    T = P.PIN_TILE
+    assert [loc(n).index.size for n in P.LOC_NAMES] == [1, T - 1, T, T + 1, 3 * T + 5, 40000, 40000]
+    assert meta["threads"] == [1, 4] and 40000 > 4 * (16 * 1024) // 2  # past parallelSort's grain
+    assert 40000 // 4 + 5 < 16 * 1024 < 40000  # the grain is 16,384: 40,000 pairs split at least once
+    for name in P.LOC_NAMES:
+        c = loc(name)
+        uniq, cnt = np.unique(c.index, return_counts=True)
+        lens = np.diff(c.offset.astype(np.int64))
+        if lens.size >= 3:
+            assert lens[0] == lens[lens.size // 2] == lens[-1] == 0
+        assert (uniq > np.uint64(1 << 63)).any() or name == "L1"
+        if name in ("Tm1", "Tp1", "3Tp5", "L40000"):
+            assert cnt.max() > 64
+        if name in ("T", "D40000"):
+            assert cnt.max() == 1
+        m = meta["cases"][name]["matched"]
+        assert m["all"] == m["absent"] == c.index.size and (0 < m["third"] < c.index.size or name == "L1")
+        if "below" in m:
+            assert m["below"] == m["above"] == 0
+            assert c.dicts["below"].max() < uniq[0] and c.dicts["above"].min() > uniq[-1]
+            assert c.dicts["absent"][0] < uniq[0] and c.dicts["absent"][-1] > uniq[-1]
+        assert c.dicts["absent"].size > uniq.size or name == "L1"
+    assert {0, P.U64 - 1} <= set(loc("3Tp5").index.tolist())
+    assert loc("Tp1").offset.size == 2 and loc("L1").offset.size == 2  # single-row cases
+    assert {n for n in P.LOC_NAMES if loc(n).value is None} == {"T", "Tp1", "D40000"}
+    # too large for the cap: held as a digest only
+    _, fx = P.load_fixture("localizer")
+    assert "L40000.all.new_index" not in fx and "L40000.all.new_index" in meta["sha256"]
+
+
 # ---------------------------------------------------------------------- live
+@pytest.mark.parametrize("seed", range(8))
+def test_live_auc(seed):
+    need("auc")
+    c = P.random_auc_case(seed)
+    want = R.auc_compute(c.y, c.p, c.g)
+    assert A.same_data(want, A.scalar_compute(c.y, c.p, c.g))
+    assert A.same_data(want, A.vector_compute(c.y, c.p, c.g))
+    # a root over the case in three workers' pieces and one list with zero counts
+    n = c.y.size
+    cuts = [0, n // 3, n // 2, n]
+    datas = [R.auc_compute(c.y[a:b], c.p[a:b], c.g) for a, b in zip(cuts, cuts[1:]) if b > a]
+    datas.append((want[0][::-1], np.zeros(want[0].size, np.uint64), want[2], want[3]))
+    root = R.RefAUC(c.g)
+    for d in datas:
+        root.merge(*d)
+    maps = root.maps()
+    kept = P.auc_without_zeros(maps)
+    assert A.same_data(kept, A.scalar_merge(datas)) and A.same_data(kept, A.vector_merge(datas))
+    from parameter_server_amd.auc import accuracy_data, evaluate_data
+    for th in P.AUC_THRESHOLDS + (1.0, -20.0):
+        assert fb(root.accuracy(th)) == fb(A.scalar_accuracy(maps, c.g, th)) \
+            == fb(A.vector_accuracy(kept, c.g, th)) == fb(accuracy_data(c.g, *kept, threshold=th))
+    assert fb(root.evaluate()) == fb(A.scalar_evaluate(maps, True)) \
+        == fb(A.vector_evaluate(maps, True)) == fb(evaluate_data(*maps, as_written=True))
+    # Evaluation<double>::auc on a tie-free input of the same size
+    p = (np.argsort(P.splitmix64(seed, n), kind="stable") - n // 2) * 0.25
+    assert fb(R.exact_auc(c.y, p)) == fb(A.scalar_exact(c.y, p)) == fb(A.vector_exact(c.y, p))
+
+
+@pytest.mark.parametrize("threads", (1, 2, 4))
+@pytest.mark.parametrize("seed", range(8))
+def test_live_localizer(seed, threads):
+    need("localizer")
+    c = P.random_loc_case(seed)
+    ref = R.RefLocalizer()
+    uniq, frq = ref.count_uniq(c.index, threads)
+    tag = np.arange(c.index.size, dtype=np.float64)
+    for form in ("scalar", "vector") if c.index.size <= 20000 else ("vector",):
+        got = restated_localizer(c, form)
+        assert same(got["uniq_idx"], uniq) and same(got["idx_frq"], frq)
+        for dname, dic in c.dicts.items():
+            res = ref.remap(c.offset, c.index, c.value, dic, threads)
+            if dname == "empty":
+                assert res is None
+                continue
+            no, ni, nv = res
+            assert same(got[dname + ".new_offset"], no) and same(got[dname + ".new_index"], ni)
+            assert same(got[dname + ".new_value"], P.fbits(nv))
+            tagged = ref.remap(c.offset, c.index, tag, dic, threads)
+            assert same(got[dname + ".remapped_idx"],
+                        P.remapped_from_tagged(c.index.size, tagged[1], tagged[2]))
+
+
 @pytest.mark.parametrize("seed", range(8))
 def test_live_fold(seed):
     need("match")
@@ -272,6 +581,33 @@ def test_live_fixtures_reproduce():
             assert rc == 0 and [lo, hi] == meta["positions"]
             for i in range(c.m):
                 assert np.array_equal(P.fbits(got[i]), fx["%s%d" % (mode, i)])
+    # the AUC and localizer fixtures: recorded again, nothing written
+    need("auc")
+    need("localizer")
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "record_reference", os.path.join(R.ROOT, "tools", "record_reference.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    again = {}
+    keep, rec.P.save_fixture = rec.P.save_fixture, lambda name, meta, arrays: again.update(
+        {name: (meta, arrays)})
+    try:
+        rec.record_auc()
+        rec.record_localizer()
+    finally:
+        rec.P.save_fixture = keep
+    assert sorted(again) == ["auc", "auc_merge", "exact_auc", "localizer"]
+    for name, (meta, arrays) in again.items():
+        wmeta, warrays = P.load_fixture(name)
+        assert json_round(meta) == wmeta and sorted(arrays) == sorted(warrays), name
+        assert all(same(arrays[k], warrays[k]) and arrays[k].dtype == warrays[k].dtype
+                   for k in arrays), name
+
+
+def json_round(meta):
+    import json
+    return json.loads(json.dumps(meta, sort_keys=True))
 
 
 @pytest.mark.parametrize("seed", range(1, 5))

@@ -1,8 +1,9 @@
 """CPU: the worker step's restatement (tests/worker_ref.py) and its binding.
 
-The restatement is this feature's oracle and it is not pinned to the
-reference's compiled code (worker_ref.py says why), so it is held to itself
-here: its two independent forms must agree bit for bit on every case the GPU
+The restatement is this feature's oracle.  Its localizer part is pinned to
+the reference's compiled code in tests/test_reference_pin.py; countKeys,
+rangeTimes and LogitLoss are not (worker_ref.py says why), so the whole of it
+is also held to itself here: its two independent forms must agree bit for bit on every case the GPU
 tests use, its sums must be order-sensitive enough for a bit-exact
 comparison to mean something, and its case generators must take every branch
 the GPU tests name."""

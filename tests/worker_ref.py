@@ -1,10 +1,15 @@
 """CPU restatements of the reference's online worker step, for the worker tests.
 
-This is a RESTATEMENT, not the reference's compiled code: loss.h needs Eigen
-and localizer.h needs protobuf and slot_reader.h, neither of which is in the
-image, so this row of the oracle is unpinned.  To make
-up for it there are two independent forms that must agree bit for bit
-(tests/test_worker.py):
+This is a RESTATEMENT.  Its localizer part (count_uniq, remap) is held to
+the reference's compiled code: localizer.h is compiled in place into
+oracle/_ref/libref_localizer.so, what it returns is recorded in
+tests/golden/reference_pin/localizer.npz, and tests/test_reference_pin.py
+holds both forms below to the recording bit for bit; only the order of
+positions within a run of equal ids has no reference (std::sort leaves it
+open; both forms are stable, as the product is).  The rest is unpinned
+(DESIGN.md section 7): loss.h and base/matrix.h need Eigen, and countKeys
+lives in ftrl.cc, which needs the whole solver.  There are two independent
+forms that must agree bit for bit (tests/test_worker.py):
 
 ``scalar_*``  Python ints and floats (IEEE binary64, one correctly rounded
               operation per operator), loops in the reference's own order,

@@ -2,8 +2,8 @@
 """Record the reference's own outputs into tests/golden/reference_pin/.
 
 Runs the reference's code compiled in place (oracle/_ref/libref_match.so,
-libref_ftrl.so, libref_countmin.so -- `make -C oracle` with the reference
-tree present) on the fixed inputs of tests/pin_cases.py and stores what it
+libref_ftrl.so, libref_countmin.so, libref_auc.so, libref_localizer.so --
+`make -C oracle` with the reference tree present) on the fixed inputs of tests/pin_cases.py and stores what it
 returns as data-only fixtures (numpy .npz: little-endian arrays and a JSON
 `meta` holding parameters, digests and the source).  Run by hand when the
 cases change; no test calls it.  A fixture is never edited to fit: if a
@@ -31,6 +31,11 @@ SOURCE = {
             "in place (oracle/ref_ftrl_shim.cc)",
     "countmin": "reference src/parameter/frequency_filter.h with src/base/countmin.h compiled in "
                 "place (oracle/ref_countmin_shim.cc)",
+    "auc": "reference src/base/auc.h (setGoodness, compute, merge, accuracy, evaluate) and "
+           "src/base/evaluation.h (Evaluation<double>::auc) compiled in place "
+           "(oracle/ref_auc_shim.cc)",
+    "localizer": "reference src/base/localizer.h (countUniqIndex, remapIndex) over "
+                 "src/util/parallel_sort.h compiled in place (oracle/ref_localizer_shim.cc)",
 }
 
 
@@ -157,6 +162,94 @@ def record_countmin():
     P.save_fixture("countmin", meta, arrays)
 
 
+def hexbits(v):
+    return "%016x" % int(P.fbits(np.array([v], np.float64))[0])
+
+
+def record_auc():
+    """auc.npz: compute's AUCData per case; auc_merge.npz: the root's maps,
+    accuracy and evaluate per merge sequence; exact_auc.npz: Evaluation::auc."""
+    arrays, sha, cases = {}, {}, {}
+    for c in P.auc_cases():
+        tk, tc, fk, fc = R.auc_compute(c.y, c.p, c.g)
+        assert int(tc.sum()) + int(fc.sum()) == c.y.size
+        for part, a in (("tp_key", tk), ("tp_count", tc), ("fp_key", fk), ("fp_count", fc)):
+            P.record_output(arrays, sha, "%s.%s" % (c.name, part), a)
+        cases[c.name] = {"input_sha256": c.digest(), "n": int(c.y.size), "goodness": c.g,
+                         "ntp": int(tk.size), "nfp": int(fk.size)}
+    # what this build of the reference returns for each undefined conversion
+    # on its own (one positive example): the key of its only entry
+    for g in P.AUC_GOODNESS:
+        keys = [int(R.auc_compute([1.0], [p], g)[0][0]) for p in P.auc_undefined(g)]
+        arrays["undefined_g%d.single_keys" % g] = np.array(keys, np.int64)
+    P.save_fixture("auc", {"source": SOURCE["auc"], "tile": P.PIN_TILE, "cases": cases,
+                           "goodness": list(P.AUC_GOODNESS), "sha256": sha}, arrays)
+
+    arrays, sha, seqs = {}, {}, {}
+    for name, (g, datas) in P.auc_merge_sequences().items():
+        root = R.RefAUC(g)
+        for d in datas:
+            root.merge(*d)
+        maps = root.maps()
+        for part, a in zip(("tp_key", "tp_count", "fp_key", "fp_count"), maps):
+            P.record_output(arrays, sha, "%s.%s" % (name, part), a)
+        seqs[name] = {"input_sha256": P.auc_sequence_digest(g, datas), "goodness": g,
+                      "accuracy_bits": [hexbits(root.accuracy(t)) for t in P.AUC_THRESHOLDS],
+                      "evaluate_bits": hexbits(root.evaluate()),
+                      "zero_count_entries": int((maps[1] == 0).sum() + (maps[3] == 0).sum())}
+    P.save_fixture("auc_merge", {"source": SOURCE["auc"], "thresholds": list(P.AUC_THRESHOLDS),
+                                 "sequences": seqs, "sha256": sha}, arrays)
+
+    cases = P.exact_auc_cases()
+    bits = np.array([int(hexbits(R.exact_auc(c.y, c.p)), 16) for c in cases], np.uint64)
+    P.save_fixture("exact_auc", {"source": SOURCE["auc"], "tile": P.PIN_TILE,
+                                 "cases": {c.name: {"input_sha256": c.digest(), "n": int(c.y.size)}
+                                           for c in cases}}, {"bits": bits})
+
+
+def run_localizer(c, threads):
+    """{key: array} of everything the reference returns for case c, and
+    {dictionary: matched, or None where remapIndex returns a null pointer}."""
+    loc = R.RefLocalizer()
+    uniq, frq = loc.count_uniq(c.index, threads)
+    out, matched = {"uniq_idx": uniq, "idx_frq": frq}, {}
+    tag = np.arange(c.index.size, dtype=np.float64)
+    for dname in sorted(c.dicts):
+        res = loc.remap(c.offset, c.index, c.value, c.dicts[dname], threads)
+        tagged = loc.remap(c.offset, c.index, tag, c.dicts[dname], threads)
+        if res is None:
+            assert tagged is None
+            matched[dname] = None
+            continue
+        no, ni, nv = res
+        assert np.array_equal(tagged[0], no) and np.array_equal(tagged[1], ni)
+        assert nv.size == (0 if c.value is None else ni.size)
+        matched[dname] = int(ni.size)
+        out[dname + ".new_offset"], out[dname + ".new_index"] = no, ni
+        out[dname + ".new_value"] = P.fbits(nv)
+        out[dname + ".remapped_idx"] = P.remapped_from_tagged(c.index.size, tagged[1], tagged[2])
+    return out, matched
+
+
+def record_localizer():
+    arrays, sha, cases = {}, {}, {}
+    for name in P.LOC_NAMES:
+        c = P.loc_case(name)
+        out, matched = run_localizer(c, P.LOC_THREADS[0])
+        for t in P.LOC_THREADS[1:]:  # the thread count must not show
+            other, om = run_localizer(c, t)
+            assert om == matched and sorted(other) == sorted(out)
+            assert all(np.array_equal(out[k], other[k]) for k in out), (name, t)
+        for k, a in out.items():
+            P.record_output(arrays, sha, "%s.%s" % (name, k), a)
+        cases[name] = {"input_sha256": c.digest(), "nnz": int(c.index.size),
+                       "rows": int(c.offset.size - 1), "binary": c.value is None,
+                       "n_uniq": int(out["uniq_idx"].size), "matched": matched}
+    P.save_fixture("localizer", {"source": SOURCE["localizer"], "tile": P.PIN_TILE,
+                                 "threads": list(P.LOC_THREADS), "cases": cases, "sha256": sha},
+                   arrays)
+
+
 def main():
     for which in R.LIBS:
         if not R.available(which):
@@ -166,6 +259,8 @@ def main():
     record_fold(bounds8)
     record_ftrl()
     record_countmin()
+    record_auc()
+    record_localizer()
     for f in sorted(os.listdir(P.GOLDEN)):
         size = os.path.getsize(os.path.join(P.GOLDEN, f))
         print("%-28s %7d bytes" % (f, size))
