@@ -207,6 +207,16 @@ int psg_received(psg_ctx* ctx, int time, int m, void* const* out);
  * allowed); PSG_ERR_UNSORTED otherwise. */
 int psg_gather(psg_ctx* ctx, int chl, const uint64_t* keys, size_t n,
                void* out, size_t* matched);
+/* The pull reply's value part as Van::send puts it on the wire (van.cc:121-131,
+ * SArray::compressTo, shared_array_inl.h:244-256): psg_gather's n values,
+ * snappy-compressed on the device (psg_snappy_compress_dev), and only the
+ * stream's *out_bytes bytes copied to `out`.  Decoded, they are exactly what
+ * psg_gather writes for the same request (n == 0: the one-byte stream of an
+ * empty part).  cap below psg_snappy_max_compressed_length(n values' bytes)
+ * is PSG_ERR_SIZE before anything runs; unsorted keys are PSG_ERR_UNSORTED
+ * and nothing is written. */
+int psg_gather_compressed(psg_ctx* ctx, int chl, const uint64_t* keys, size_t n, void* out,
+                          size_t cap, size_t* out_bytes, size_t* matched);
 
 /* ------------------------------------------------------------------ */
 /* Device-array forms of the server context: push and pull for        */
@@ -1073,6 +1083,34 @@ int psg_snappy_uncompress_dev(const uint8_t* src, const uint64_t* soff, uint64_t
                               uint8_t* dst, const uint64_t* doff, int32_t* status,
                               void* stream);
 int psg_snappy_uncompressed_length(const void* src, size_t n, size_t* len);
+
+/* snappy raw-format compression of device-resident message parts: what
+ * Van::send does per key and value part (van.cc:121-131,
+ * SArray::compressTo, shared_array_inl.h:244-256), for nparts parts in one
+ * call.  Part i is src[soff[i], soff[i+1]); its stream is written
+ * contiguously from dst + doff[i] and its length to clen[i].  The stream is a
+ * pure function of the part's bytes (the rule of DESIGN.md 4.12: 64 KB
+ * fragments, literal / copy-1 / copy-2 elements, never a copy-4), whatever
+ * the launch holds besides; it is a valid snappy stream, not libsnappy's own.
+ * It never exceeds psg_snappy_max_compressed_length(part bytes) =
+ * 32 + n + n / 6 (snappy::MaxCompressedLength): providing that much room at
+ * doff[i] is the caller's duty (the sizes are on the device, so the host
+ * cannot check it), and nothing is written past the stream's end.  A part of
+ * 4 GiB or more gets clen[i] = 0 and no stream (the preamble is a 32-bit
+ * varint).  soff[nparts + 1], doff[nparts] and clen[nparts] are device arrays;
+ * `scratch` is device memory of psg_snappy_compress_scratch_bytes(the parts'
+ * total bytes, nparts) bytes, 256-byte aligned, free again once the call's
+ * work on `stream` has run.  Enqueued on `stream`: waits for nothing and
+ * allocates nothing.
+ * psg_snappy_compress_host is the same rule in plain C++ on host memory and
+ * gives the same stream byte for byte; cap below the maximum length is
+ * PSG_ERR_SIZE. */
+size_t psg_snappy_max_compressed_length(size_t n);
+size_t psg_snappy_compress_scratch_bytes(size_t total_src_bytes, uint64_t nparts);
+int psg_snappy_compress_dev(const uint8_t* src, const uint64_t* soff, uint64_t nparts,
+                            uint8_t* dst, const uint64_t* doff, uint64_t* clen, void* scratch,
+                            void* stream);
+int psg_snappy_compress_host(const void* src, size_t n, void* dst, size_t cap, size_t* len);
 int psg_crc32c_dev(const void* data, const uint64_t* off, uint64_t nseg,
                    uint64_t max_len, const uint32_t* init, uint32_t* out,
                    void* stream);

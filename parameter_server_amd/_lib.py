@@ -148,6 +148,7 @@ SIGNATURES = {
     "psg_received_shape": (C.c_int, [_p, C.c_int, C.POINTER(C.c_int), _psz, _psz]),
     "psg_received": (C.c_int, [_p, C.c_int, C.c_int, C.POINTER(_p)]),
     "psg_gather": (C.c_int, [_p, C.c_int, _p, _sz, _p, _psz]),
+    "psg_gather_compressed": (C.c_int, [_p, C.c_int, _p, _sz, _p, _sz, _psz, _psz]),
     "psg_push_dev": (C.c_int, [_p, C.c_int, C.c_int, _u64, _u64, _p, _sz, C.c_int,
                                C.POINTER(_p), _sz, _p]),
     "psg_pull_dev": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p, _p]),
@@ -170,6 +171,10 @@ SIGNATURES = {
     "psg_crc32c_dev": (C.c_int, [_p, _p, _u64, _u64, _p, _p, _p]),
     "psg_snappy_uncompress_dev": (C.c_int, [_p, _p, _u64, _p, _p, _p, _p]),
     "psg_snappy_uncompressed_length": (C.c_int, [_p, _sz, _psz]),
+    "psg_snappy_max_compressed_length": (_sz, [_sz]),
+    "psg_snappy_compress_scratch_bytes": (_sz, [_sz, _u64]),
+    "psg_snappy_compress_dev": (C.c_int, [_p, _p, _u64, _p, _p, _p, _p, _p]),
+    "psg_snappy_compress_host": (C.c_int, [_p, _sz, _p, _sz, _psz]),
     "psg_freq_resize": (C.c_int, [_p, C.c_int, C.c_int, C.c_int]),
     "psg_freq_clear": (C.c_int, [_p, C.c_int]),
     "psg_freq_empty": (C.c_int, [_p, C.c_int, C.POINTER(C.c_int)]),

@@ -218,6 +218,19 @@ class KVVector {
     msg->addValue(out);
   }
 
+  // getValue with the reply's value part as Van::send puts it on the wire
+  // (van.cc:121-131, SArray::compressTo): the snappy stream of the gathered
+  // values, made on the device; only its bytes cross PCIe
+  std::vector<char> getValueCompressed(const MessagePtr& msg, size_t* matched = nullptr) {
+    const auto& k = msg->key;
+    std::vector<char> out(psg_snappy_max_compressed_length(k.size() * sizeof(V)));
+    size_t nbytes = 0;
+    check(psg_gather_compressed(ctx_.get(), msg->task.key_channel, k.data(), k.size(), out.data(),
+                                out.size(), &nbytes, matched));
+    out.resize(nbytes);
+    return out;
+  }
+
   // snappy-compressed parts off the wire (Van::recv, van.cc:204-214)
   void setValueCompressed(const Task& t, const std::vector<char>& ckeys,
                           const std::vector<std::vector<char>>& cvals) {

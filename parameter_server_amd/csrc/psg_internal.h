@@ -369,6 +369,15 @@ hipError_t launch_snappy(const uint8_t* src, const uint64_t* soff, uint64_t nmsg
                          void* scratch, hipStream_t stream, unsigned long long* nbad,
                          bool pairs = false);
 
+// snappy raw-format compression (psg_snappy_enc.hip; the rule is
+// psg_snappy_enc.h's): part i = src[soff[i], soff[i+1]) -> its stream at
+// dst + doff[i], clen[i] bytes.  scratch: snappy_compress_scratch_bytes of the
+// parts' total size (device).  Three launches on `stream`, no wait.
+size_t snappy_compress_scratch_bytes(size_t total_src_bytes, uint64_t nparts);
+hipError_t launch_snappy_compress(const uint8_t* src, const uint64_t* soff, uint64_t nparts,
+                                  uint8_t* dst, const uint64_t* doff, uint64_t* clen,
+                                  void* scratch, hipStream_t stream);
+
 // CRC-32C (psg_crc32c.hip): out[i] = crc32c::Extend(init ? init[i] : 0,
 // data + off[i], min(off[i+1] - off[i], max_len)); all pointers device
 uint64_t crc32c_chunks_per_segment(uint64_t max_len);

@@ -215,6 +215,21 @@ int psg_snappy_uncompress_dev(const uint8_t* src, const uint64_t* soff, uint64_t
   return PSG_OK;
 }
 
+size_t psg_snappy_compress_scratch_bytes(size_t total_src_bytes, uint64_t nparts) {
+  return psg::snappy_compress_scratch_bytes(total_src_bytes, nparts);
+}
+
+int psg_snappy_compress_dev(const uint8_t* src, const uint64_t* soff, uint64_t nparts,
+                            uint8_t* dst, const uint64_t* doff, uint64_t* clen, void* scratch,
+                            void* stream) {
+  if (nparts == 0) return PSG_OK;
+  if (!src || !soff || !dst || !doff || !clen || !scratch)
+    return fail(PSG_ERR_ARG, "null argument");
+  HIP_TRY(psg::launch_snappy_compress(src, soff, nparts, dst, doff, clen, scratch,
+                                      (hipStream_t)stream));
+  return PSG_OK;
+}
+
 int psg_snappy_uncompressed_length(const void* src, size_t n, size_t* len) {
   if (!len || (n && !src)) return fail(PSG_ERR_ARG, "null argument");
   // the preamble: a little-endian base-128 varint of at most 32 bits

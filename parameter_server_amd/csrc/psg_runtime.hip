@@ -999,4 +999,72 @@ int psg_gather(psg_ctx* c, int chl, const uint64_t* keys, size_t n, void* out,
   return PSG_OK;
 }
 
+int psg_gather_compressed(psg_ctx* c, int chl, const uint64_t* keys, size_t n, void* out,
+                          size_t cap, size_t* out_bytes, size_t* matched) {
+  if (!c || !out || !out_bytes || (n && !keys)) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  const size_t sv = vsize(c->dtype), raw = n * sv;
+  const size_t room = psg_snappy_max_compressed_length(raw);
+  if (raw > 0xffffffffull) return fail(PSG_ERR_SIZE, "gather: a value part of %zu bytes", raw);
+  if (cap < room)
+    return fail(PSG_ERR_SIZE, "gather: room for %zu bytes, %zu values may need %zu", cap, n, room);
+  if (matched) *matched = 0;
+  *out_bytes = 0;
+  if (n == 0) {  // the stream of an empty part: its preamble
+    *(uint8_t*)out = 0;
+    *out_bytes = 1;
+    return PSG_OK;
+  }
+  if (int rc = set_dev(c->device)) return rc;
+  Channel& C = c->ch[chl];
+  if (C.n != C.nvals)  // CHECK_EQ(key_[ch].size(), val_[ch].size()) kv_vector.h:220
+    return fail(PSG_ERR_SIZE, "channel %d: %zu keys but %zu values", chl, C.n, C.nvals);
+  // one pooled block: request keys | offsets and clen | values | stream | scratch
+  const size_t o_off = align_up(8 * n, 256), o_val = o_off + 256;
+  const size_t o_dst = o_val + align_up(raw, 256), o_scr = o_dst + align_up(room, 256);
+  const size_t bytes = o_scr + psg::snappy_compress_scratch_bytes(raw, 1);
+  void* blk = nullptr;
+  if (int rc = c->dev_get(bytes, &blk, c->copy)) return rc;
+  char* b = (char*)blk;
+  uint64_t* d_req = (uint64_t*)b;
+  uint64_t* d_off = (uint64_t*)(b + o_off);  // soff[2], doff[1], clen[1]
+  const uint64_t h_off[3] = {0, (uint64_t)raw, 0};
+  int rc = c->h2d(d_req, keys, 8 * n);
+  if (rc == PSG_OK) rc = c->h2d(d_off, h_off, sizeof h_off);
+  if (rc == PSG_OK) rc = c->join_copy();
+  if (rc == PSG_OK) rc = c->chan_order(C, c->stream);
+  hipError_t e = hipSuccess;
+  if (rc == PSG_OK) {
+    e = hipMemsetAsync(c->d_small, 0, 16, c->stream);
+    if (e == hipSuccess) e = psg::launch_check_sorted(d_req, n, c->d_small + 1, c->stream, false);
+    if (e == hipSuccess)
+      e = psg::launch_gather(c->dtype, C.d_keys, C.n, C.d_vals, d_req, n, b + o_val, c->d_small,
+                             c->stream);
+    if (e == hipSuccess)
+      e = psg::launch_snappy_compress((const uint8_t*)b + o_val, d_off, 1, (uint8_t*)b + o_dst,
+                                      d_off + 2, d_off + 3, b + o_scr, c->stream);
+    // the stream's length first, then that many bytes
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(c->h_small, c->d_small, 16, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(c->h_small + 12, d_off + 3, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) rc = fail(PSG_ERR_DEVICE, "gather: %s", hipGetErrorString(e));
+  }
+  const int rf = c->h2d_finish();
+  if (rc == PSG_OK) rc = rf;
+  if (rc == PSG_OK && c->h_small[1]) rc = fail(PSG_ERR_UNSORTED, "gather: request keys not sorted");
+  const size_t len = (size_t)c->h_small[12];
+  if (rc == PSG_OK && (len == 0 || len > room))
+    rc = fail(PSG_ERR_DEVICE, "gather: a stream of %zu bytes for %zu values", len, n);
+  if (rc == PSG_OK) rc = c->d2h(out, b + o_dst, len);
+  if (rc == PSG_OK && (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+    rc = fail(PSG_ERR_DEVICE, "gather: %s", hipGetErrorString(e));
+  c->dev_put(blk, bytes);
+  if (rc) return rc;
+  *out_bytes = len;
+  if (matched) *matched = (size_t)c->h_small[0];
+  return PSG_OK;
+}
+
 }  // extern "C"

@@ -206,6 +206,20 @@ class KVVector:
         msg.value.append(out)
         return matched.value
 
+    def getValueCompressed(self, msg: Message):
+        """getValue with the reply's value part as Van::send puts it on the
+        wire: gathered and snappy-compressed on the device, and only the
+        stream copied back (psg_gather_compressed).  Returns (stream bytes,
+        matched count); msg.value is left alone."""
+        keys = np.ascontiguousarray(msg.key, dtype=np.uint64)
+        cap = self._L.psg_snappy_max_compressed_length(keys.size * np.dtype(self.np_dtype).itemsize)
+        out = np.empty(cap, np.uint8)
+        nbytes, matched = C.c_size_t(), C.c_size_t()
+        _lib.check(self._L.psg_gather_compressed(self._h, msg.key_channel, _ptr(keys), keys.size,
+                                                 _ptr(out), cap, C.byref(nbytes),
+                                                 C.byref(matched)))
+        return out[:nbytes.value].tobytes(), matched.value
+
 
     # -- device-array forms (psg_push_dev / psg_pull_dev / psg_dev_status) --
     def push_dev(self, channel: int, time: int, key_range, keys_dev: int, n: int,
