@@ -349,7 +349,7 @@ int psg_gather_dev(int dtype, const uint64_t* dkeys, uint64_t nd,
                    void* out, unsigned long long* matched, void* stream);
 
 /* Device-resident key union: out = a U b (both strictly increasing, else
- * PSG_ERR_UNSORTED); out must hold na+nb; *nout (host) receives |a U b|.
+ * PSG_ERR_UNSORTED, with nothing stored past out[na+nb)); out must hold na+nb; *nout (host) receives |a U b|.
  * The N-way merge of psg_nway_* with two pushes.  Synchronises. */
 int psg_key_union_dev(const uint64_t* a, uint64_t na, const uint64_t* b,
                       uint64_t nb, uint64_t* out, uint64_t* nout,
@@ -371,7 +371,12 @@ int psg_key_union_dev(const uint64_t* a, uint64_t na, const uint64_t* b,
  * Run: no host wait, capturable; the merged count is a device word
  * (psg_nway_count_dev).  psg_nway_result synchronises and returns
  * PSG_ERR_UNSORTED if a push was not strictly increasing (the reference's
- * std::set_union precondition; the output is then unspecified). */
+ * std::set_union precondition; the output is then unspecified, but no
+ * entry at or past sum(n) of out_keys / out_vals is written).  A merge of
+ * disordered pushes can overflow a tile of the kernels: that is
+ * PSG_ERR_UNSORTED too, decided by a check of the pushes' order on the error
+ * path; PSG_ERR_DEVICE is left for an overflow with strictly increasing
+ * pushes and for a look-back timeout. */
 typedef struct psg_nway psg_nway;
 int psg_nway_max_push(void);
 int psg_nway_create(int device, int dtype, int m, unsigned flags, int npush,
@@ -395,6 +400,19 @@ int psg_nway_result(psg_nway* u, uint64_t* nout);
  * the merged output adds |union| * (8 + m s_V). */
 int psg_nway_bytes(psg_nway* u, uint64_t* bytes, uint64_t* kv_pairs);
 int psg_nway_destroy(psg_nway* u);
+/* Read-outs of the planner and of a run, for tests.
+ * psg_nway_shape: the plan psg_nway_create_batch would make for these push
+ * lengths (npush / n as there; empty pushes are dropped the same way): per
+ * merge shape[j * 5 ..] = K (non-empty pushes), s (sample stride), cw (rank
+ * bucket width), B (buckets = splitters), T (tiles); *rank_form = the rank
+ * kernel's candidates per thread (16, 4 or 1), *round_robin = 1 if the tile
+ * tickets go round-robin over the merges (both nullable).  Host arithmetic
+ * only: needs no device.
+ * psg_nway_splitters: synchronises and copies the B splitter keys of merge j
+ * of the last run to out (host). */
+int psg_nway_shape(int nmerge, const int* npush, const uint64_t* n, uint32_t* shape,
+                   int* rank_form, int* round_robin);
+int psg_nway_splitters(psg_nway* u, int j, uint64_t* out);
 
 /* ------------------------------------------------------------------ */
 /* Shard exchange over RCCL ("unsliced" ingress)          */

@@ -210,6 +210,8 @@ SIGNATURES = {
     "psg_nway_result": (C.c_int, [_p, _pu64]),
     "psg_nway_bytes": (C.c_int, [_p, _pu64, _pu64]),
     "psg_nway_destroy": (C.c_int, [_p]),
+    "psg_nway_shape": (C.c_int, [C.c_int, _p, _pu64, _p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "psg_nway_splitters": (C.c_int, [_p, C.c_int, _pu64]),
     "psg_darling_init": (C.c_int, [_p, C.c_int, C.c_double]),
     "psg_darling_reset_active": (C.c_int, [_p, C.c_int]),
     "psg_darling_update": (C.c_int, [_p, C.c_int, C.c_int, _p, C.POINTER(C.c_double)]),

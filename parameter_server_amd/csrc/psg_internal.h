@@ -224,6 +224,13 @@ size_t nway_scratch_bytes(uint32_t K, const uint64_t* n);
 hipError_t nway_union_enqueue(uint32_t K, const uint64_t* const* keys, const uint64_t* n,
                               uint64_t* out_keys, void* scratch, unsigned long long** d_bad,
                               hipStream_t stream);
+// The error path of a merge whose (*d_bad)[0] has high bits set (a tile
+// overflowed / a look-back timed out): *disordered = some push is not
+// strictly increasing, which makes it PSG_ERR_UNSORTED and not a device
+// fault (only such pushes can overflow a tile).  Checks every push on
+// `stream` and waits.
+hipError_t nway_disordered(uint32_t K, const uint64_t* const* keys, const uint64_t* n,
+                           hipStream_t stream, bool* disordered);
 hipError_t launch_slice(const uint64_t* keys, uint64_t n, uint64_t kb,
                         uint64_t ke, const uint64_t* sep, int nsep,
                         uint64_t* pos, hipStream_t stream);

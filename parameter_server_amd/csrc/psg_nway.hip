@@ -42,7 +42,13 @@
 // after split[t-1] in key order lies in bucket >= t and at most K
 // candidates (one per push) equal split[t-1], so A(split[t-1]) >= t C' - K s;
 // hence a tile spans at most C' + 2 K s - K elements <= kCap (C' = kCap -
-// 2 K s): no tile overflows, whatever the key distribution.
+// 2 K s): no tile overflows, whatever the key distribution of strictly
+// increasing pushes.  Pushes that are not: nw_seg's searches of them need not
+// increase from tile to tile, so a tile can overflow (reported, merged as
+// empty), pieces can overlap, and the tiles' unique counts can sum to more
+// than sum(n) -- the compacted write is bounded by the merge's total, and
+// psg_nway_result / the key unions classify such a run as PSG_ERR_UNSORTED
+// (nway_disordered, on the error path only).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,15 +59,16 @@
 #include "psg_device.h"
 #include "psg_host.h"
 #include "psg_internal.h"
+#include "psg_nway_plan.h"
 
 namespace psg {
 
 namespace {
 
-constexpr int kNT = 256;            // threads per tile workgroup
-constexpr int kPer = 8;             // merged elements per thread
-constexpr int kCap = kNT * kPer;    // elements per tile (LDS)
-constexpr int kMaxRuns = 64;        // pushes per merge (runs per tile)
+constexpr int kNT = kNwThreads;     // threads per tile workgroup
+constexpr int kPer = kNwPer;        // merged elements per thread
+constexpr int kCap = kNwCap;        // elements per tile (LDS)
+constexpr int kMaxRuns = kNwMaxRuns;  // pushes per merge (runs per tile)
 
 // G / GW: global (not flat) accesses, so the LDS waits of the rank and tile
 // stages do not wait for loads in flight too
@@ -84,6 +91,7 @@ struct NwArgs {
   uint64_t* out_keys;
   void* const* out_vals;        // [M]
   uint64_t ncand;
+  uint64_t ntot;                // sum(n): the entries out_keys / out_vals hold
   uint32_t K, B, T, s, cw;      // pushes, buckets, tiles, sample stride, bucket width C'
   uint32_t flags;
 };
@@ -676,7 +684,11 @@ __global__ __launch_bounds__(kNT) void nw_tile_kernel(NwBatch bt) {
   __syncthreads();
   NP_MARK(6);
   const unsigned long long base = sh_base;
-  for (uint32_t e = tid; e < U; e += kNT) {
+  // out_keys / out_vals hold sum(n) entries: sorted pushes never give more,
+  // disordered ones can (header), and nothing is stored past the total
+  const uint64_t room = base < a.ntot ? a.ntot - base : 0ull;
+  const uint32_t nst = room < U ? (uint32_t)room : U;
+  for (uint32_t e = tid; e < nst; e += kNT) {
     GW(a.out_keys)[base + e] = sk[e];
 #pragma unroll
     for (int mi = 0; mi < M; ++mi) GW((V*)a.out_vals[mi])[base + e] = sv[mi][e];
@@ -710,55 +722,24 @@ size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 }  // namespace
 
-// One merge's shape: sample stride s and bucket width C' (header: a tile
-// holds <= C' + K s + K elements), candidates, buckets, tiles.
-struct NwShape {
-  uint32_t K = 0, s = 1, cw = 1, B = 1, T = 2;
-  uint64_t ncand = 0;
-  std::vector<uint64_t> cbase;
-  void plan(uint32_t k, const uint64_t* pn) {
-    K = k;
-    uint64_t ntot = 0;
-    for (uint32_t q = 0; q < K; ++q) ntot += pn[q];
-    s = std::max<uint32_t>(1, kCap / (8 * std::max<uint32_t>(K, 1)));
-    cw = kCap - 2 * K * s;
-    cbase.assign(K + 1, 0);
-    for (uint32_t q = 0; q < K; ++q) cbase[q + 1] = cbase[q] + pn[q] / s;
-    ncand = cbase[K];
-    B = (uint32_t)(ntot / cw + 1);
-    T = B + 1;
-    if (K == 0) B = T = 0;  // no pushes: no work, the merged count stays 0
-  }
-  // rank workgroups at `per` candidates per thread
-  uint64_t waves(uint32_t per) const { return (ncand + 256u * per - 1) / (256u * per); }
-};
-
 // Device scratch of a batch of nm merges: [tables: per merge key / value /
 // length / candidate-base / output pointer arrays; NwArgs[nm]; prefix
 // counts][zeroed per run: per merge rank, splitters, look-back words; the
 // ticket; per merge (bad, nout)][per merge piece starts].  The tables are
 // written once (upload); a run clears one region and enqueues 5 launches.
-struct NwLayout {
-  uint32_t nm = 0;
+struct NwLayout : NwPlan {
   int m = 0;
-  std::vector<NwShape> sh;
   struct Off { size_t k, v, n, cb, ov, rank, split, state, seg, candk; };
   std::vector<Off> off;
   size_t o_args = 0, o_pre = 0, o_zero = 0, o_ticket = 0, o_misc = 0, zero_len = 0, bytes = 0;
-  uint64_t nwaves = 0, ncand = 0, nseg = 0, ntiles = 0;
-  uint64_t maxT = 0;  // the most tiles of one merge (round-robin tickets: maxT * nm)
-  uint32_t rk_per = 16;  // rank-stage candidates per thread (16, 4 or 1)
 
   // pn: the merges' push lengths back to back, npush[j] per merge
   void plan(uint32_t nmerge, const uint32_t* npush, const uint64_t* pn, int mm) {
-    nm = nmerge;
+    plan_shapes(nmerge, npush, pn);
     m = mm;
-    sh.assign(nm, NwShape{});
     off.assign(nm, Off{});
-    size_t o = 0, pcur = 0;
+    size_t o = 0;
     for (uint32_t j = 0; j < nm; ++j) {
-      sh[j].plan(npush[j], pn + pcur);
-      pcur += npush[j];
       const uint32_t K = npush[j];
       Off& f = off[j];
       f.k = o; o = al256(o + 8 * (size_t)K);
@@ -786,30 +767,7 @@ struct NwLayout {
       o = al256(o + 8 * sh[j].ncand);
     }
     bytes = o;
-    nwaves = ncand = nseg = ntiles = maxT = 0;
-    // the fewest candidates per thread that still gives >= 512 rank workgroups
-    uint64_t w16 = 0, w4 = 0;
-    for (const NwShape& x : sh) {
-      w16 += x.waves(16);
-      w4 += x.waves(4);
-    }
-    rk_per = w16 >= 512 ? 16u : (w4 >= 512 ? 4u : 1u);
-    for (const NwShape& x : sh) {
-      nwaves += x.waves(rk_per);
-      ncand += x.ncand;
-      nseg += (uint64_t)(x.T + 1) * x.K;
-      ntiles += x.T;
-      maxT = std::max<uint64_t>(maxT, x.T);
-    }
   }
-#ifndef PSG_NW_RR
-#define PSG_NW_RR 1
-#endif
-  // round-robin tickets run maxT * nm workgroups: only where that stays
-  // within a small factor of the tiles (a skewed batch -- one large merge and
-  // many one-tile merges -- would launch mostly idle workgroups)
-  bool rr() const { return PSG_NW_RR && nm > 1 && maxT * nm <= 2 * ntiles; }
-  uint64_t tickets() const { return rr() ? maxT * nm : ntiles; }
 
   unsigned long long* misc(char* b, uint32_t j) const {
     return (unsigned long long*)(b + o_misc) + 2 * (size_t)j;
@@ -864,6 +822,7 @@ struct NwLayout {
       A.seg = (uint32_t*)(b + f.seg);
       A.out_keys = out_keys[j];
       A.ncand = x.ncand;
+      A.ntot = x.ntot;
       A.K = K;
       A.B = x.B;
       A.T = x.T;
@@ -932,6 +891,28 @@ hipError_t nway_union_enqueue(uint32_t K, const uint64_t* const* pk, const uint6
   return nway_enqueue(b, L, PSG_F32, st);
 }
 
+// The error path of a run whose `bad` word has high bits set (a tile
+// overflowed or a look-back timed out): are the K pushes strictly
+// increasing?  A tile that overflows merges nothing and so counts no order
+// violation of its own, and the header's bound holds for such pushes only:
+// disorder makes the run PSG_ERR_UNSORTED, not a device fault.  One check
+// per push on `st` and a wait; nothing of it is enqueued by a good run.
+hipError_t nway_disordered(uint32_t K, const uint64_t* const* pk, const uint64_t* pn,
+                           hipStream_t st, bool* disordered) {
+  unsigned long long* d_word = nullptr;
+  unsigned long long h = 0;
+  hipError_t e = hipMalloc((void**)&d_word, 8);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(d_word, 0, 8, st);
+  for (uint32_t q = 0; q < K && e == hipSuccess; ++q)
+    e = launch_check_sorted(pk[q], pn[q], d_word, st, true);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, d_word, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_word);
+  *disordered = h != 0;
+  return e;
+}
+
 }  // namespace psg
 
 using psg::fail;
@@ -943,6 +924,10 @@ struct psg_nway {
   uint64_t bytes = 0;             // algorithmic bytes read by a run
   void* blob = nullptr;
   psg::NwLayout layout;
+  // the kept pushes, back to back over the merges (the error path's order
+  // check, psg_nway_result)
+  std::vector<const uint64_t*> pk;
+  std::vector<uint64_t> pn;
   hipStream_t last = nullptr;
 };
 
@@ -971,13 +956,16 @@ int nway_create(int device, int dtype, int m, unsigned flags, int nmerge, const 
   std::vector<const uint64_t*> pk;
   std::vector<const void*> pv;
   std::vector<uint64_t> pn;
-  std::vector<uint32_t> kept(nmerge, 0);
+  std::vector<uint32_t> kept;
+  std::vector<size_t> idx;
+  nway_keep(nmerge, npush, n, kept, idx);
   uint64_t ntot = 0;
-  size_t p = 0;
-  for (int j = 0; j < nmerge; ++j) {
+  size_t x = 0, first = 0;  // first: merge j's first push in the caller's list
+  for (int j = 0; j < nmerge; first += (size_t)npush[j], ++j) {
     uint64_t mt = 0;
-    for (int e = 0; e < npush[j]; ++e, ++p) {
-      if (n[p] == 0) continue;
+    for (uint32_t r = 0; r < kept[j]; ++r, ++x) {
+      const size_t p = idx[x];
+      const int e = (int)(p - first);
       if (!keys[p]) return fail(PSG_ERR_ARG, "merge %d push %d: null keys", j, e);
       pk.push_back(keys[p]);
       for (int i = 0; i < m; ++i) {
@@ -985,7 +973,6 @@ int nway_create(int device, int dtype, int m, unsigned flags, int nmerge, const 
         pv.push_back(vals[p * m + i]);
       }
       pn.push_back(n[p]);
-      ++kept[j];
       mt += n[p];
     }
     if (kept[j] > (uint32_t)kMaxRuns)
@@ -1017,6 +1004,8 @@ int nway_create(int device, int dtype, int m, unsigned flags, int nmerge, const 
   // SURVEY 8d general form, the read side: every push's keys and values
   // (the merged output adds |union| * (8 + m s_V), known after a run)
   u->bytes = ntot * (8 + (uint64_t)m * (dtype == PSG_F32 ? 4 : 8));
+  u->pk = std::move(pk);
+  u->pn = std::move(pn);
   *out = u;
   return PSG_OK;
 }
@@ -1078,10 +1067,69 @@ int psg_nway_result(psg_nway* u, uint64_t* nout) {
     dev |= h[2 * j] >> 32;
     bad += h[2 * j] & 0xffffffffull;
   }
-  if (dev) return fail(PSG_ERR_DEVICE, "nway: tile overflow / look-back timeout (%llx)", dev);
+  if (dev) {
+    // a tile overflows only when a push is not strictly increasing (header)
+    bool dis = false;
+    HIP_TRY(psg::nway_disordered((uint32_t)u->pk.size(), u->pk.data(), u->pn.data(), u->last,
+                                 &dis));
+    if (!dis) return fail(PSG_ERR_DEVICE, "nway: tile overflow / look-back timeout (%llx)", dev);
+    return fail(PSG_ERR_UNSORTED, "nway: a push is not strictly increasing (tile overflow, "
+                "%llx; %llu keys seen out of order)", dev, bad);
+  }
   if (bad)
     return fail(PSG_ERR_UNSORTED, "nway: %llu keys out of order (pushes must be strictly "
                 "increasing)", bad);
+  return PSG_OK;
+}
+
+int psg_nway_shape(int nmerge, const int* npush, const uint64_t* n, uint32_t* shape,
+                   int* rank_form, int* round_robin) {
+  if (nmerge < 1 || !npush || !shape) return fail(PSG_ERR_ARG, "null argument");
+  size_t tot_push = 0;
+  for (int j = 0; j < nmerge; ++j) {
+    if (npush[j] < 0) return fail(PSG_ERR_ARG, "merge %d: %d pushes", j, npush[j]);
+    tot_push += (size_t)npush[j];
+  }
+  if (tot_push && !n) return fail(PSG_ERR_ARG, "null argument");
+  std::vector<uint32_t> kept;
+  std::vector<size_t> idx;
+  psg::nway_keep(nmerge, npush, n, kept, idx);
+  std::vector<uint64_t> pn;
+  for (size_t p : idx) pn.push_back(n[p]);
+  size_t x = 0;
+  for (int j = 0; j < nmerge; x += kept[j], ++j) {
+    uint64_t mt = 0;
+    for (uint32_t r = 0; r < kept[j]; ++r) mt += pn[x + r];
+    if (kept[j] > (uint32_t)psg::kNwMaxRuns)
+      return fail(PSG_ERR_ARG, "merge %d: %u pushes > %d per merge", j, kept[j], psg::kNwMaxRuns);
+    if (mt >= (1ull << 32))
+      return fail(PSG_ERR_ARG, "merge %d: %llu keys >= 2^32", j, (unsigned long long)mt);
+  }
+  psg::NwPlan P;
+  P.plan_shapes((uint32_t)nmerge, kept.data(), pn.data());
+  for (int j = 0; j < nmerge; ++j) {
+    const psg::NwShape& s = P.sh[j];
+    uint32_t* o = shape + 5 * (size_t)j;
+    o[0] = s.K;
+    o[1] = s.s;
+    o[2] = s.cw;
+    o[3] = s.B;
+    o[4] = s.T;
+  }
+  if (rank_form) *rank_form = (int)P.rk_per;
+  if (round_robin) *round_robin = P.rr() ? 1 : 0;
+  return PSG_OK;
+}
+
+int psg_nway_splitters(psg_nway* u, int j, uint64_t* out) {
+  if (!u || !out) return fail(PSG_ERR_ARG, "null argument");
+  if (j < 0 || (uint32_t)j >= u->nm) return fail(PSG_ERR_ARG, "merge %d of %u", j, u->nm);
+  HIP_TRY(hipSetDevice(u->device));
+  if (u->last) HIP_TRY(hipStreamSynchronize(u->last));
+  const uint32_t B = u->layout.sh[j].B;
+  if (B)
+    HIP_TRY(hipMemcpy(out, (char*)u->blob + u->layout.off[j].split, 8 * (size_t)B,
+                      hipMemcpyDeviceToHost));
   return PSG_OK;
 }
 

@@ -166,8 +166,14 @@ int psg_key_union_dev(const uint64_t* a, uint64_t na, const uint64_t* b,
   (void)hipFree(scratch);
   if (e != hipSuccess) return fail(PSG_ERR_DEVICE, "key union: %s", hipGetErrorString(e));
   // high bits: tile overflow (1 << 32) / look-back timeout (1 << 40) of the
-  // N-way kernels, a device fault and not an order violation
-  if (h[0] >> 32) return fail(PSG_ERR_DEVICE, "key union: device fault (%llx)", h[0]);
+  // N-way kernels: a device fault and not an order violation, unless an
+  // input is not strictly increasing (only then can a tile overflow)
+  if (h[0] >> 32) {
+    bool dis = false;
+    HIP_TRY(psg::nway_disordered((uint32_t)pk.size(), pk.data(), pn.data(), s, &dis));
+    if (!dis) return fail(PSG_ERR_DEVICE, "key union: device fault (%llx)", h[0]);
+    return fail(PSG_ERR_UNSORTED, "an input is not strictly increasing (%llx)", h[0]);
+  }
   if (h[0]) return fail(PSG_ERR_UNSORTED, "%llu order violations", h[0]);
   *nout = h[1];
   return PSG_OK;

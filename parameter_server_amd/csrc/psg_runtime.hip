@@ -236,7 +236,15 @@ int key_union_impl(psg_ctx* c, int chl, const std::vector<const uint64_t*>& d_pu
     const unsigned long long bad = c->h_small[0], nu = c->h_small[1];
     if (bad) {  // the pushes of this merge are not applied; earlier ones are
       c->dev_put(d_out, 8 * cap);
-      return settle(fail(bad >> 32 ? PSG_ERR_DEVICE : PSG_ERR_UNSORTED,
+      // high bits (tile overflow / look-back timeout): a device fault only
+      // if every push is strictly increasing
+      bool dis = false;
+      if (bad >> 32) {
+        e = psg::nway_disordered(K, pk.data(), pn.data(), c->stream, &dis);
+        if (e != hipSuccess)
+          return settle(fail(PSG_ERR_DEVICE, "key union: %s", hipGetErrorString(e)));
+      }
+      return settle(fail((bad >> 32) && !dis ? PSG_ERR_DEVICE : PSG_ERR_UNSORTED,
                          "key-only push: %llu order violations", bad));
     }
     c->dev_put(C.d_keys, C.kbytes);

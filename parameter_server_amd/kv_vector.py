@@ -356,9 +356,24 @@ class NWayMergeBatch:
         b, kv = C.c_uint64(), C.c_uint64()
         _lib.check(self._L.psg_nway_bytes(h, C.byref(b), C.byref(kv)))
         self.bytes_in, self.kv_pairs = b.value, kv.value
+        self.shape, self.rank_form, self.round_robin = nway_shape([x["push_n"] for x in merges])
 
     def run(self, stream: Optional[int] = None) -> None:
         _lib.check(self._L.psg_nway_run(self._h, stream or None))
+
+    def splitters(self, j: int = 0) -> np.ndarray:
+        """Synchronises; merge j's splitter keys of the last run (one per rank
+        bucket, psg_nway_splitters)."""
+        out = np.zeros(max(1, self.shape[j][3]), np.uint64)
+        _lib.check(self._L.psg_nway_splitters(self._h, j,
+                                              out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[: self.shape[j][3]]
+
+    def count_dev(self) -> int:
+        """The device address of the first merge's merged-count word."""
+        p = C.c_void_p()
+        _lib.check(self._L.psg_nway_count_dev(self._h, C.byref(p)))
+        return p.value
 
     def result(self) -> List[int]:
         """Synchronises; the merged key count of each merge."""
@@ -404,9 +419,24 @@ class NWayMerge:
         b, kv = C.c_uint64(), C.c_uint64()
         _lib.check(self._L.psg_nway_bytes(h, C.byref(b), C.byref(kv)))
         self.bytes_in, self.kv_pairs = b.value, kv.value
+        self.shape, self.rank_form, self.round_robin = nway_shape([list(push_n)])
 
     def run(self, stream: Optional[int] = None) -> None:
         _lib.check(self._L.psg_nway_run(self._h, stream or None))
+
+    def splitters(self, j: int = 0) -> np.ndarray:
+        """Synchronises; merge j's splitter keys of the last run (one per rank
+        bucket, psg_nway_splitters)."""
+        out = np.zeros(max(1, self.shape[j][3]), np.uint64)
+        _lib.check(self._L.psg_nway_splitters(self._h, j,
+                                              out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[: self.shape[j][3]]
+
+    def count_dev(self) -> int:
+        """The device address of the first merge's merged-count word."""
+        p = C.c_void_p()
+        _lib.check(self._L.psg_nway_count_dev(self._h, C.byref(p)))
+        return p.value
 
     def result(self) -> int:
         """Synchronises; the merged key count (PSGError if a push was unsorted)."""
@@ -424,6 +454,21 @@ class NWayMerge:
             self.close()
         except Exception:
             pass
+
+
+def nway_shape(push_n):
+    """The N-way merge's plan for merges of these push lengths ([[n] per
+    push] per merge; psg_nway_shape, host arithmetic only): ([(K, s, cw, B,
+    T)] per merge, rank form, round robin)."""
+    L = _lib.lib()
+    nm = len(push_n)
+    np_ = (C.c_int * max(1, nm))(*[len(x) for x in push_n])
+    ns = [int(n) for x in push_n for n in x]
+    pn = (C.c_uint64 * max(1, len(ns)))(*ns)
+    shape = (C.c_uint32 * (5 * max(1, nm)))()
+    form, rr = C.c_int(), C.c_int()
+    _lib.check(L.psg_nway_shape(nm, np_, pn, shape, C.byref(form), C.byref(rr)))
+    return [tuple(shape[5 * j: 5 * j + 5]) for j in range(nm)], form.value, bool(rr.value)
 
 
 def shard_bounds(n: int) -> np.ndarray:
