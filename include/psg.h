@@ -859,8 +859,9 @@ size_t psg_mb_sort_tile(void);
  * copy and the result, or the line's rejection, is patched in.  Results do
  * not depend on how many tokens are slow.  A LIBSVM idx:val token counts as
  * one token and is slow if either half is.
- * Out of scope: TERAFEA, ignore_feature_group = false, files, gzip, the
- * protobuf and binary formats, text that is already on the device. */
+ * Out of scope: TERAFEA, files, gzip, the protobuf and binary formats, text
+ * that is already on the device.  ignore_feature_group = false is
+ * psg_mb_load_text_groups, below. */
 #define PSG_TEXT_ADFEA 4   /* DataConfig::ADFEA */
 #define PSG_TEXT_LIBSVM 5  /* DataConfig::LIBSVM */
 typedef struct psg_text_result {
@@ -900,6 +901,110 @@ size_t psg_text_chunk(void);
 #define PSG_MB_INDEX 25  /* uint64[nnz] */
 #define PSG_MB_VALUE 26  /* double[nnz], none for a binary matrix */
 #define PSG_MB_Y 27      /* double[rows] */
+
+/* ------------------------------------------------------------------ */
+/* Text ingest by feature group: SlotReader::read                      */
+/* (src/data/slot_reader.cc:35-232) with ignore_feature_group = false: */
+/* the slot id of every entry, the ExampleInfo of the load             */
+/* (ExampleParser::toProto / info, example_parser.cc:38-82) and one    */
+/* resident matrix per group.                                          */
+/* ------------------------------------------------------------------ */
+/* The grouped parse is the parse above with two differences.
+ * (1) The line rule is FileLineReader's (util/filelinereader.cc:34-42), not
+ * fgets': a line is the bytes up to '\n' (a last line without '\n' counts
+ * only when final != 0); the terminating '\n' and then at most one '\r'
+ * directly before it are chopped before the line is tokenised (on a final
+ * line without '\n', at most one trailing '\r').  Every other byte is a token
+ * byte as above, any other '\r' and an ADFEA '\t' included: such a token is
+ * slow and libc decides (strtol("7\r") rejects, "\t7" is accepted).  What
+ * follows from the chop is kept: "id 1 1\n" is a valid ADFEA row with no
+ * entry, and "id 1 1 5:2 9\n" parses the key 9 and drops it, because no slot
+ * token follows.  The 61439-byte rule (the '\n' and '\r' counted), the NUL
+ * rule and "fewer than three ADFEA tokens" stay as they are.
+ * (2) The slot tokens are read.  ADFEA: after the label, even tokens are slot
+ * ids by strtoi32: strtol base 10 truncated to int32 and consumed to the
+ * end, so "4294967297" is slot 1.  The fast grammar is 1..4 decimal digits;
+ * every other slot token is a slow token.  LIBSVM: every entry has slot 1.
+ * Defined deviation, a rejected line: a line holding a slot id outside
+ * [1, 4095].  In the reference id 0 as a line's first group appends its keys
+ * to the label slot, a negative id indexes SlotReader's vslots out of bounds,
+ * and an id >= 4096 makes toProto return false after it has updated a part of
+ * its slot_info_.
+ * A rejected line ends the parse exactly as above: the rows before it are
+ * kept, the line is consumed and reported in bad_line.  (SlotReader itself
+ * skips such a line and goes on, slot_reader.cc:148; a caller does that by
+ * cutting the line out and parsing again.)
+ * psg_mb_load_text_groups is psg_mb_load_text with that rule: it leaves the
+ * minibatch as psg_mb_load_text would (offset / index / value / y, loaded)
+ * plus the resident slot array, one uint16 per entry, which
+ * psg_mb_read(PSG_MB_SLOT) reads and psg_mb_groups works on.  A slow slot
+ * token goes the way of every slow token (the host's libc call, patched in)
+ * and is counted in slow_tokens.  Same errors and host waits.
+ * psg_text_parse_groups_host is psg_text_parse_host with that rule and one
+ * more output, slot[nnz] (may be NULL when offset is NULL).  Its arrays are
+ * what psg_mb_load and psg_mb_set_slots take. */
+int psg_mb_load_text_groups(psg_minibatch* mb, const char* text, size_t nbytes, int format,
+                            size_t max_rows, int final, psg_text_result* result);
+int psg_text_parse_groups_host(const char* text, size_t nbytes, int format, size_t max_rows,
+                               int final, uint64_t* offset, uint64_t* index, double* value,
+                               double* y, uint16_t* slot, size_t rows_cap, size_t nnz_cap,
+                               psg_text_result* result);
+#define PSG_MB_SLOT 28   /* uint16[nnz]: the slot id of every entry (after psg_mb_load_text_groups
+                          * or psg_mb_set_slots) */
+
+/* The slot ids of the loaded minibatch's entries: slot[n], a host array free
+ * on return, n == nnz (PSG_ERR_SIZE otherwise); after psg_mb_load /
+ * psg_mb_load_text and before psg_mb_uniq (PSG_ERR_ARG otherwise).  The ids
+ * are checked by psg_mb_groups, not here. */
+int psg_mb_set_slots(psg_minibatch* mb, const uint16_t* slot, size_t n);
+/* SlotInfo (proto/example.proto) */
+#define PSG_SLOT_DENSE 1
+#define PSG_SLOT_SPARSE 2
+#define PSG_SLOT_SPARSE_BINARY 3
+typedef struct psg_slot_info {
+  int32_t id;
+  int32_t format;
+  uint64_t min_key, max_key, nnz_ele, nnz_ex;
+} psg_slot_info;
+/* toProto's bookkeeping (example_parser.cc:43-55) and info() (:59-82) for the
+ * whole load, in ascending id order.  The label slot 0 first (dropped when
+ * rows == 0): PSG_SLOT_DENSE, min_key 0, max_key 1, nnz_ex = nnz_ele = rows.
+ * Then every feature slot with an entry: PSG_SLOT_SPARSE for a valued matrix
+ * (LIBSVM), PSG_SLOT_SPARSE_BINARY for a binary one (ADFEA); min_key the
+ * smallest key; max_key the largest key + 1 as written, in uint64, so key
+ * 2^64 - 1 contributes 0; nnz_ele its entries; nnz_ex the rows that hold it,
+ * and for a valued matrix `rows` (parseLibsvm adds slot 1 to every example).
+ * *n = the slots; PSG_ERR_SIZE with *n set (nothing written) when cap is
+ * short; info may be NULL then.
+ * The format's contract is "same group_ids should appear together"
+ * (example_parser.cc:127): a row in which a slot id occurs in two separate
+ * runs makes the reference push two row_siz entries for one example and lose
+ * the row alignment of that slot.  Defined deviation: such a row, or a row
+ * holding a slot id outside [1, 4095], is reported in *bad_row (the smallest
+ * such row; -1: none), the call returns PSG_ERR_ARG and psg_mb_group_extract
+ * is refused.  Equal ids at the end of row r and the start of row r + 1 are
+ * legal.
+ * A stable radix sort of (slot, position) over the digits in which the ids
+ * differ, then integer counts, minima and maxima per slot: the same input
+ * gives the same bytes on every run.  One host wait (the slots and the
+ * verdict).  Needs psg_mb_set_slots; PSG_ERR_ARG after psg_mb_uniq. */
+int psg_mb_groups(psg_minibatch* mb, psg_slot_info* info, size_t cap, size_t* n,
+                  int64_t* bad_row);
+/* SlotReader::index(g) / offset(g) / value(g) (slot_reader.cc:234-290) of
+ * slot `slot_id` as the loaded minibatch `dst` (of the same context): all of
+ * src's rows (a row without the group is empty: row_siz's zero padding), the
+ * group's entries in their original order, y copied.  An absent slot gives
+ * `rows` empty rows.  Device to device; dst is left as psg_mb_load leaves it
+ * (one host wait).  PSG_ERR_ARG: before psg_mb_groups on src or after a
+ * psg_mb_groups that reported a bad row, after psg_mb_uniq on src (it reuses
+ * the sort's blocks), src == dst, a slot id outside [1, 4095], two contexts. */
+int psg_mb_group_extract(psg_minibatch* src, int slot_id, psg_minibatch* dst);
+/* Range<Key>(begin, end).evenDivide(n, i) for every i (range.h:85-98), which
+ * cuts a slot's [min_key, max_key) into feature blocks
+ * (batch_solver.cc:61-65): bounds[n + 1], block i is [bounds[i], bounds[i +
+ * 1]), in long double as written.  Host arithmetic.  PSG_ERR_ARG: n == 0,
+ * end < begin (the reference CHECKs both). */
+int psg_even_divide(uint64_t begin, uint64_t end, size_t n, uint64_t* bounds);
 
 /* ------------------------------------------------------------------ */
 /* Batch worker step: the worker half of Darling::updateModel          */
@@ -968,6 +1073,27 @@ int psg_mb_darling_set_state(psg_minibatch* mb, const double* dual, const double
 #define PSG_MB_DARLING_DELTA 34    /* double[ndict] */
 #define PSG_MB_DARLING_ACTIVE 35   /* uint8[ndict], 0 / 1 */
 #define PSG_MB_DARLING_DELTA_W 36  /* double[ce - cb] of the last psg_mb_darling_update_dual */
+/* One dual for the feature groups of a worker: in the reference dual_ is one
+ * vector over the rows, created once (batch_solver.cc:344-349) and updated by
+ * every group's updateDual (darling.cc:358-435).  After this call, made
+ * before psg_mb_darling_init(mb), every Darling call on `mb` reads and writes
+ * `owner`'s dual block: gradients, update_dual, objv, set_state and
+ * psg_mb_read(PSG_MB_DARLING_DUAL).  psg_mb_darling_init of a sharer needs
+ * w_dev == NULL (PSG_ERR_ARG otherwise) and does not touch the dual: the
+ * reference starts from zero weights (its init_w branch is under #if 0), so
+ * every dual is 1, which the owner's own init wrote.  PSG_ERR_ARG: the row
+ * counts or contexts differ, mb == owner, the owner has not had
+ * psg_mb_darling_init, the owner shares someone else's dual, mb's own dual is
+ * shared.  A load or the destruction of the owner invalidates its sharers
+ * (their Darling calls are PSG_ERR_ARG until they share and init again), and
+ * while the owner has no Darling state (after its psg_mb_localize, until its
+ * next psg_mb_darling_init) they are PSG_ERR_ARG too.  A load of the sharer
+ * ends its sharing; so does owner == NULL.
+ * A minibatch's own calls run in call order whatever streams they are given,
+ * but nothing orders the calls of two minibatches: the order in which the
+ * groups touch the shared dual is the caller's, by passing ONE stream (e.g.
+ * psg_mb_stream's) to every Darling call of the owner and its sharers. */
+int psg_mb_darling_share_dual(psg_minibatch* mb, psg_minibatch* owner);
 
 /* ------------------------------------------------------------------ */
 /* Model evaluation: the distributed AUC (src/base/auc.h:8-103) and    */

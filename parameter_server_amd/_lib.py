@@ -77,6 +77,9 @@ PSG_AUC_BY_KEY, PSG_AUC_AS_WRITTEN = 0, 1
 PSG_MB_OFFSET, PSG_MB_INDEX, PSG_MB_VALUE, PSG_MB_Y = range(24, 28)
 # psg_mb_load_text's formats (DataConfig's values)
 PSG_TEXT_ADFEA, PSG_TEXT_LIBSVM = 4, 5
+# ... the entries' slot ids, and psg_slot_info's formats (SlotInfo)
+PSG_MB_SLOT = 28
+PSG_SLOT_DENSE, PSG_SLOT_SPARSE, PSG_SLOT_SPARSE_BINARY = 1, 2, 3
 
 # Every symbol include/psg.h declares, with its ctypes signature.
 _u64 = C.c_uint64
@@ -119,6 +122,13 @@ class TextResult(C.Structure):
 
     _fields_ = [("rows", _u64), ("nnz", _u64), ("consumed", _u64), ("bad_line", C.c_int64),
                 ("slow_tokens", _u64), ("parse_ms", C.c_double)]
+
+
+class SlotInfo(C.Structure):
+    """psg_slot_info (include/psg.h)."""
+
+    _fields_ = [("id", C.c_int32), ("format", C.c_int32), ("min_key", _u64), ("max_key", _u64),
+                ("nnz_ele", _u64), ("nnz_ex", _u64)]
 
 
 SIGNATURES = {
@@ -258,6 +268,15 @@ SIGNATURES = {
     "psg_text_parse_host": (C.c_int, [_p, _sz, C.c_int, _sz, C.c_int, _p, _p, _p, _p, _sz, _sz,
                                       C.POINTER(TextResult)]),
     "psg_text_chunk": (_sz, []),
+    "psg_mb_load_text_groups": (C.c_int, [_p, _p, _sz, C.c_int, _sz, C.c_int,
+                                          C.POINTER(TextResult)]),
+    "psg_text_parse_groups_host": (C.c_int, [_p, _sz, C.c_int, _sz, C.c_int, _p, _p, _p, _p, _p,
+                                             _sz, _sz, C.POINTER(TextResult)]),
+    "psg_mb_set_slots": (C.c_int, [_p, _p, _sz]),
+    "psg_mb_groups": (C.c_int, [_p, C.POINTER(SlotInfo), _sz, _psz, C.POINTER(C.c_int64)]),
+    "psg_mb_group_extract": (C.c_int, [_p, C.c_int, _p]),
+    "psg_even_divide": (C.c_int, [_u64, _u64, _sz, _pu64]),
+    "psg_mb_darling_share_dual": (C.c_int, [_p, _p]),
     "psg_auc_create": (C.c_int, [_p, C.c_int64, C.POINTER(_p)]),
     "psg_auc_destroy": (None, [_p]),
     "psg_auc_clear": (C.c_int, [_p]),

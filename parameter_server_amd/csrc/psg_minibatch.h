@@ -21,6 +21,8 @@ enum BufId {
   // psg_text.hip: the text, the chunks' counts and bases, the lanes' counts,
   // the lines' ends, the slow tokens and their patches, the control words
   B_TEXT, B_TX_CHUNK, B_TX_LANE, B_TX_LINE_END, B_TX_SLOW, B_TX_PATCH, B_TX_WORDS,
+  // psg_groups.hip: the entries' slot ids; two control words and the slots' statistics
+  B_SLOT, B_GRP,
   B_COUNT
 };
 
@@ -64,6 +66,22 @@ struct psg_minibatch : psg::DeviceBlocks<B_COUNT> {
   void* h_slow = nullptr;
   size_t h_slow_cap = 0;
 
+  // psg_groups.hip: psg_mb_set_slots has run since the load, with the bits in
+  // which its ids differ; psg_mb_groups has run and found no bad row, with
+  // every slot's segment of the sorted pairs (ascending id)
+  bool has_slots = false;
+  uint64_t slot_differ = 0;
+  bool groups_ok = false;
+  struct Group {
+    uint32_t id, start, end;
+  };
+  std::vector<Group> groups;
+  // psg_mb_darling_share_dual: whose dual block this minibatch's Darling calls
+  // use (null: its own), and who uses this one's
+  psg_minibatch* dual_owner = nullptr;
+  std::vector<psg_minibatch*> sharers;
+  double* dual() const { return (dual_owner ? dual_owner : this)->at<double>(B_DUAL); }
+
   uint32_t* d_u32(int word) const { return (uint32_t*)(d_small + 4) + word; }
   uint32_t* d_dtotal() const { return (uint32_t*)(d_small + 6); }
 };
@@ -77,4 +95,7 @@ int mb_load_begin(psg_minibatch* mb, size_t rows, size_t nnz, bool valued);
 // written there by work enqueued on the minibatch's stream): the row of every
 // position, the OR / AND of the keys, one wait, and the state S_LOADED.
 int mb_load_finish(psg_minibatch* mb, size_t rows, size_t nnz, bool valued);
+// mb's dual block is about to go (a load, its destruction): its sharers lose
+// their Darling state, and mb stops sharing another's
+void mb_drop_sharing(psg_minibatch* mb);
 }  // namespace psg

@@ -41,10 +41,13 @@ size_t token_end(const unsigned char* t, size_t nbytes, int libsvm, size_t s) {
   return e;
 }
 
-SlowPatch resolve_one(const unsigned char* t, size_t nbytes, int libsvm, const SlowToken& k) {
+SlowPatch resolve_one(const unsigned char* t, size_t nbytes, int libsvm, bool grouped,
+                      const SlowToken& k) {
   SlowPatch p{0, 0.0, 0, 0};
   if (k.start >= nbytes) return p;
-  const size_t e = token_end(t, nbytes, libsvm, k.start);
+  const size_t e = grouped && !libsvm
+                       ? k.start + grouped_field(t + k.start, nbytes - k.start, 0xfffffffeu)
+                       : token_end(t, nbytes, libsvm, k.start);
   const std::string z((const char*)t + k.start, e - k.start);  // NUL-terminated copy
   switch (k.kind) {
     case kLibsvmLabel: {
@@ -70,6 +73,12 @@ SlowPatch resolve_one(const unsigned char* t, size_t nbytes, int libsvm, const S
     case kAdfeaKey:
       p.ok = libc_u64(z.c_str(), &p.key);
       break;
+    case kAdfeaSlot: {  // strtoi32, then the ids this library takes (include/psg.h)
+      int32_t id;
+      p.ok = libc_i32(z.c_str(), &id) && id >= 1 && id < kSlotMax;
+      p.key = (uint64_t)(uint32_t)id;
+      break;
+    }
     default:
       break;
   }
@@ -81,16 +90,21 @@ struct Out {  // the caller's arrays (null: count only) and their room
   uint64_t* index;
   double* value;
   double* y;
+  uint16_t* slot;  // the grouped parse
   size_t rows_cap, nnz_cap;
 };
 
 // One line [ls, le) into row `row`, entries from `*nnz` on.  false: rejected.
-bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, size_t ls, size_t le,
-                const Out& o, size_t row, uint64_t* nnz, uint64_t* slow) {
+// grouped: FileLineReader's chop first, and the ADFEA slot tokens are read.
+bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, bool grouped, size_t ls,
+                size_t le, const Out& o, size_t row, uint64_t* nnz, uint64_t* slow) {
   if (le - ls >= kMaxLine - 1) return false;
   if (memchr(t + ls, 0, le - ls)) return false;
+  const bool ga = grouped && !libsvm;
+  if (ga) le = chopped_end(t, ls, le);  // no byte past the chopped line is a token's
   uint32_t ord = 0;
   uint64_t last = 0, key = 0;
+  uint16_t slot = 1;
   size_t p = ls;
   for (;; ++ord) {
     while (p < le && is_delim(libsvm, t[p])) ++p;
@@ -110,17 +124,26 @@ bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, size_t ls, si
       }
       pt.val = (double)f;
     } else if (ord == 2) {
-      verdict = adfea_label(t + p, nbytes - p, &pt.val);
+      verdict = ga ? grouped_label(t + p, nbytes - p, &pt.val)
+                   : adfea_label(t + p, nbytes - p, &pt.val);
       st.kind = kAdfeaLabel;
     } else if (ord >= 3 && ord % 2 == 1) {
-      verdict = adfea_key(t + p, nbytes - p, &pt.key);
+      verdict = ga ? grouped_key(t + p, nbytes - p, &pt.key)
+                   : adfea_key(t + p, nbytes - p, &pt.key);
       st.kind = kAdfeaKey;
+    } else if (ga && ord >= 4) {
+      uint32_t id = 0;
+      verdict = grouped_slot(t + p, nbytes - p, &id);
+      if (verdict == kFast && (id < 1 || id >= kSlotMax)) return false;
+      slot = (uint16_t)id;
+      st.kind = kAdfeaSlot;
     }
     if (verdict == kReject) return false;
     if (verdict == kSlow) {
       ++*slow;
-      pt = resolve_one(t, le, libsvm, st);
+      pt = resolve_one(t, ga ? nbytes : le, libsvm, grouped, st);
       if (!pt.ok) return false;
+      if (st.kind == kAdfeaSlot) slot = (uint16_t)pt.key;
     }
     if (libsvm) {
       if (ord == 0) {
@@ -130,6 +153,7 @@ bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, size_t ls, si
         last = pt.key;
         if (o.index && *nnz < o.nnz_cap) o.index[*nnz] = pt.key;
         if (o.value && *nnz < o.nnz_cap) o.value[*nnz] = pt.val;
+        if (o.slot && *nnz < o.nnz_cap) o.slot[*nnz] = 1;
         ++*nnz;
       }
     } else if (ord == 2) {
@@ -138,6 +162,7 @@ bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, size_t ls, si
       key = pt.key;
     } else if (ord >= 4) {
       if (o.index && *nnz < o.nnz_cap) o.index[*nnz] = key;
+      if (o.slot && *nnz < o.nnz_cap) o.slot[*nnz] = slot;
       ++*nnz;
     }
     p = e;
@@ -145,8 +170,8 @@ bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, size_t ls, si
   return libsvm ? ord >= 1 : ord >= 3;
 }
 
-int parse(const unsigned char* t, size_t nbytes, int libsvm, size_t max_rows, bool final,
-          const Out& o, psg_text_result* r) {
+int parse(const unsigned char* t, size_t nbytes, int libsvm, bool grouped, size_t max_rows,
+          bool final, const Out& o, psg_text_result* r) {
   uint64_t rows = 0, nnz = 0, slow = 0;
   size_t at = 0;
   int64_t bad = -1;
@@ -156,7 +181,7 @@ int parse(const unsigned char* t, size_t nbytes, int libsvm, size_t max_rows, bo
     if (!nl && !final) break;
     const size_t le = nl ? (size_t)(nl - t) + 1 : nbytes;
     uint64_t n = nnz;
-    const bool ok = parse_line(t, nbytes, libsvm, at, le, o, (size_t)rows, &n, &slow);
+    const bool ok = parse_line(t, nbytes, libsvm, grouped, at, le, o, (size_t)rows, &n, &slow);
     at = le;
     if (!ok) {
       bad = (int64_t)rows;
@@ -177,32 +202,54 @@ int parse(const unsigned char* t, size_t nbytes, int libsvm, size_t max_rows, bo
 
 }  // namespace
 
-void resolve_slow(const unsigned char* text, size_t nbytes, int format_libsvm,
+void resolve_slow(const unsigned char* text, size_t nbytes, int format_libsvm, int grouped,
                   const SlowToken* tok, size_t n, SlowPatch* patch) {
-  for (size_t i = 0; i < n; ++i) patch[i] = resolve_one(text, nbytes, format_libsvm, tok[i]);
+  for (size_t i = 0; i < n; ++i)
+    patch[i] = resolve_one(text, nbytes, format_libsvm, grouped != 0, tok[i]);
 }
 
 }  // namespace text
 }  // namespace psg
 
-extern "C" int psg_text_parse_host(const char* text, size_t nbytes, int format, size_t max_rows,
-                                   int final, uint64_t* offset, uint64_t* index, double* value,
-                                   double* y, size_t rows_cap, size_t nnz_cap,
-                                   psg_text_result* result) {
+namespace {
+
+int parse_entry(const char* text, size_t nbytes, int format, bool grouped, size_t max_rows,
+                int final, uint64_t* offset, uint64_t* index, double* value, double* y,
+                uint16_t* slot, size_t rows_cap, size_t nnz_cap, psg_text_result* result) {
   using namespace psg::text;
   if (!result || (nbytes && !text)) return psg::fail(PSG_ERR_ARG, "null argument");
   if (format != PSG_TEXT_ADFEA && format != PSG_TEXT_LIBSVM)
     return psg::fail(PSG_ERR_ARG, "text format %d", format);
   const int libsvm = format == PSG_TEXT_LIBSVM;
   const unsigned char* t = (const unsigned char*)text;
-  if ((offset && !y && rows_cap) || (offset && !index && nnz_cap))
+  if ((offset && !y && rows_cap) || (offset && !index && nnz_cap) ||
+      (offset && grouped && !slot && nnz_cap))
     return psg::fail(PSG_ERR_ARG, "null output");
   const Out o{offset, offset ? index : nullptr, offset && libsvm ? value : nullptr,
-              offset ? y : nullptr, rows_cap, nnz_cap};
-  if (int rc = parse(t, nbytes, libsvm, max_rows, final != 0, o, result)) return rc;
+              offset ? y : nullptr, offset && grouped ? slot : nullptr, rows_cap, nnz_cap};
+  if (int rc = parse(t, nbytes, libsvm, grouped, max_rows, final != 0, o, result)) return rc;
   if (offset && (result->rows > rows_cap || result->nnz > nnz_cap))
     return psg::fail(PSG_ERR_SIZE, "%llu rows and %llu entries, room for %zu and %zu",
                      (unsigned long long)result->rows, (unsigned long long)result->nnz, rows_cap,
                      nnz_cap);
   return PSG_OK;
+}
+
+}  // namespace
+
+extern "C" int psg_text_parse_host(const char* text, size_t nbytes, int format, size_t max_rows,
+                                   int final, uint64_t* offset, uint64_t* index, double* value,
+                                   double* y, size_t rows_cap, size_t nnz_cap,
+                                   psg_text_result* result) {
+  return parse_entry(text, nbytes, format, false, max_rows, final, offset, index, value, y,
+                     nullptr, rows_cap, nnz_cap, result);
+}
+
+extern "C" int psg_text_parse_groups_host(const char* text, size_t nbytes, int format,
+                                          size_t max_rows, int final, uint64_t* offset,
+                                          uint64_t* index, double* value, double* y,
+                                          uint16_t* slot, size_t rows_cap, size_t nnz_cap,
+                                          psg_text_result* result) {
+  return parse_entry(text, nbytes, format, true, max_rows, final, offset, index, value, y, slot,
+                     rows_cap, nnz_cap, result);
 }

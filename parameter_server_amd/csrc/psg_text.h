@@ -29,8 +29,10 @@ enum SlowKind : uint32_t {
   kLibsvmLabel = 0,  // strtof -> y[dest]
   kLibsvmPair = 1,   // idx:val, strtoull and strtof -> index[dest], value[dest]
   kAdfeaLabel = 2,   // strtol -> y[dest]
-  kAdfeaKey = 3      // strtoull -> index[dest]
+  kAdfeaKey = 3,     // strtoull -> index[dest]
+  kAdfeaSlot = 4     // the grouped parse: strtol truncated to int32 -> slot[dest], 1..4095 or rejected
 };
+constexpr int64_t kSlotMax = 4096;  // kSlotIDmax, example_parser.h: the ids are 1 .. kSlotMax - 1
 constexpr uint32_t kNoDest = 0xffffffffu;  // converted for its verdict only
 
 struct SlowToken {  // one token outside the fast grammar
@@ -160,9 +162,67 @@ PSG_HD int adfea_key(const unsigned char* p, size_t avail, uint64_t* key) {
   return !slow && fast_u64(p, e, key) ? kFast : kSlow;
 }
 
+
+// ---- the grouped parse (include/psg.h, "Text ingest by feature group") --------
+// 1..4 decimal digits: the slot id strtoi32 gives ("07" is 7).  The range
+// [1, kSlotMax) is the caller's check.
+PSG_HD bool fast_slot(const unsigned char* p, uint32_t len, uint32_t* id) {
+  if (len == 0 || len > 4) return false;
+  uint32_t v = 0;
+  for (uint32_t i = 0; i < len; ++i) {
+    if (!is_digit(p[i])) return false;
+    v = v * 10u + (uint32_t)(p[i] - '0');
+  }
+  *id = v;
+  return true;
+}
+// A byte of the grouped ADFEA parse that no token holds: a delimiter, the
+// line's '\n', and the one '\r' that FileLineReader chops: directly before
+// the '\n', or the last byte of the text (a final line without '\n'; a
+// partial line that is not final is not taken at all).  next: the byte after
+// c; at_end: there is none.
+PSG_HD bool grouped_gap(unsigned char c, unsigned char next, bool at_end) {
+  return c == ' ' || c == ':' || c == '\n' || (c == '\r' && (at_end || next == '\n'));
+}
+// the length of the token at p, up to max + 1; avail: the bytes from p to the
+// end of the text
+PSG_HD uint32_t grouped_field(const unsigned char* p, size_t avail, uint32_t max) {
+  uint32_t e = 0;
+  while (e < avail && e <= max &&
+         !grouped_gap(p[e], e + 1 < avail ? p[e + 1] : (unsigned char)0, e + 1 == avail))
+    ++e;
+  return e;
+}
+// A further token follows, on its line, the token that ends at p: a key whose
+// slot token is missing is parsed and dropped (example_parser.cc:146-155).
+PSG_HD bool grouped_follows(const unsigned char* p, size_t avail) {
+  size_t i = 0;
+  while (i < avail && (p[i] == ' ' || p[i] == ':')) ++i;
+  return i < avail && !grouped_gap(p[i], i + 1 < avail ? p[i + 1] : (unsigned char)0, i + 1 == avail);
+}
+PSG_HD int grouped_label(const unsigned char* p, size_t avail, double* y) {
+  const uint32_t e = grouped_field(p, avail, kMaxField);
+  return e <= kMaxField && fast_label(p, e, y) ? kFast : kSlow;
+}
+PSG_HD int grouped_key(const unsigned char* p, size_t avail, uint64_t* key) {
+  const uint32_t e = grouped_field(p, avail, kMaxField);
+  return e <= kMaxField && fast_u64(p, e, key) ? kFast : kSlow;
+}
+PSG_HD int grouped_slot(const unsigned char* p, size_t avail, uint32_t* id) {
+  return fast_slot(p, grouped_field(p, avail, 4), id) ? kFast : kSlow;
+}
+// FileLineReader's chop (util/filelinereader.cc:37-42): the end of the line
+// [ls, le) once its '\n' and then at most one '\r' are gone
+PSG_HD size_t chopped_end(const unsigned char* t, size_t ls, size_t le) {
+  if (le > ls && t[le - 1] == '\n') --le;
+  if (le > ls && t[le - 1] == '\r') --le;
+  return le;
+}
+
 // The slow tokens through libc (psg_text.cc; host only).  patch[i] is what
 // the reference's call makes of tok[i].
-void resolve_slow(const unsigned char* text, size_t nbytes, int format_libsvm,
+// grouped: the tokens are cut by the grouped parse's line rule.
+void resolve_slow(const unsigned char* text, size_t nbytes, int format_libsvm, int grouped,
                   const SlowToken* tok, size_t n, SlowPatch* patch);
 
 }  // namespace text

@@ -34,6 +34,11 @@
 //  (7) order_kernel (LIBSVM: idx must not decrease within a line),
 //      line_kernel (the length limit), verdict_kernel (the first rejected
 //      line, the rows and entries kept, the bytes consumed).
+// psg_mb_load_text_groups is the same pipeline in its grouped
+// mode: FileLineReader's line rule for ADFEA (`ga`: the line's '\n' and the
+// '\r' chopped with it are no token bytes, lane_tok_start), the slot id of
+// every entry into a uint16 block, slow slot tokens through (6), and after (7)
+// the OR / AND of the ids kept (slot_bits_kernel) for the grouping's sort.
 // Integer atomics: the minimum over the rejected lines, nothing else.  Every
 // array element has one writer (or, for a slow token, a second one ordered
 // after the first), so the same text gives the same arrays on every run.
@@ -57,7 +62,11 @@ constexpr uint32_t kChunk = 4096;  // bytes per workgroup: 256 lanes x 16
 constexpr uint32_t kNone = 0xffffffffu;
 
 // control words (uint32) on the device
-enum Word { W_LINES = 0, W_ROWS, W_NNZ, W_SLOW, W_BAD, W_ROWS_OUT, W_NNZ_OUT, W_CONSUMED, W_COUNT };
+enum Word {
+  W_LINES = 0, W_ROWS, W_NNZ, W_SLOW, W_BAD, W_ROWS_OUT, W_NNZ_OUT, W_CONSUMED,
+  W_SLOT_OR, W_SLOT_AND,  // the grouped parse: over the slot ids of the entries kept
+  W_COUNT
+};
 
 // per-chunk arrays, each `nc` words, in one block
 struct Chunks {
@@ -79,6 +88,7 @@ struct Lane {
     return (unsigned char)((j < 8 ? lo >> (8 * j) : hi >> (8 * (j - 8))) & 255u);
   }
   unsigned char prev;
+  unsigned char next;  // the byte after them (0 past the text): the grouped parse's look-ahead
   uint32_t n;   // how many of the 16 are text
   uint64_t i0;  // the first one's place
 };
@@ -92,23 +102,35 @@ __device__ __forceinline__ Lane load_lane(const unsigned char* __restrict__ text
   l.lo = (uint64_t)v.x | ((uint64_t)v.y << 32);
   l.hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
   l.prev = l.n && l.i0 ? text[l.i0 - 1] : '\n';
+  l.next = l.n && l.i0 + l.n < nbytes ? text[l.i0 + l.n] : 0;
   return l;
 }
 
 __device__ __forceinline__ bool tok_start(int libsvm, unsigned char prev, unsigned char c) {
   return !is_delim(libsvm, c) && (prev == '\n' || is_delim(libsvm, prev));
 }
+// Byte j of the lane starts a token.  ga (grouped ADFEA): the line's '\n' and
+// the '\r' chopped with it are no token bytes, which takes the byte after c.
+// A chopped '\r' is never the byte before a token byte (a '\n' or the end of
+// the text follows it), so `prev` needs no look-ahead of its own.
+__device__ __forceinline__ bool lane_tok_start(const Lane& l, int libsvm, int ga, uint32_t j,
+                                               unsigned char prev, unsigned char c,
+                                               uint64_t nbytes) {
+  if (!ga) return tok_start(libsvm, prev, c);
+  const unsigned char next = j + 1 < l.n ? l.at(j + 1) : l.next;
+  return !grouped_gap(c, next, l.i0 + j + 1 == nbytes) && (prev == '\n' || is_delim(0, prev));
+}
 
 // the lane's newlines, token starts, and token starts after its last newline
-__device__ __forceinline__ void lane_counts(const Lane& l, int libsvm, uint32_t* nls,
-                                            uint32_t* total, uint32_t* after) {
+__device__ __forceinline__ void lane_counts(const Lane& l, int libsvm, int ga, uint64_t nbytes,
+                                            uint32_t* nls, uint32_t* total, uint32_t* after) {
   uint32_t n = 0, t = 0, a = 0;
   unsigned char prev = l.prev;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     if ((uint32_t)j < l.n) {
       const unsigned char c = l.at(j);
-      const uint32_t st = tok_start(libsvm, prev, c) ? 1u : 0u;
+      const uint32_t st = lane_tok_start(l, libsvm, ga, (uint32_t)j, prev, c, nbytes) ? 1u : 0u;
       t += st;
       a += st;  // an ADFEA '\n' that starts a token belongs to the line it ends
       if (c == '\n') {
@@ -157,11 +179,12 @@ __device__ __forceinline__ void lane_state(uint32_t nls, uint32_t total, uint32_
 
 // ---- (1) ----------------------------------------------------------------------
 __global__ __launch_bounds__(256) void count_kernel(const unsigned char* __restrict__ text,
-                                                    uint64_t nbytes, int libsvm, Chunks ch) {
+                                                    uint64_t nbytes, int libsvm, int ga,
+                                                    Chunks ch) {
   __shared__ uint32_t sh[16];
   const Lane l = load_lane(text, nbytes);
   uint32_t nls, total, after;
-  lane_counts(l, libsvm, &nls, &total, &after);
+  lane_counts(l, libsvm, ga, nbytes, &nls, &total, &after);
   const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
   const uint64_t m = __ballot(nls != 0);
   if (lane == 0) sh[8 + w] = m ? (w * 64u + 63u - (uint32_t)__clzll((long long)m)) + 1u : 0u;
@@ -238,6 +261,7 @@ struct Emit {  // (5)'s outputs; all null in (3)
   uint64_t* index;
   double* value;
   double* y;
+  uint16_t* slot;  // the grouped parse; null otherwise
   uint32_t* line_end;
   SlowToken* slow;
   uint32_t* words;
@@ -250,7 +274,8 @@ struct Emit {  // (5)'s outputs; all null in (3)
 // same walk with the lane's first entry `fpos` and first slow token `spos`.
 template <bool kEmit>
 __device__ __forceinline__ void lane_walk(const unsigned char* __restrict__ text, uint64_t nbytes,
-                                          int libsvm, int final, const Lane& l, uint32_t line0,
+                                          int libsvm, int ga, int final, const Lane& l,
+                                          uint32_t line0,
                                           uint32_t ord0, uint32_t rows, uint32_t fpos,
                                           uint32_t spos, const Emit& o, uint32_t* nfeat,
                                           uint32_t* nslow) {
@@ -265,7 +290,7 @@ __device__ __forceinline__ void lane_walk(const unsigned char* __restrict__ text
       const unsigned char c = l.at(j);
       if (c == '\n') nlm |= 1u << j;
       if (c == 0) zero |= 1u << j;
-      if (tok_start(libsvm, prev, c)) stm |= 1u << j;
+      if (lane_tok_start(l, libsvm, ga, (uint32_t)j, prev, c, nbytes)) stm |= 1u << j;
       prev = c;
     }
   }
@@ -300,26 +325,44 @@ __device__ __forceinline__ void lane_walk(const unsigned char* __restrict__ text
         verdict = libsvm_pair(p, avail, &key, &f);
         kind = kLibsvmPair;
         dest = fpos + feat;
+        if (kEmit && o.slot && dest < o.nnz) o.slot[dest] = 1;  // parseLibsvm's one slot
         ++feat;
         featm |= 1u << j;
       }
       val = (double)f;
     } else if (ord == 2) {
-      verdict = adfea_label(p, avail, &val);
+      verdict = ga ? grouped_label(p, avail, &val) : adfea_label(p, avail, &val);
       kind = kAdfeaLabel;
       dest = line;
     } else if (ord >= 3 && (ord & 1u)) {
-      verdict = adfea_key(p, avail, &key);
+      verdict = ga ? grouped_key(p, avail, &key) : adfea_key(p, avail, &key);
       kind = kAdfeaKey;
       // the key's entry is its slot token's; a key with no slot token ends
       // the text, and its place is past the last entry
       dest = fpos + feat;
       if (kEmit && dest >= o.nnz) dest = kNone;
+      if (kEmit && ga) {  // ... or, in the grouped parse, ends any line: that place is the next line's
+        uint32_t e = grouped_field(p, avail, kMaxField);
+        if (e > kMaxField) e = grouped_field(p, avail, 0xfffffffeu);
+        if (!grouped_follows(p + e, avail - e)) dest = kNone;
+      }
     } else if (ord >= 4) {
+      if (ga) {  // the slot id of the entry this token completes
+        uint32_t id = 0;
+        verdict = grouped_slot(p, avail, &id);
+        kind = kAdfeaSlot;
+        dest = fpos + feat;
+        key = id;
+      }
       ++feat;
       featm |= 1u << j;
     }
-    if (verdict == kSlow) {
+    if (kEmit && kind == kAdfeaSlot && verdict == kFast) {
+      if (key < 1 || key >= (uint64_t)kSlotMax)
+        atomicMin(&o.words[W_BAD], line);
+      else if (dest < o.nnz)
+        o.slot[dest] = (uint16_t)key;
+    } else if (verdict == kSlow) {
       if (kEmit && spos + slow < o.nslow)  // always, by the counts
         o.slow[spos + slow] = SlowToken{(uint32_t)i, line, dest, (uint32_t)kind};
       ++slow;
@@ -368,17 +411,18 @@ __device__ __forceinline__ void lane_walk(const unsigned char* __restrict__ text
 }
 
 __global__ __launch_bounds__(256) void class_kernel(const unsigned char* __restrict__ text,
-                                                    uint64_t nbytes, int libsvm, int final,
-                                                    Chunks ch, const uint32_t* __restrict__ words,
+                                                    uint64_t nbytes, int libsvm, int ga,
+                                                    int final, Chunks ch,
+                                                    const uint32_t* __restrict__ words,
                                                     uint16_t* __restrict__ lane_cnt) {
   __shared__ uint32_t sh[16];
   const Lane l = load_lane(text, nbytes);
   uint32_t nls, total, after, line, ord;
-  lane_counts(l, libsvm, &nls, &total, &after);
+  lane_counts(l, libsvm, ga, nbytes, &nls, &total, &after);
   lane_state(nls, total, after, ch.line_base[blockIdx.x], ch.ord_base[blockIdx.x], sh, &line, &ord);
   uint32_t feat, slow;
-  lane_walk<false>(text, nbytes, libsvm, final, l, line, ord, words[W_ROWS], 0, 0, Emit{}, &feat,
-                   &slow);
+  lane_walk<false>(text, nbytes, libsvm, ga, final, l, line, ord, words[W_ROWS], 0, 0, Emit{},
+                   &feat, &slow);
   lane_cnt[(size_t)blockIdx.x * 256u + threadIdx.x] = (uint16_t)(feat | (slow << 8));  // <= 8 each
   uint32_t fsum, ssum;
   (void)block_exscan(feat, sh, &fsum);
@@ -390,20 +434,22 @@ __global__ __launch_bounds__(256) void class_kernel(const unsigned char* __restr
 }
 
 __global__ __launch_bounds__(256) void emit_kernel(const unsigned char* __restrict__ text,
-                                                   uint64_t nbytes, int libsvm, int final,
-                                                   Chunks ch, const uint16_t* __restrict__ lane_cnt,
+                                                   uint64_t nbytes, int libsvm, int ga,
+                                                   int final, Chunks ch,
+                                                   const uint16_t* __restrict__ lane_cnt,
                                                    uint32_t rows, Emit o) {
   __shared__ uint32_t sh[16];
   const Lane l = load_lane(text, nbytes);
   uint32_t nls, total, after, line, ord;
-  lane_counts(l, libsvm, &nls, &total, &after);
+  lane_counts(l, libsvm, ga, nbytes, &nls, &total, &after);
   lane_state(nls, total, after, ch.line_base[blockIdx.x], ch.ord_base[blockIdx.x], sh, &line, &ord);
   const uint32_t cnt = lane_cnt[(size_t)blockIdx.x * 256u + threadIdx.x];
   uint32_t tot;
   const uint32_t fpos = ch.feat[blockIdx.x] + block_exscan(cnt & 255u, sh, &tot);
   const uint32_t spos = ch.slow[blockIdx.x] + block_exscan(cnt >> 8, sh + 4, &tot);
   uint32_t feat, slow;
-  lane_walk<true>(text, nbytes, libsvm, final, l, line, ord, rows, fpos, spos, o, &feat, &slow);
+  lane_walk<true>(text, nbytes, libsvm, ga, final, l, line, ord, rows, fpos, spos, o, &feat,
+                  &slow);
 }
 
 // ---- (6), (7) -------------------------------------------------------------------
@@ -420,6 +466,8 @@ __global__ __launch_bounds__(256) void patch_kernel(const SlowToken* __restrict_
   }
   if (t.kind == kLibsvmLabel || t.kind == kAdfeaLabel) {
     o.y[t.dest] = p.val;
+  } else if (t.kind == kAdfeaSlot) {
+    if (t.dest < o.nnz) o.slot[t.dest] = (uint16_t)p.key;
   } else if (t.dest < o.nnz) {
     o.index[t.dest] = p.key;
     if (t.kind == kLibsvmPair) o.value[t.dest] = p.val;
@@ -466,6 +514,26 @@ __global__ void verdict_kernel(const uint64_t* __restrict__ offset,
   words[W_CONSUMED] = line_end[last];                 // + 1 on the host: it may be 2^32 - 1
 }
 
+// OR / AND of the slot ids of the entries kept: the digits the grouping sorts on
+__global__ __launch_bounds__(256) void slot_bits_kernel(const uint16_t* __restrict__ slot,
+                                                        uint32_t* __restrict__ words) {
+  const uint32_t n = words[W_NNZ_OUT];
+  uint32_t o = 0, a = 0xffffu;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n;
+       i += (uint64_t)gridDim.x * 256u) {
+    o |= slot[i];
+    a &= slot[i];
+  }
+  for (int s = 32; s >= 1; s >>= 1) {
+    o |= __shfl_xor(o, s, 64);
+    a &= __shfl_xor(a, s, 64);
+  }
+  if ((threadIdx.x & 63u) == 0) {
+    atomicOr(&words[W_SLOT_OR], o);
+    atomicAnd(&words[W_SLOT_AND], a);
+  }
+}
+
 }  // namespace
 }  // namespace psg
 
@@ -475,14 +543,17 @@ extern "C" {
 
 size_t psg_text_chunk(void) { return psg::kChunk; }
 
-int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format,
-                     size_t max_rows, int final, psg_text_result* result) {
+namespace {
+
+int load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format, size_t max_rows,
+              int final, bool grouped, psg_text_result* result) {
   using namespace psg;
   if (!mb || !result || (nbytes && !text)) return fail(PSG_ERR_ARG, "null argument");
   if (format != PSG_TEXT_ADFEA && format != PSG_TEXT_LIBSVM)
     return fail(PSG_ERR_ARG, "text format %d", format);
   if (nbytes >= 0xffffffffull) return fail(PSG_ERR_SIZE, "%zu bytes of text >= 2^32 - 1", nbytes);
   const int libsvm = format == PSG_TEXT_LIBSVM;
+  const int ga = grouped && !libsvm;  // grouped ADFEA: the line rule changes, slot tokens are read
   const uint32_t want_rows = (uint32_t)std::min<size_t>(max_rows, 0xfffffffeull);
   *result = psg_text_result{0, 0, 0, -1, 0, -1.0};
   HIP_TRY(hipSetDevice(mb->device));
@@ -494,6 +565,7 @@ int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int for
   uint32_t* h = mb->h_text;
   for (int i = 0; i < W_COUNT; ++i) h[i] = 0;
   h[W_BAD] = kNone;
+  h[W_SLOT_AND] = 0xffffu;
   const int tev = 2 * PSG_MB_STAGES;
   const bool timed = mb->prof && mb->tev[tev] && mb->tev[tev + 1];
   if (nc) {
@@ -506,9 +578,9 @@ int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int for
     HIP_TRY(hipMemcpyAsync(mb->b[B_TEXT].p, text, nbytes, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(words, h, 4 * W_COUNT, hipMemcpyHostToDevice, s));
     if (timed) HIP_TRY(hipEventRecord(mb->tev[tev], s));
-    LAUNCH(count_kernel, nc, s, d_text, (uint64_t)nbytes, libsvm, ch);
+    LAUNCH(count_kernel, nc, s, d_text, (uint64_t)nbytes, libsvm, ga, ch);
     LAUNCH(chunk_scan_kernel, 1, s, d_text, (uint64_t)nbytes, nc, ch, want_rows, final, words);
-    LAUNCH(class_kernel, nc, s, d_text, (uint64_t)nbytes, libsvm, final, ch, words,
+    LAUNCH(class_kernel, nc, s, d_text, (uint64_t)nbytes, libsvm, ga, final, ch, words,
            mb->at<uint16_t>(B_TX_LANE));
     LAUNCH(row_scan_kernel, 2, s, ch.feat, nc, words + W_NNZ);  // W_NNZ, W_SLOW
     if (int rc = launched("text count")) return rc;
@@ -517,6 +589,8 @@ int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int for
   }
   const size_t rows = h[W_ROWS], n = h[W_NNZ], nslow = h[W_SLOW];
   if (int rc = mb_load_begin(mb, rows, n, libsvm != 0)) return rc;
+  if (grouped)
+    if (int rc = mb->need(B_SLOT, 2 * n)) return rc;
   if (rows) {
     if (int rc = mb->need_all({{B_TX_LINE_END, 4 * rows}, {B_TX_SLOW, sizeof(SlowToken) * nslow},
                                {B_TX_PATCH, sizeof(SlowPatch) * nslow}}))
@@ -525,12 +599,13 @@ int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int for
     uint32_t* words = mb->at<uint32_t>(B_TX_WORDS);
     const Chunks ch = chunks_of(mb->at<uint32_t>(B_TX_CHUNK), nc);
     const Emit o{mb->at<uint64_t>(B_OFFSET), mb->at<uint64_t>(B_INDEX), mb->at<double>(B_VALUE),
-                 mb->at<double>(B_Y), mb->at<uint32_t>(B_TX_LINE_END), mb->at<SlowToken>(B_TX_SLOW),
+                 mb->at<double>(B_Y), grouped ? mb->at<uint16_t>(B_SLOT) : nullptr,
+                 mb->at<uint32_t>(B_TX_LINE_END), mb->at<SlowToken>(B_TX_SLOW),
                  words, (uint32_t)n, (uint32_t)nslow};
     uint64_t* h_n = (uint64_t*)(h + W_COUNT);  // pinned, and not read into again
     *h_n = n;
     HIP_TRY(hipMemcpyAsync(o.offset + rows, h_n, 8, hipMemcpyHostToDevice, s));
-    LAUNCH(emit_kernel, nc, s, d_text, (uint64_t)nbytes, libsvm, final, ch,
+    LAUNCH(emit_kernel, nc, s, d_text, (uint64_t)nbytes, libsvm, ga, final, ch,
            mb->at<uint16_t>(B_TX_LANE), (uint32_t)rows, o);
     if (int rc = launched("text emit")) return rc;
     if (nslow) {
@@ -546,7 +621,7 @@ int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int for
       SlowToken* h_tok = (SlowToken*)(h_patch + nslow);
       HIP_TRY(hipMemcpyAsync(h_tok, o.slow, sizeof(SlowToken) * nslow, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));  // the slow tokens
-      resolve_slow((const unsigned char*)text, nbytes, libsvm, h_tok, nslow, h_patch);
+      resolve_slow((const unsigned char*)text, nbytes, libsvm, grouped, h_tok, nslow, h_patch);
       HIP_TRY(hipMemcpyAsync(mb->b[B_TX_PATCH].p, h_patch, sizeof(SlowPatch) * nslow,
                              hipMemcpyHostToDevice, s));
       LAUNCH(patch_kernel, blocks_of(nslow, 256), s, o.slow, mb->at<SlowPatch>(B_TX_PATCH),
@@ -558,6 +633,8 @@ int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int for
     LAUNCH(line_kernel, blocks_of(rows, 256), s, o.line_end, (uint32_t)rows, words);
     hipLaunchKernelGGL(verdict_kernel, dim3(1), dim3(64), 0, s, o.offset, o.line_end,
                        (uint32_t)rows, words);
+    if (grouped && n)
+      LAUNCH(slot_bits_kernel, std::min<uint32_t>(blocks_of(n, 256), 1024u), s, o.slot, words);
     if (int rc = launched("text verdict")) return rc;
     HIP_TRY(hipMemcpyAsync(h, words, 4 * W_COUNT, hipMemcpyDeviceToHost, s));
   } else {
@@ -577,12 +654,28 @@ int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int for
     }
   }
   result->slow_tokens = nslow;
+  if (grouped) {
+    mb->slot_differ = rows && result->nnz ? (uint64_t)((h[W_SLOT_OR] ^ h[W_SLOT_AND]) & 0xffffu) : 0;
+    mb->has_slots = true;
+  }
   if (timed && nc) {
     float ms = 0;
     HIP_TRY(hipEventElapsedTime(&ms, mb->tev[tev], mb->tev[tev + 1]));
     result->parse_ms = ms;
   }
   return PSG_OK;
+}
+
+}  // namespace
+
+int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format,
+                     size_t max_rows, int final, psg_text_result* result) {
+  return load_text(mb, text, nbytes, format, max_rows, final, false, result);
+}
+
+int psg_mb_load_text_groups(psg_minibatch* mb, const char* text, size_t nbytes, int format,
+                            size_t max_rows, int final, psg_text_result* result) {
+  return load_text(mb, text, nbytes, format, max_rows, final, true, result);
 }
 
 }  // extern "C"

@@ -736,6 +736,8 @@ size_t elem_size(int what) {
       return 4;
     case PSG_MB_DARLING_ACTIVE:
       return 1;
+    case PSG_MB_SLOT:
+      return 2;
     default:
       return 8;
   }
@@ -745,12 +747,26 @@ size_t elem_size(int what) {
 
 namespace psg {
 
+void mb_drop_sharing(psg_minibatch* mb) {
+  for (psg_minibatch* sh : mb->sharers) {
+    sh->dual_owner = nullptr;
+    sh->darling = false;
+  }
+  mb->sharers.clear();
+  if (psg_minibatch* o = mb->dual_owner) {
+    o->sharers.erase(std::remove(o->sharers.begin(), o->sharers.end(), mb), o->sharers.end());
+    mb->dual_owner = nullptr;
+  }
+}
+
 int mb_load_begin(psg_minibatch* mb, size_t rows, size_t n, bool valued) {
   HIP_TRY(hipSetDevice(mb->device));
   if (int rc = mb->settle()) return rc;  // the previous minibatch's work
   mb->state = S_NEW;
   mb->darling = false;
   mb->xw_own = false;
+  mb->has_slots = mb->groups_ok = false;
+  mb_drop_sharing(mb);
   const size_t ntiles = blocks_of(n, kSortTile);
   return mb->need_all({
       {B_OFFSET, 8 * (rows + 1)}, {B_Y, 8 * rows}, {B_INDEX, 8 * n},
@@ -815,6 +831,7 @@ int psg_mb_create(psg_ctx* ctx, psg_minibatch** out) {
 
 void psg_mb_destroy(psg_minibatch* mb) {
   if (!mb) return;
+  psg::mb_drop_sharing(mb);
   mb->close();
   for (hipEvent_t e : mb->tev)
     if (e) (void)hipEventDestroy(e);
@@ -1109,6 +1126,9 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
     case PSG_MB_INDEX: need_state = S_LOADED; id = B_INDEX; n = mb->nnz; break;
     case PSG_MB_VALUE: need_state = S_LOADED; id = B_VALUE; n = mb->binary ? 0 : mb->nnz; break;
     case PSG_MB_Y: need_state = S_LOADED; id = B_Y; n = mb->rows; break;
+    case PSG_MB_SLOT:
+      if (!mb->has_slots) return fail(PSG_ERR_ARG, "psg_mb_read: no slot ids since the load");
+      need_state = S_LOADED; id = B_SLOT; n = mb->nnz; break;
     case PSG_MB_REMAPPED: need_state = S_LOCAL; id = B_REMAPPED; n = mb->nnz; break;
     case PSG_MB_NEW_OFFSET: need_state = S_LOCAL; id = B_NEW_OFFSET; n = mb->rows + 1; break;
     case PSG_MB_NEW_INDEX: need_state = S_LOCAL; id = B_NEW_INDEX; n = kept_unknown; break;
@@ -1132,7 +1152,7 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
       break;
     default: return fail(PSG_ERR_ARG, "psg_mb_read: array %d", what);
   }
-  if (what >= PSG_MB_DARLING_DUAL && !mb->darling)
+  if (what >= PSG_MB_DARLING_DUAL && (!mb->darling || (mb->dual_owner && !mb->dual_owner->darling)))
     return fail(PSG_ERR_ARG, "psg_mb_read: array %d before psg_mb_darling_init", what);
   if (mb->state < need_state)
     return fail(PSG_ERR_ARG, "psg_mb_read: array %d is not computed yet", what);
@@ -1157,7 +1177,9 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
   if (bytes == 0) return PSG_OK;
   if (!out) return fail(PSG_ERR_ARG, "null output");
   const void* src = id == -1 ? (const void*)mb->skey
-                             : id == -2 ? (const void*)mb->spos : (const void*)mb->b[id].p;
+                             : id == -2 ? (const void*)mb->spos
+                                        : id == B_DUAL ? (const void*)mb->dual()
+                                                       : (const void*)mb->b[id].p;
   HIP_TRY(hipMemcpy(out, (const char*)src + first * elem_size(what), bytes,
                     hipMemcpyDeviceToHost));
   return PSG_OK;
@@ -1170,6 +1192,8 @@ int darling_ready(psg_minibatch* mb, const char* who) {
   if (!mb) return fail(PSG_ERR_ARG, "null argument");
   if (mb->state < S_LOCAL || !mb->darling)
     return fail(PSG_ERR_ARG, "%s before psg_mb_darling_init", who);
+  if (mb->dual_owner && !mb->dual_owner->darling)
+    return fail(PSG_ERR_ARG, "%s: the owner of the shared dual has no Darling state", who);
   return PSG_OK;
 }
 
@@ -1193,9 +1217,14 @@ int psg_mb_darling_init(psg_minibatch* mb, double delta_init, const double* w_de
   if (mb->state < S_LOCAL) return fail(PSG_ERR_ARG, "psg_mb_darling_init before psg_mb_localize");
   HIP_TRY(hipSetDevice(mb->device));
   mb->darling = false;
+  const bool shares = mb->dual_owner != nullptr;
+  if (shares && w_dev)
+    return fail(PSG_ERR_ARG, "psg_mb_darling_init with weights on a minibatch that shares a dual");
+  if (shares && !mb->dual_owner->darling)
+    return fail(PSG_ERR_ARG, "psg_mb_darling_init: the owner of the shared dual has no Darling state");
   const size_t rows_z = mb->rows, n_z = mb->nnz, nd_z = mb->ndict;
   if (int rc = mb->need_all({
-      {B_DUAL, 8 * rows_z}, {B_CUR_W, 8 * nd_z}, {B_DELTA, 8 * nd_z}, {B_ACTIVE, nd_z},
+      {B_DUAL, shares ? 0 : 8 * rows_z}, {B_CUR_W, 8 * nd_z}, {B_DELTA, 8 * nd_z}, {B_ACTIVE, nd_z},
       {B_DELTA_W, 8 * nd_z}, {B_EXP_DELTA, mb->binary ? 8 * nd_z : 0}, {B_TERM2, 16 * n_z},
       {B_RKEY_A, 8 * n_z}, {B_RKEY_B, 8 * n_z}, {B_RPOS_A, 4 * n_z}, {B_RPOS_B, 4 * n_z},
       {B_ROW_START, 4 * (rows_z + 1)}, {B_COL_RANGE, 8 * nd_z}}))
@@ -1205,8 +1234,9 @@ int psg_mb_darling_init(psg_minibatch* mb, double delta_init, const double* w_de
   const uint32_t n = (uint32_t)n_z, nd = (uint32_t)nd_z, nu = (uint32_t)mb->n_uniq;
   const uint32_t rows = (uint32_t)rows_z;
   double* dual = mb->at<double>(B_DUAL);
-  // dual_ = exp(y .* (X w)), darling.cc:110; the worker's copy of w
-  if (rows) {
+  // dual_ = exp(y .* (X w)), darling.cc:110; the worker's copy of w.  A shared
+  // dual is the owner's to fill.
+  if (rows && !shares) {
     if (w_dev) {
       if (int rc = enqueue_times(mb, w_dev, dual, s)) return rc;
       LAUNCH(dual_init_kernel, blocks_of(rows, 256), s, mb->at<double>(B_Y), rows, dual);
@@ -1272,6 +1302,33 @@ int psg_mb_darling_init(psg_minibatch* mb, double delta_init, const double* w_de
   return PSG_OK;
 }
 
+int psg_mb_darling_share_dual(psg_minibatch* mb, psg_minibatch* owner) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (owner) {
+    if (owner == mb) return fail(PSG_ERR_ARG, "psg_mb_darling_share_dual with itself");
+    if (owner->ctx != mb->ctx) return fail(PSG_ERR_ARG, "minibatches of two contexts");
+    if (owner->state < S_LOCAL || !owner->darling)
+      return fail(PSG_ERR_ARG, "the owner has not had psg_mb_darling_init");
+    if (owner->dual_owner) return fail(PSG_ERR_ARG, "the owner shares another minibatch's dual");
+    if (!mb->sharers.empty()) return fail(PSG_ERR_ARG, "the minibatch's own dual is shared");
+    if (mb->state < S_LOADED || owner->rows != mb->rows)
+      return fail(PSG_ERR_ARG, "%zu rows share a dual of %zu rows", mb->rows, owner->rows);
+  }
+  if (psg_minibatch* o = mb->dual_owner)
+    o->sharers.erase(std::remove(o->sharers.begin(), o->sharers.end(), mb), o->sharers.end());
+  mb->dual_owner = nullptr;
+  mb->darling = false;  // psg_mb_darling_init comes after this call
+  if (owner) {
+    try {
+      owner->sharers.push_back(mb);
+    } catch (const std::bad_alloc&) {
+      return fail(PSG_ERR_OOM, "host allocation");
+    }
+    mb->dual_owner = owner;
+  }
+  return PSG_OK;
+}
+
 int psg_mb_darling_reset_active(psg_minibatch* mb, void* stream) {
   if (int rc = darling_ready(mb, "psg_mb_darling_reset_active")) return rc;
   HIP_TRY(hipSetDevice(mb->device));
@@ -1302,12 +1359,12 @@ int psg_mb_darling_gradients(psg_minibatch* mb, size_t cb, size_t ce, double* g_
     if (mb->binary)
       LAUNCH(darling_terms_kernel<true>, blocks_of(hi - lo, 256), s, mb->spos,
              mb->at<uint32_t>(B_ROW_OF), mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK),
-             (const double*)nullptr, mb->at<double>(B_Y), mb->at<double>(B_DUAL),
+             (const double*)nullptr, mb->at<double>(B_Y), mb->dual(),
              mb->at<double>(B_EXP_DELTA), active, lo, hi, n, nu, nd, term);
     else
       LAUNCH(darling_terms_kernel<false>, blocks_of(hi - lo, 256), s, mb->spos,
              mb->at<uint32_t>(B_ROW_OF), mb->at<uint32_t>(B_RUN_OF), mb->at<uint32_t>(B_RUN_RANK),
-             mb->at<double>(B_VALUE), mb->at<double>(B_Y), mb->at<double>(B_DUAL),
+             mb->at<double>(B_VALUE), mb->at<double>(B_Y), mb->dual(),
              mb->at<double>(B_DELTA), active, lo, hi, n, nu, nd, term);
   }
   LAUNCH(darling_sum_short_kernel, blocks_of(e - b, 256), s, mb->at<uint32_t>(B_DICT_RUN), nd,
@@ -1352,7 +1409,7 @@ int psg_mb_darling_update_dual(psg_minibatch* mb, size_t cb, size_t ce, const do
              mb->at<double>(B_VALUE), mb->at<double>(B_Y), mb->at<double>(B_DELTA_W), active, lo,
              hi, n, nu, nd, factor);
     LAUNCH(darling_rows_kernel, blocks_of(rows, 256), s, mb->at<uint32_t>(B_ROW_START),
-           mb->row_pair, rows, lo, hi, n, factor, mb->at<double>(B_DUAL));
+           mb->row_pair, rows, lo, hi, n, factor, mb->dual());
   }
   if (int rc = launched("darling update_dual")) return rc;
   return mb->mark(s);
@@ -1366,7 +1423,7 @@ int psg_mb_darling_objv(psg_minibatch* mb, double* objv, void* stream) {
   if (int rc = mb->order(s)) return rc;
   const uint32_t rows = (uint32_t)mb->rows, nparts = blocks_of(rows, 256);
   if (rows)
-    LAUNCH(darling_objv_kernel, nparts, s, mb->at<double>(B_DUAL), rows,
+    LAUNCH(darling_objv_kernel, nparts, s, mb->dual(), rows,
            mb->at<double>(B_PARTIAL));
   LAUNCH(objv_kernel, 1, s, mb->at<double>(B_PARTIAL), nparts, (double*)(mb->d_small + 3));
   if (int rc = launched("darling objv")) return rc;
@@ -1383,7 +1440,7 @@ int psg_mb_darling_set_state(psg_minibatch* mb, const double* dual, const double
   HIP_TRY(hipSetDevice(mb->device));
   if (int rc = mb->settle()) return rc;
   if (dual && mb->rows)
-    HIP_TRY(hipMemcpy(mb->b[B_DUAL].p, dual, 8 * mb->rows, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(mb->dual(), dual, 8 * mb->rows, hipMemcpyHostToDevice));
   if (cur_w && mb->ndict)
     HIP_TRY(hipMemcpy(mb->b[B_CUR_W].p, cur_w, 8 * mb->ndict, hipMemcpyHostToDevice));
   if (delta && mb->ndict)

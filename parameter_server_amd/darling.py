@@ -101,6 +101,33 @@ class DarlingWorker:
         _lib.check(self._L.psg_mb_darling_init(mb._h, self.delta_init, w_dev, None))
         self.dict_keys, self.ndict = dict_keys, dict_keys.size
 
+    def load_group(self, reader, slot_id: int, dict_keys, w=None, dual_of=None) -> None:
+        """``load`` for feature group ``slot_id`` of ``reader`` (a
+        ``slots.SlotReader`` on this worker's context) with no host copy of
+        the matrix: psg_mb_group_extract, uniq, localize, psg_mb_darling_init.
+        ``dual_of``: another DarlingWorker (already loaded, over the same
+        rows) whose dual this one shares (psg_mb_darling_share_dual), as the
+        groups of a reference worker share dual_; ``w`` must then be None, and
+        every call on the sharing workers has to be given one stream (the
+        default does: they are on one context)."""
+        dict_keys = np.ascontiguousarray(dict_keys, dtype=np.uint64)
+        if dual_of is not None and w is not None:
+            raise _lib.PSGError(_lib.PSG_ERR_ARG, "weights for a worker that shares a dual")
+        mb = self.mb
+        reader.extract(slot_id, mb)
+        mb.uniq()
+        mb.localize(self._upload(self._DICT, dict_keys), dict_keys.size)
+        w_dev = None
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.size != dict_keys.size:
+                raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"{w.size} weights, {dict_keys.size} keys")
+            w_dev = self._upload(self._W, w)
+        if dual_of is not None:
+            _lib.check(self._L.psg_mb_darling_share_dual(mb._h, dual_of.mb._h))
+        _lib.check(self._L.psg_mb_darling_init(mb._h, self.delta_init, w_dev, None))
+        self.dict_keys, self.ndict = dict_keys, dict_keys.size
+
     def reset_active(self) -> None:
         """kkt_filter_reset (:167-169)."""
         _lib.check(self._L.psg_mb_darling_reset_active(self.mb._h, None))

@@ -47,6 +47,7 @@ ARRAYS = {
     "index": (_lib.PSG_MB_INDEX, np.uint64),
     "value": (_lib.PSG_MB_VALUE, np.float64),
     "y": (_lib.PSG_MB_Y, np.float64),
+    "slot": (_lib.PSG_MB_SLOT, np.uint16),
 }
 FORMATS = {"adfea": _lib.PSG_TEXT_ADFEA, "libsvm": _lib.PSG_TEXT_LIBSVM}
 
@@ -141,6 +142,18 @@ class Minibatch:
         r = _lib.TextResult()
         _lib.check(self._L.psg_mb_load_text(self._h, text, len(text), _format(fmt), cap,
                                             1 if final else 0, C.byref(r)))
+        self.rows, self.nnz = int(r.rows), int(r.nnz)
+        self.n_uniq = self.ndict = 0
+        return r
+
+    def load_text_groups(self, text: bytes, fmt, max_rows=None, final: bool = True):
+        """psg_mb_load_text_groups: ``load_text`` by the grouped parse's line
+        rule, with the slot id of every entry resident too (read("slot"))."""
+        text = bytes(text) if not isinstance(text, bytes) else text
+        cap = (1 << 64) - 1 if max_rows is None else int(max_rows)
+        r = _lib.TextResult()
+        _lib.check(self._L.psg_mb_load_text_groups(self._h, text, len(text), _format(fmt), cap,
+                                                   1 if final else 0, C.byref(r)))
         self.rows, self.nnz = int(r.rows), int(r.nnz)
         self.n_uniq = self.ndict = 0
         return r
