@@ -176,18 +176,20 @@ def test_gpu_freq_filter_device_entry_points_and_k_clamp():
 
 
 @pytest.mark.gpu
-def test_gpu_freq_filter_large_table_cas_form():
+@pytest.mark.parametrize("k", [3, 9])
+def test_gpu_freq_filter_large_table_cas_form(k):
     """A table past the binned insert's 128 MB (2^27 + 4,096 counters): the
-    per-probe CAS form runs; bytes exact against the oracle, including
-    counters hit by many keys (repeated keys, byte wrap)."""
+    per-probe CAS form runs (probes in registers at k = 3, the loop past 8
+    probes at k = 9); bytes exact against the oracle, including counters hit
+    by many keys (repeated keys, byte wrap)."""
     import torch
     assert torch.cuda.is_available()
     from parameter_server_amd import _lib
     rng = np.random.default_rng(8)
     v = _ctx()
     n = (1 << 27) + 4096
-    _lib.check(v._L.psg_freq_resize(v._h, 1, n, 3))
-    t, nn, kk = O.cm_resize(n, 3)
+    _lib.check(v._L.psg_freq_resize(v._h, 1, n, k))
+    t, nn, kk = O.cm_resize(n, k)
     keys = np.concatenate([rng.integers(0, 1 << 62, 60_000, dtype=np.uint64),
                            np.full(700, 12345, np.uint64)])
     counts = rng.integers(1, 300, keys.size).astype(np.uint32)
