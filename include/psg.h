@@ -1007,6 +1007,74 @@ int psg_mb_group_extract(psg_minibatch* src, int slot_id, psg_minibatch* dst);
 int psg_even_divide(uint64_t begin, uint64_t end, size_t n, uint64_t* bounds);
 
 /* ------------------------------------------------------------------ */
+/* SlotReader's cache arrays (src/data/slot_reader.cc:86-141,208-290): */
+/* per (file, slot) a .colidx (uint64), a .rowsiz (uint16) and a       */
+/* .value (float) file, each a sequence of snappy streams              */
+/* ("partitions") that a .partition file lists as start / size pairs.  */
+/* DESIGN.md 4.11c.                                                    */
+/* ------------------------------------------------------------------ */
+#define PSG_CACHE_COLIDX 0  /* uint64[nnz]:  the minibatch's index                      */
+#define PSG_CACHE_ROWSIZ 1  /* uint16[rows]: offset[r+1] - offset[r]                    */
+#define PSG_CACHE_VALUE  2  /* float[nnz]:   (float)value; PSG_ERR_ARG for a binary mb  */
+#define PSG_CACHE_LABEL  3  /* float[rows]:  (float)y  (slot 0's .value)                */
+/* A raw array of raw_bytes cut into partitions of part_bytes raw bytes, the
+ * last one shorter; part_bytes == 0: one partition; not a multiple of 8:
+ * PSG_ERR_ARG.  *nparts = the partitions (0 for an empty array), *cap = the
+ * sum of psg_snappy_max_compressed_length over them.  Host arithmetic. */
+int psg_cache_pack_bound(size_t raw_bytes, size_t part_bytes, size_t* cap, size_t* nparts);
+/* One cache array of a loaded minibatch (after any load or
+ * psg_mb_group_extract; whenever psg_mb_read(PSG_MB_INDEX) is served), cut
+ * as above, every partition compressed on the device in one call of the
+ * compressor (so stream i is psg_snappy_compress_host of partition i's raw
+ * bytes) and the streams copied back to back into host `out`: *len their
+ * bytes, parts[2i] the start and parts[2i + 1] the size of stream i, *nparts
+ * their count.  cap and parts_cap below psg_cache_pack_bound's are
+ * PSG_ERR_SIZE, as is a partition of 4 GiB or more.  An empty array gives
+ * len = 0 and nparts = 0 (compressTo of an empty array).
+ * Defined deviation: the reference's pushBack into SArray<uint16> wraps a
+ * row of more than 65535 entries silently; here PSG_CACHE_ROWSIZ reports the
+ * smallest such row in *bad_row (-1: none) and returns PSG_ERR_RANGE with
+ * nothing written.  One host wait. */
+int psg_mb_cache_pack(psg_minibatch* mb, int what, size_t part_bytes, void* out, size_t cap,
+                      size_t* len, uint64_t* parts /* (start, size) pairs */, size_t parts_cap,
+                      size_t* nparts, int64_t* bad_row);
+
+typedef struct psg_cache_array {   /* one array of one file; host memory, free on return */
+  const void* data; size_t nbytes;          /* the file's bytes                            */
+  const uint64_t* parts; size_t nparts;     /* (start, size) pairs; nparts == 0: the whole */
+} psg_cache_array;                          /* file is one stream (no .partition file)     */
+typedef struct psg_cache_file {
+  psg_cache_array colidx, rowsiz, value, label;
+  uint64_t num_ex;                          /* the file's .info num_ex                     */
+} psg_cache_file;
+typedef struct psg_cache_result {
+  uint64_t rows, nnz; int64_t bad_file; int32_t bad_what; int32_t bad_part;
+} psg_cache_result;
+/* SlotReader::index / offset / value over `nfiles` files (:234-290) as the
+ * loaded minibatch mb, left exactly as psg_mb_load leaves it: the rows are
+ * the files' rows in the order given, offset the running sum of every rowsiz,
+ * index the concatenated colidx, value (double) of the floats (not read, and
+ * none, when valued == 0), y (double) of the labels.  All partitions of all
+ * arrays of all files are decoded in one decoder launch; one host wait.
+ * The reference's CHECKs: a partition outside its file, a partition whose
+ * declared length is no multiple of the element size, and for a file f
+ * sum rowsiz(f) != the colidx count, value count != colidx count (valued),
+ * rowsiz count, label count and num_ex not all equal, or a total of
+ * 2^32 - 1 entries or more are PSG_ERR_SIZE; a corrupt stream is
+ * PSG_ERR_ARG.  bad_file / bad_what (a PSG_CACHE_* id) / bad_part name the
+ * file, array and partition (-1: not applicable).  A partition of size 0
+ * decodes to nothing.  After any error the minibatch is empty (as created)
+ * and the next load works.
+ * Defined deviation: a file whose colidx, rowsiz and value are all empty
+ * (the slot is absent from that file) contributes num_ex empty rows; the
+ * reference's offset() fails its CHECK_EQ(os.size(), num_ex + 1) there. */
+int psg_mb_load_cache(psg_minibatch* mb, const psg_cache_file* files, size_t nfiles,
+                      int valued, psg_cache_result* result);
+/* Rows per workgroup of the load's scan of the row sizes (tests sit on its
+ * multiples). */
+size_t psg_cache_scan_tile(void);
+
+/* ------------------------------------------------------------------ */
 /* Batch worker step: the worker half of Darling::updateModel          */
 /* (src/linear_method/darling.cc:196-250) on a localized minibatch:    */
 /* computeGradients (:306-356), updateDual (:358-435), the worker's    */

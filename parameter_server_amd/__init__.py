@@ -11,6 +11,7 @@ from .worker import FTRLWorker, Minibatch  # noqa: F401,E402
 from .darling import DarlingWorker  # noqa: F401,E402
 from .auc import AUC, exact_auc  # noqa: F401,E402
 from .slots import SlotReader  # noqa: F401,E402
+from .slot_cache import CachedSlotReader  # noqa: F401,E402
 
 __all__ = ["PSGError", "lib", "FTRLWorker", "Minibatch", "DarlingWorker", "AUC", "exact_auc",
-           "SlotReader"]
+           "SlotReader", "CachedSlotReader"]

@@ -80,6 +80,8 @@ PSG_TEXT_ADFEA, PSG_TEXT_LIBSVM = 4, 5
 # ... the entries' slot ids, and psg_slot_info's formats (SlotInfo)
 PSG_MB_SLOT = 28
 PSG_SLOT_DENSE, PSG_SLOT_SPARSE, PSG_SLOT_SPARSE_BINARY = 1, 2, 3
+# psg_mb_cache_pack's arrays
+PSG_CACHE_COLIDX, PSG_CACHE_ROWSIZ, PSG_CACHE_VALUE, PSG_CACHE_LABEL = range(4)
 
 # Every symbol include/psg.h declares, with its ctypes signature.
 _u64 = C.c_uint64
@@ -129,6 +131,26 @@ class SlotInfo(C.Structure):
 
     _fields_ = [("id", C.c_int32), ("format", C.c_int32), ("min_key", _u64), ("max_key", _u64),
                 ("nnz_ele", _u64), ("nnz_ex", _u64)]
+
+
+class CacheArray(C.Structure):
+    """psg_cache_array (include/psg.h)."""
+
+    _fields_ = [("data", _p), ("nbytes", _sz), ("parts", _pu64), ("nparts", _sz)]
+
+
+class CacheFile(C.Structure):
+    """psg_cache_file (include/psg.h)."""
+
+    _fields_ = [("colidx", CacheArray), ("rowsiz", CacheArray), ("value", CacheArray),
+                ("label", CacheArray), ("num_ex", _u64)]
+
+
+class CacheResult(C.Structure):
+    """psg_cache_result (include/psg.h)."""
+
+    _fields_ = [("rows", _u64), ("nnz", _u64), ("bad_file", C.c_int64), ("bad_what", C.c_int32),
+                ("bad_part", C.c_int32)]
 
 
 SIGNATURES = {
@@ -276,6 +298,12 @@ SIGNATURES = {
     "psg_mb_groups": (C.c_int, [_p, C.POINTER(SlotInfo), _sz, _psz, C.POINTER(C.c_int64)]),
     "psg_mb_group_extract": (C.c_int, [_p, C.c_int, _p]),
     "psg_even_divide": (C.c_int, [_u64, _u64, _sz, _pu64]),
+    "psg_cache_pack_bound": (C.c_int, [_sz, _sz, _psz, _psz]),
+    "psg_mb_cache_pack": (C.c_int, [_p, C.c_int, _sz, _p, _sz, _psz, _p, _sz, _psz,
+                                    C.POINTER(C.c_int64)]),
+    "psg_mb_load_cache": (C.c_int, [_p, C.POINTER(CacheFile), _sz, C.c_int,
+                                    C.POINTER(CacheResult)]),
+    "psg_cache_scan_tile": (_sz, []),
     "psg_mb_darling_share_dual": (C.c_int, [_p, _p]),
     "psg_auc_create": (C.c_int, [_p, C.c_int64, C.POINTER(_p)]),
     "psg_auc_destroy": (None, [_p]),

@@ -23,6 +23,10 @@ enum BufId {
   B_TEXT, B_TX_CHUNK, B_TX_LANE, B_TX_LINE_END, B_TX_SLOW, B_TX_PATCH, B_TX_WORDS,
   // psg_groups.hip: the entries' slot ids; two control words and the slots' statistics
   B_SLOT, B_GRP,
+  // psg_cache.hip: a raw cache array (pack) or the files' bytes (load); the
+  // streams (pack) or the staged rowsiz / value / label (load); the
+  // partitions' tables and the verdicts; the compressor's or decoder's scratch
+  B_CA_RAW, B_CA_OUT, B_CA_TAB, B_CA_SCR,
   B_COUNT
 };
 
