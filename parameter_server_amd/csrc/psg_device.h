@@ -113,6 +113,80 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// The tile kernels' search window: consecutive 8-B keys of the LDS image of D
+// from one slot on.  Written as plain loads, the compiler fuses each pair
+// into one two-address ds_read2_b64, which the LDS serves as two accesses of
+// 4 lane groups at 32-bank mapping: 8 LDS-array cycles per pair, where a
+// ds_read_b64 takes 2 and a ds_read_b128 4 (64-bank mapping), i.e. 16 cycles
+// for a 32-B window that needs 8.  The forms (PSG_LDSWIN, A/B builds;
+// profiles/ldswin_ab.txt):
+//   0  plain loads (fused)
+//   1  single-address ds_read_b64 in one asm statement.  The compiler does
+//      not count LDS reads issued by asm, so the statement waits for them
+//      itself, its outputs are early-clobber and it orders itself against
+//      the compiler's LDS accesses ("memory")
+//   2  (4 keys) the window start rounded down to even, read as two 16-B
+//      aligned ds_read_b128: lds_window4 returns that start, and the caller
+//      counts from it (the key before an odd bucket start lies in an earlier
+//      bucket, so it is below every key of this one)
+//   3  single-address ds_read_b64 the compiler issues and counts itself:
+//      each from its own copy of the address, made opaque by an empty asm
+//      statement, so no two share a base register to be fused on
+#ifndef PSG_LDSWIN
+#define PSG_LDSWIN 1
+#endif
+constexpr bool kWindowEven = PSG_LDSWIN == 2;
+typedef __attribute__((address_space(3))) const uint64_t* LdsKeys;
+__device__ __forceinline__ void lds_window2(const uint64_t* dk, uint32_t l, uint64_t& k0,
+                                            uint64_t& k1) {
+#if PSG_LDSWIN == 1
+  const uint32_t a = (uint32_t)(uintptr_t)(LdsPtr)(dk + l);
+  asm volatile(
+      "ds_read_b64 %0, %2\n\tds_read_b64 %1, %2 offset:8\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(k0), "=&v"(k1)
+      : "v"(a)
+      : "memory");
+#elif PSG_LDSWIN == 3
+  LdsKeys q = (LdsKeys)(dk + l);
+  k0 = q[0];
+  asm("" : "+v"(q));
+  k1 = q[1];
+#else
+  k0 = dk[l];
+  k1 = dk[l + 1];
+#endif
+}
+__device__ __forceinline__ uint32_t lds_window4(const uint64_t* dk, uint32_t l, uint64_t& k0,
+                                                uint64_t& k1, uint64_t& k2, uint64_t& k3) {
+#if PSG_LDSWIN == 1
+  const uint32_t a = (uint32_t)(uintptr_t)(LdsPtr)(dk + l);
+  asm volatile(
+      "ds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:8\n\t"
+      "ds_read_b64 %2, %4 offset:16\n\tds_read_b64 %3, %4 offset:24\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(k0), "=&v"(k1), "=&v"(k2), "=&v"(k3)
+      : "v"(a)
+      : "memory");
+#elif PSG_LDSWIN == 2
+  l &= ~1u;
+  const u64x2 x0 = *(const u64x2*)&dk[l], x1 = *(const u64x2*)&dk[l + 2];
+  k0 = x0.x; k1 = x0.y; k2 = x1.x; k3 = x1.y;
+#elif PSG_LDSWIN == 3
+  LdsKeys q = (LdsKeys)(dk + l);
+  k0 = q[0];
+  asm("" : "+v"(q));
+  k1 = q[1];
+  asm("" : "+v"(q));
+  k2 = q[2];
+  asm("" : "+v"(q));
+  k3 = q[3];
+#else
+  k0 = dk[l]; k1 = dk[l + 1]; k2 = dk[l + 2]; k3 = dk[l + 3];
+#endif
+  return l;
+}
+
 // ----------------------------------------------------------------------
 // wave-cooperative k-ary search: first index i in [0, n) whose key
 // satisfies (upper ? S[i] > key : S[i] >= key); n if none.  64 probes per

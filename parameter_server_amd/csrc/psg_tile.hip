@@ -472,8 +472,9 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
       continue;
     }
 #endif
-    // ---- search every held round: one bucket-table read, then a window of
-    // the 4 server keys from the bucket start, compared without branches.
+    // ---- search every held round: one bucket-table read (the bucket's
+    // start), then a window of the 4 server keys from the bucket start
+    // (dev::lds_window4: single-address reads), compared without branches.
     // The bucket map is monotone, so every key past the bucket is > k (and
     // the sentinels ~0 past the tile are >= k): c = window keys below k is
     // the lower bound inside the bucket whenever the bucket holds <= 4 keys
@@ -491,29 +492,34 @@ __global__ __launch_bounds__(nt_of(kGroup), (occupancy<V, M, kGroup>())) void ti
         const uint64_t k = ek[r];
         const uint32_t b = bucket(k);
         const uint32_t l = bt[b];
-        const uint32_t n = (uint32_t)bt[b + 1] - l;
-        const uint64_t* wk = dk + l;
-        const uint64_t k0 = wk[0], k1 = wk[1], k2 = wk[2], k3 = wk[3];
+        uint64_t k0, k1, k2, k3;
+        const uint32_t wl = lds_window4(dk, l, k0, k1, k2, k3);
         const uint32_t c = (uint32_t)(k0 < k) + (uint32_t)(k1 < k) + (uint32_t)(k2 < k) +
                            (uint32_t)(k3 < k);
-        const uint32_t p = l + c;
+        // (a window from the even slot below l: a key outside the tile's
+        // range counts nothing and stays at its end bucket's start)
+        const uint32_t p = kWindowEven && wl + c < l ? l : wl + c;
         pos[r] = p;
         // equality as lane masks (4 compares + 3 scalar ors)
         const uint64_t eq = __ballot(k0 == k) | __ballot(k1 == k) | __ballot(k2 == k) |
                             __ballot(k3 == k);
         const bool hit = ((eq >> lane) & 1ull) && p < nt;
         fd |= (uint32_t)hit << r;
-        deep |= (uint32_t)(c == 4u && n > 4u) << r;
+        deep |= (uint32_t)(c == 4u) << r;
       }
     }
-    if (__ballot(deep != 0u)) {  // long buckets: bisect the rest of the bucket
+    // long buckets: bisect the rest of the bucket.  The bucket's end is read
+    // only here, off the common path; a bucket that ends with the window has
+    // nothing left (n = 0), and its key stays not found at the window's end
+    if (__ballot(deep != 0u)) {
 #pragma unroll
       for (int r = 0; r < kCap; ++r) {
         if ((deep >> r) & 1u) {
           const uint64_t k = ek[r];
           const uint32_t b = bucket(k);
-          uint32_t l = bt[b] + 4u;
-          uint32_t n = (uint32_t)bt[b + 1] - l;
+          uint32_t l = (kWindowEven ? (uint32_t)bt[b] & ~1u : (uint32_t)bt[b]) + 4u;
+          const uint32_t e = bt[b + 1];
+          uint32_t n = e > l ? e - l : 0u;
           while (n > 0u) {
             const uint32_t half = n >> 1;
             if (dk[l + half] < k) {

@@ -718,7 +718,8 @@ __global__ __launch_bounds__(kNT, (occupancy<V, M>())) void tile_packed_kernel(
             n = half;
           }
         }
-        const uint64_t k0 = dk[l], k1 = dk[l + 1];
+        uint64_t k0, k1;
+        lds_window2(dk, l, k0, k1);
         pos[r] = l + ((n > 0u && k0 < k) ? 1u : 0u) + ((n > 1u && k1 < k) ? 1u : 0u);
         okm |= (uint32_t)((n > 0u && k0 == k) || (n > 1u && k1 == k)) << r;
       }
