@@ -356,6 +356,77 @@ int psg_key_union_dev(const uint64_t* a, uint64_t na, const uint64_t* b,
                       void* stream);
 
 /* ------------------------------------------------------------------ */
+/* Row-valued pushes: k values per key, folded and gathered on device  */
+/* ------------------------------------------------------------------ */
+/* A push whose value array holds k values per key, the k values of a key
+ * next to each other: the layout the reference's wire rule cuts at
+ * lr * (val.size() / key.size()) (sliceKeyOrderedMsg, system/message.h:116).
+ * The entries below lift the CHECK_EQ(recv_data.size(), recv_key.size()) of
+ * kv_vector.h:108,187 (PSG_ERR_SIZE elsewhere in this header) for device
+ * buffers: every column c of the result is, bit for bit, what the scalar
+ * plan gives for the pushes (keys, rows[:, c]).  Rows need element alignment
+ * only; when the row bytes and every rows / out pointer are multiples of 16
+ * the kernels move 16 B per lane. */
+typedef struct psg_rows_job {
+  const uint64_t* keys;      /* device: server keys D[lo, hi) (sorted unique) */
+  uint64_t nslots;           /* hi - lo; 0 is legal (nothing is written) */
+  int npush;                 /* pushes in arrival order; empty ones are legal */
+  const uint64_t* const* push_keys; /* host array[npush] of device pointers */
+  const void* const* push_rows;     /* host array[npush]: device, push_n[p] * k values */
+  const uint64_t* push_n;           /* host array[npush], each < 2^32 */
+  void* out;                 /* device: nslots * k values, row-major */
+} psg_rows_job;
+
+typedef struct psg_rows_plan psg_rows_plan;
+
+/* Lifts kv_vector.h:108 for a device-resident batch (rows as message.h:116
+ * lays them out).  All jobs share dtype, k and flags; flags is
+ * PSG_SERIAL_MATCH or PSG_PARALLEL_MATCH and nothing else (PSG_ERR_ARG);
+ * 1 <= k <= psg_rows_max_width(); npush <= psg_plan_max_push() per job.
+ * out[j][c] = the fold, in arrival order, of rows_p[i][c] over the pushes
+ * with push_keys_p[i] == keys[j], one rounded add each: the first non-empty
+ * push assigns (kv_vector.h:195-196), every other push adds, onto +0.0 where
+ * no push held the key before it.  PSG_SERIAL_MATCH adds one trailing +0.0 to every
+ * element of a row that some non-empty push lacks; a slot no push holds is a
+ * row of +0.0 in both modes.  A push key that is absent from keys, outside
+ * them or not above the key before it is unmatched and contributes nothing.
+ * The plan keeps no index of D and no hints: a run depends only on what the
+ * pointers hold, so keys and rows (not the lengths) may change between runs. */
+int psg_rows_plan_create(int device, int dtype, int k, unsigned flags,
+                         const psg_rows_job* jobs, int njobs, psg_rows_plan** out);
+/* Enqueue on `stream` (message.h:116 rows; lifts kv_vector.h:108): two
+ * launches, no allocation, no host wait, capturable like psg_plan_run. */
+int psg_rows_plan_run(psg_rows_plan* plan, void* stream);
+/* Synchronises the plan's last run and returns the matched count of every
+ * push (message.h:116 rows; lifts kv_vector.h:108), jobs in order. */
+int psg_rows_plan_matched(psg_rows_plan* plan, uint64_t* matched);
+/* Algorithmic bytes of a run of rows (message.h:116; lifts kv_vector.h:108):
+ * sum n_p (8 + k s_V) + nslots (8 + k s_V); kv_pairs = sum n_p. */
+int psg_rows_plan_bytes(psg_rows_plan* plan, uint64_t* bytes, uint64_t* kv_pairs);
+int psg_rows_plan_destroy(psg_rows_plan* plan);
+/* The widest row (message.h:116) for which kv_vector.h:108 is lifted: 256. */
+int psg_rows_max_width(void);
+/* How the kernels deal rows of k values of dtype (message.h:116; lifts
+ * kv_vector.h:108): shape[0] = T, the slots of a tile (a power of two);
+ * shape[1] = L, the lanes that share a row; shape[2] = E, the elements of one
+ * 16-B lane access; shape[3] = the rows a wave handles per pass (64 / L).  A
+ * lane makes ceil(k / (L E)) accesses per row.  A workgroup's LDS is
+ * T (k s_V + 12) + 64 bytes, at most 80 KB.  Host arithmetic only (the kernels
+ * read the same function); PSG_ERR_ARG for a bad k or dtype. */
+int psg_rows_shape(int dtype, int k, int shape[4]);
+/* The pull reply for rows (message.h:116; lifts kv_vector.h:108 for
+ * getValue, kv_vector.h:215-227): out[i] = the row of req[i] in drows (nd * k
+ * values beside dkeys), assigned, or a row of +0.0 where req[i] is not in
+ * dkeys.  As psg_gather_dev: a request key that repeats the one before it
+ * reads +0.0 and is not counted, the count found is added to *matched
+ * (device, nullable: zero it first), requests are expected in increasing
+ * order and, there being no context to defer an error to, an inversion is not
+ * reported (psg_pull_dev checks a context's requests).  Enqueues only. */
+int psg_gather_rows_dev(int dtype, int k, const uint64_t* dkeys, uint64_t nd,
+                        const void* drows, const uint64_t* req, uint64_t nreq,
+                        void* out, unsigned long long* matched, void* stream);
+
+/* ------------------------------------------------------------------ */
 /* N-way merge of sorted pushes into their merged key set  */
 /* ------------------------------------------------------------------ */
 /* out_keys = the union of the npush pushes' keys (SArray::setUnion applied

@@ -12,6 +12,7 @@ from .darling import DarlingWorker  # noqa: F401,E402
 from .auc import AUC, exact_auc  # noqa: F401,E402
 from .slots import SlotReader  # noqa: F401,E402
 from .slot_cache import CachedSlotReader  # noqa: F401,E402
+from .kv_vector import RowMergePlan, gather_rows_dev, rows_shape  # noqa: F401,E402
 
 __all__ = ["PSGError", "lib", "FTRLWorker", "Minibatch", "DarlingWorker", "AUC", "exact_auc",
-           "SlotReader", "CachedSlotReader"]
+           "SlotReader", "CachedSlotReader", "RowMergePlan", "gather_rows_dev", "rows_shape"]

@@ -105,6 +105,20 @@ class MergeJob(C.Structure):
     ]
 
 
+class RowsJob(C.Structure):
+    """psg_rows_job (include/psg.h)."""
+
+    _fields_ = [
+        ("keys", _p),
+        ("nslots", _u64),
+        ("npush", C.c_int),
+        ("push_keys", C.POINTER(_p)),
+        ("push_rows", C.POINTER(_p)),
+        ("push_n", _pu64),
+        ("out", _p),
+    ]
+
+
 class FtrlParam(C.Structure):
     """psg_ftrl_param (include/psg.h)."""
 
@@ -198,6 +212,15 @@ SIGNATURES = {
     "psg_plan_destroy": (C.c_int, [_p]),
     "psg_gather_dev": (C.c_int, [C.c_int, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     "psg_key_union_dev": (C.c_int, [_p, _u64, _p, _u64, _p, _pu64, _p]),
+    "psg_rows_plan_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint,
+                                       C.POINTER(RowsJob), C.c_int, C.POINTER(_p)]),
+    "psg_rows_plan_run": (C.c_int, [_p, _p]),
+    "psg_rows_plan_matched": (C.c_int, [_p, _pu64]),
+    "psg_rows_plan_bytes": (C.c_int, [_p, _pu64, _pu64]),
+    "psg_rows_plan_destroy": (C.c_int, [_p]),
+    "psg_rows_max_width": (C.c_int, []),
+    "psg_rows_shape": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "psg_gather_rows_dev": (C.c_int, [C.c_int, C.c_int, _p, _u64, _p, _p, _u64, _p, _p, _p]),
     "psg_shard_bounds": (C.c_int, [_sz, _pu64]),
     "psg_slice_dev": (C.c_int, [_p, _u64, _u64, _u64, _p, C.c_int, _p, _p]),
     "psg_crc32c_dev": (C.c_int, [_p, _p, _u64, _u64, _p, _p, _p]),

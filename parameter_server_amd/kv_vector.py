@@ -10,6 +10,7 @@ to libpsg.so; a failing reference ``CHECK`` surfaces as :class:`PSGError`.
 ``MergePlan`` is the device-resident batched form used by bench.py and the
 multi-GPU shards: every buffer is a device pointer (e.g. a torch tensor's
 ``data_ptr()``), and a run is two kernel launches on a caller stream.
+``RowMergePlan`` is its form for pushes that carry a row of k values per key.
 """
 from __future__ import annotations
 
@@ -324,6 +325,86 @@ class MergePlan:
             self.close()
         except Exception:
             pass
+
+
+class RowMergePlan:
+    """A prepared device-resident batch of merges of row-valued pushes
+    (psg_rows_plan_*): every key carries k values, stored next to each other.
+
+    jobs: list of dicts with device pointers
+        {"keys": int, "nslots": int, "push_keys": [int], "push_rows": [int],
+         "push_n": [int], "out": int}
+    push_rows[p] holds push_n[p] * k values, out nslots * k, both row-major.
+    """
+
+    def __init__(self, device: int, dtype: int, k: int, jobs: Sequence[dict],
+                 parallel_match: bool = False):
+        self._L = _lib.lib()
+        self._keep = []
+        cj = (_lib.RowsJob * max(1, len(jobs)))()
+        for j, J in enumerate(jobs):
+            npush = len(J["push_keys"])
+            pk = _lib.ptr_array(J["push_keys"])
+            pr = _lib.ptr_array(J["push_rows"])
+            pn = (C.c_uint64 * max(1, npush))(*J["push_n"])
+            self._keep += [pk, pr, pn]
+            cj[j].keys = J["keys"]
+            cj[j].nslots = J["nslots"]
+            cj[j].npush = npush
+            cj[j].push_keys = C.cast(pk, C.POINTER(C.c_void_p))
+            cj[j].push_rows = C.cast(pr, C.POINTER(C.c_void_p))
+            cj[j].push_n = C.cast(pn, C.POINTER(C.c_uint64))
+            cj[j].out = J["out"]
+        h = C.c_void_p()
+        flags = PSG_PARALLEL_MATCH if parallel_match else PSG_SERIAL_MATCH
+        _lib.check(self._L.psg_rows_plan_create(device, dtype, k, flags, cj, len(jobs),
+                                                C.byref(h)))
+        self._h = h
+        self.k = k
+        self.npush_total = sum(len(J["push_keys"]) for J in jobs)
+        b, kv = C.c_uint64(), C.c_uint64()
+        _lib.check(self._L.psg_rows_plan_bytes(h, C.byref(b), C.byref(kv)))
+        self.bytes, self.kv_pairs = b.value, kv.value
+
+    def run(self, stream: Optional[int] = None) -> None:
+        _lib.check(self._L.psg_rows_plan_run(self._h, stream or None))
+
+    def matched(self) -> np.ndarray:
+        """Synchronises; the matched count of every push, jobs in order."""
+        out = np.zeros(max(1, self.npush_total), np.uint64)
+        _lib.check(self._L.psg_rows_plan_matched(
+            self._h, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out[: self.npush_total]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psg_rows_plan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rows_shape(dtype: int, k: int) -> tuple:
+    """(T, L, E, R) of the row kernels for rows of k values (psg_rows_shape,
+    host arithmetic only): the slots of a tile, the lanes that share a row,
+    the elements of one lane access and the rows a wave handles per pass."""
+    shape = (C.c_int * 4)()
+    _lib.check(_lib.lib().psg_rows_shape(dtype, k, shape))
+    return tuple(shape)
+
+
+def gather_rows_dev(dtype: int, k: int, dkeys: int, nd: int, drows: int, req: int, nreq: int,
+                    out: int, matched: Optional[int] = None, stream: Optional[int] = None) -> None:
+    """The pull reply for rows (psg_gather_rows_dev): out[nreq][k] = the rows
+    of the sorted request keys req[nreq] among dkeys[nd] / drows[nd][k], +0.0
+    rows where absent; the count found is added to the device word `matched`.
+    All device pointers; enqueues only."""
+    _lib.check(_lib.lib().psg_gather_rows_dev(dtype, k, dkeys, nd, drows, req, nreq, out,
+                                              matched or None, stream or None))
 
 
 class NWayMergeBatch:
