@@ -930,9 +930,10 @@ size_t psg_mb_sort_tile(void);
  * copy and the result, or the line's rejection, is patched in.  Results do
  * not depend on how many tokens are slow.  A LIBSVM idx:val token counts as
  * one token and is slow if either half is.
- * Out of scope: TERAFEA, files, gzip, the protobuf and binary formats, text
- * that is already on the device.  ignore_feature_group = false is
- * psg_mb_load_text_groups, below. */
+ * Out of scope: files, gzip, the protobuf and binary formats, text that is
+ * already on the device, and TERAFEA on this (the online) path.
+ * ignore_feature_group = false is psg_mb_load_text_groups, below; TERAFEA
+ * is read by the grouped path only (psg_mb_load_terafea, below). */
 #define PSG_TEXT_ADFEA 4   /* DataConfig::ADFEA */
 #define PSG_TEXT_LIBSVM 5  /* DataConfig::LIBSVM */
 typedef struct psg_text_result {
@@ -1022,6 +1023,55 @@ int psg_text_parse_groups_host(const char* text, size_t nbytes, int format, size
                                psg_text_result* result);
 #define PSG_MB_SLOT 28   /* uint16[nnz]: the slot id of every entry (after psg_mb_load_text_groups
                           * or psg_mb_set_slots) */
+
+/* ------------------------------------------------------------------ */
+/* TERAFEA text ingest: ExampleParser::parseTerafea                    */
+/* (src/data/example_parser.cc:162-234), the format of the reference's */
+/* own CTR configuration (config/ctr_l1lr.conf, -shuffle_fea_id), for  */
+/* the grouped path.                                                   */
+/* ------------------------------------------------------------------ */
+/* Lines by the grouped parse's rule (FileLineReader's chop; `final` as above).
+ * Tokens split at " |" only, so '\t' and every other byte are token bytes.
+ * Token 0 is the label by strtoi32 (strtol base 10 truncated to int32,
+ * consumed to the end), y = label > 0 ? 1 : -1.  Token 1, the line id, is
+ * skipped unparsed.  Every further token is a key by strtou64 (strtoull base
+ * 10, consumed to the end; it saturates).  The keys of a line are sorted
+ * ascending, duplicates kept, and for each key in that order: its slot is
+ * key >> 54, its feature id the whole key, and with PSG_TERAFEA_SHUFFLE
+ * MurmurHash3_x64_128(id, 8, 512927377) folded o[0] ^ o[1].  Equal slots are
+ * neighbours after the sort, so every slot is one run of its row.  Every row
+ * of a line the length rule admits is sorted, whatever its length ("-1" is
+ * strtoull's 2^64 - 1, a two-byte key: about 20 K keys fit a line).  With
+ * PSG_TERAFEA_BETA one more entry ends every row, a row without a key
+ * included: feature id 0, not shuffled, in slot 1023.  The matrix is binary.
+ * Defined deviations, each a rejected line that ends the minibatch as above
+ * (rows before it kept, line consumed, bad_line set): a line with no token
+ * (the reference stores a label slot without a value); a line holding a key
+ * below 2^54, which is group 0 (the reference appends it to the label slot);
+ * the 61439-byte and NUL rules.
+ * The fast grammar: the label as the ADFEA label, a key as every key; any
+ * other token is a slow token through the host's libc call, patched in before
+ * the sort.  Results do not depend on how many tokens are slow.
+ * psg_mb_load_terafea leaves the minibatch exactly as psg_mb_load_text_groups
+ * leaves an ADFEA one (offset / index / y loaded, binary, the resident uint16
+ * slot array), so psg_mb_groups, psg_mb_group_extract and psg_mb_cache_pack
+ * work unchanged.  Errors and host waits are those of
+ * psg_mb_load_text_groups; unknown flag bits are PSG_ERR_ARG; PSG_ERR_SIZE
+ * also when PSG_TERAFEA_BETA is set and entries + rows reach 2^32 - 1.
+ * psg_mb_load_text and psg_mb_load_text_groups keep refusing format 6.
+ * psg_text_parse_terafea_host is the same parse serially on the host (two
+ * calls or one, as psg_text_parse_host; index, y and slot are written). */
+#define PSG_TEXT_TERAFEA 6     /* DataConfig::TERAFEA */
+#define PSG_TERAFEA_SHUFFLE 1u /* FLAGS_shuffle_fea_id */
+#define PSG_TERAFEA_BETA 2u    /* FLAGS_add_beta_feature */
+int psg_mb_load_terafea(psg_minibatch* mb, const char* text, size_t nbytes, unsigned flags,
+                        size_t max_rows, int final, psg_text_result* result);
+int psg_text_parse_terafea_host(const char* text, size_t nbytes, unsigned flags, size_t max_rows,
+                                int final, uint64_t* offset, uint64_t* index, double* y,
+                                uint16_t* slot, size_t rows_cap, size_t nnz_cap,
+                                psg_text_result* result);
+/* Entries per workgroup of the row sort (tests size rows by it). */
+size_t psg_terafea_tile(void);
 
 /* The slot ids of the loaded minibatch's entries: slot[n], a host array free
  * on return, n == nnz (PSG_ERR_SIZE otherwise); after psg_mb_load /

@@ -77,6 +77,9 @@ PSG_AUC_BY_KEY, PSG_AUC_AS_WRITTEN = 0, 1
 PSG_MB_OFFSET, PSG_MB_INDEX, PSG_MB_VALUE, PSG_MB_Y = range(24, 28)
 # psg_mb_load_text's formats (DataConfig's values)
 PSG_TEXT_ADFEA, PSG_TEXT_LIBSVM = 4, 5
+# ... and psg_mb_load_terafea's format and flags
+PSG_TEXT_TERAFEA = 6
+PSG_TERAFEA_SHUFFLE, PSG_TERAFEA_BETA = 1, 2
 # ... the entries' slot ids, and psg_slot_info's formats (SlotInfo)
 PSG_MB_SLOT = 28
 PSG_SLOT_DENSE, PSG_SLOT_SPARSE, PSG_SLOT_SPARSE_BINARY = 1, 2, 3
@@ -317,6 +320,11 @@ SIGNATURES = {
                                           C.POINTER(TextResult)]),
     "psg_text_parse_groups_host": (C.c_int, [_p, _sz, C.c_int, _sz, C.c_int, _p, _p, _p, _p, _p,
                                              _sz, _sz, C.POINTER(TextResult)]),
+    "psg_mb_load_terafea": (C.c_int, [_p, _p, _sz, C.c_uint, _sz, C.c_int,
+                                      C.POINTER(TextResult)]),
+    "psg_text_parse_terafea_host": (C.c_int, [_p, _sz, C.c_uint, _sz, C.c_int, _p, _p, _p, _p,
+                                              _sz, _sz, C.POINTER(TextResult)]),
+    "psg_terafea_tile": (_sz, []),
     "psg_mb_set_slots": (C.c_int, [_p, _p, _sz]),
     "psg_mb_groups": (C.c_int, [_p, C.POINTER(SlotInfo), _sz, _psz, C.POINTER(C.c_int64)]),
     "psg_mb_group_extract": (C.c_int, [_p, C.c_int, _p]),

@@ -102,4 +102,16 @@ int mb_load_finish(psg_minibatch* mb, size_t rows, size_t nnz, bool valued);
 // mb's dual block is about to go (a load, its destruction): its sharers lose
 // their Darling state, and mb stops sharing another's
 void mb_drop_sharing(psg_minibatch* mb);
+// psg_terafea.hip, enqueued on `s` by psg_mb_load_terafea.  raw[n]: the keys in
+// line order; offset[rows + 1]: the tokeniser's.
+// *bad = min(*bad, the first row holding a key of group 0)
+int terafea_check(const uint64_t* raw, const uint64_t* offset, uint32_t rows, uint32_t n,
+                  uint32_t* bad, hipStream_t s);
+// every row's keys ascending, in place
+int terafea_sort(uint64_t* raw, const uint64_t* offset, uint32_t rows, uint32_t n, hipStream_t s);
+// index / slot of the sorted keys (PSG_TERAFEA_* flags); with the beta entry
+// offset[r] += r and *nnz_kept += *rows_kept (device words)
+int terafea_finish(const uint64_t* raw, uint64_t* offset, uint32_t rows, uint32_t n,
+                   unsigned flags, uint64_t* index, uint16_t* slot, const uint32_t* rows_kept,
+                   uint32_t* nnz_kept, hipStream_t s);
 }  // namespace psg

@@ -7,7 +7,10 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
+#include <new>
 #include <string>
+#include <vector>
 
 #include "psg_host.h"
 
@@ -41,12 +44,14 @@ size_t token_end(const unsigned char* t, size_t nbytes, int libsvm, size_t s) {
   return e;
 }
 
-SlowPatch resolve_one(const unsigned char* t, size_t nbytes, int libsvm, bool grouped,
+// grouped: 0 the plain parse, 1 the grouped one, 2 TERAFEA
+SlowPatch resolve_one(const unsigned char* t, size_t nbytes, int libsvm, int grouped,
                       const SlowToken& k) {
   SlowPatch p{0, 0.0, 0, 0};
   if (k.start >= nbytes) return p;
   const size_t e = grouped && !libsvm
-                       ? k.start + grouped_field(t + k.start, nbytes - k.start, 0xfffffffeu)
+                       ? k.start + grouped_field(t + k.start, nbytes - k.start, 0xfffffffeu,
+                                                 grouped == 2 ? kTerafeaSep : ':')
                        : token_end(t, nbytes, libsvm, k.start);
   const std::string z((const char*)t + k.start, e - k.start);  // NUL-terminated copy
   switch (k.kind) {
@@ -141,7 +146,7 @@ bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, bool grouped,
     if (verdict == kReject) return false;
     if (verdict == kSlow) {
       ++*slow;
-      pt = resolve_one(t, ga ? nbytes : le, libsvm, grouped, st);
+      pt = resolve_one(t, ga ? nbytes : le, libsvm, grouped ? 1 : 0, st);
       if (!pt.ok) return false;
       if (st.kind == kAdfeaSlot) slot = (uint16_t)pt.key;
     }
@@ -170,8 +175,57 @@ bool parse_line(const unsigned char* t, size_t nbytes, int libsvm, bool grouped,
   return libsvm ? ord >= 1 : ord >= 3;
 }
 
-int parse(const unsigned char* t, size_t nbytes, int libsvm, bool grouped, size_t max_rows,
-          bool final, const Out& o, psg_text_result* r) {
+// One TERAFEA line [ls, le) (parseTerafea, example_parser.cc:171-234): the
+// keys of the line sorted, each one's group from its top 10 bits, the shuffle
+// and the beta entry.  keys: the caller's scratch.
+bool terafea_line(const unsigned char* t, size_t nbytes, unsigned flags, size_t ls, size_t le,
+                  const Out& o, size_t row, uint64_t* nnz, uint64_t* slow,
+                  std::vector<uint64_t>* keys) {
+  if (le - ls >= kMaxLine - 1) return false;
+  if (memchr(t + ls, 0, le - ls)) return false;
+  le = chopped_end(t, ls, le);
+  keys->clear();
+  uint32_t ord = 0;
+  size_t p = ls;
+  for (;; ++ord) {
+    while (p < le && (t[p] == ' ' || t[p] == kTerafeaSep)) ++p;
+    if (p >= le) break;
+    size_t e = p;
+    while (e < le && t[e] != ' ' && t[e] != kTerafeaSep) ++e;
+    SlowToken st{(uint32_t)p, (uint32_t)row, kNoDest, ord == 0 ? kAdfeaLabel : kAdfeaKey};
+    SlowPatch pt{0, 0.0, 1, 0};
+    int verdict = kFast;
+    if (ord == 0) verdict = grouped_label(t + p, nbytes - p, &pt.val, kTerafeaSep);
+    if (ord >= 2) verdict = grouped_key(t + p, nbytes - p, &pt.key, kTerafeaSep);
+    if (verdict == kSlow) {
+      ++*slow;
+      pt = resolve_one(t, nbytes, 0, 2, st);
+      if (!pt.ok) return false;
+    }
+    if (ord == 0 && o.y && row < o.rows_cap) o.y[row] = pt.val;
+    if (ord >= 2) {
+      if ((pt.key >> kGroupShift) == 0) return false;  // group 0: the label slot's id
+      keys->push_back(pt.key);
+    }
+    p = e;
+  }
+  if (ord == 0) return false;
+  std::sort(keys->begin(), keys->end());
+  const auto put = [&](uint64_t id, uint16_t slot) {
+    if (o.index && *nnz < o.nnz_cap) o.index[*nnz] = id;
+    if (o.slot && *nnz < o.nnz_cap) o.slot[*nnz] = slot;
+    ++*nnz;
+  };
+  for (const uint64_t key : *keys)
+    put(flags & PSG_TERAFEA_SHUFFLE ? murmur_shuffle(key) : key, (uint16_t)(key >> kGroupShift));
+  if (flags & PSG_TERAFEA_BETA) put(0, kBetaSlot);
+  return true;
+}
+
+// tflags < 0: LIBSVM / ADFEA; else TERAFEA with these flags
+int parse(const unsigned char* t, size_t nbytes, int libsvm, bool grouped, int tflags,
+          size_t max_rows, bool final, const Out& o, psg_text_result* r) {
+  std::vector<uint64_t> keys;
   uint64_t rows = 0, nnz = 0, slow = 0;
   size_t at = 0;
   int64_t bad = -1;
@@ -181,7 +235,10 @@ int parse(const unsigned char* t, size_t nbytes, int libsvm, bool grouped, size_
     if (!nl && !final) break;
     const size_t le = nl ? (size_t)(nl - t) + 1 : nbytes;
     uint64_t n = nnz;
-    const bool ok = parse_line(t, nbytes, libsvm, grouped, at, le, o, (size_t)rows, &n, &slow);
+    const bool ok =
+        tflags >= 0
+            ? terafea_line(t, nbytes, (unsigned)tflags, at, le, o, (size_t)rows, &n, &slow, &keys)
+            : parse_line(t, nbytes, libsvm, grouped, at, le, o, (size_t)rows, &n, &slow);
     at = le;
     if (!ok) {
       bad = (int64_t)rows;
@@ -205,7 +262,7 @@ int parse(const unsigned char* t, size_t nbytes, int libsvm, bool grouped, size_
 void resolve_slow(const unsigned char* text, size_t nbytes, int format_libsvm, int grouped,
                   const SlowToken* tok, size_t n, SlowPatch* patch) {
   for (size_t i = 0; i < n; ++i)
-    patch[i] = resolve_one(text, nbytes, format_libsvm, grouped != 0, tok[i]);
+    patch[i] = resolve_one(text, nbytes, format_libsvm, grouped, tok[i]);
 }
 
 }  // namespace text
@@ -227,7 +284,7 @@ int parse_entry(const char* text, size_t nbytes, int format, bool grouped, size_
     return psg::fail(PSG_ERR_ARG, "null output");
   const Out o{offset, offset ? index : nullptr, offset && libsvm ? value : nullptr,
               offset ? y : nullptr, offset && grouped ? slot : nullptr, rows_cap, nnz_cap};
-  if (int rc = parse(t, nbytes, libsvm, grouped, max_rows, final != 0, o, result)) return rc;
+  if (int rc = parse(t, nbytes, libsvm, grouped, -1, max_rows, final != 0, o, result)) return rc;
   if (offset && (result->rows > rows_cap || result->nnz > nnz_cap))
     return psg::fail(PSG_ERR_SIZE, "%llu rows and %llu entries, room for %zu and %zu",
                      (unsigned long long)result->rows, (unsigned long long)result->nnz, rows_cap,
@@ -252,4 +309,31 @@ extern "C" int psg_text_parse_groups_host(const char* text, size_t nbytes, int f
                                           psg_text_result* result) {
   return parse_entry(text, nbytes, format, true, max_rows, final, offset, index, value, y, slot,
                      rows_cap, nnz_cap, result);
+}
+
+extern "C" int psg_text_parse_terafea_host(const char* text, size_t nbytes, unsigned flags,
+                                           size_t max_rows, int final, uint64_t* offset,
+                                           uint64_t* index, double* y, uint16_t* slot,
+                                           size_t rows_cap, size_t nnz_cap,
+                                           psg_text_result* result) {
+  using namespace psg::text;
+  if (!result || (nbytes && !text)) return psg::fail(PSG_ERR_ARG, "null argument");
+  if (flags & ~(PSG_TERAFEA_SHUFFLE | PSG_TERAFEA_BETA))
+    return psg::fail(PSG_ERR_ARG, "TERAFEA flags %#x", flags);
+  if ((offset && !y && rows_cap) || (offset && (!index || !slot) && nnz_cap))
+    return psg::fail(PSG_ERR_ARG, "null output");
+  const Out o{offset, offset ? index : nullptr, nullptr, offset ? y : nullptr,
+              offset ? slot : nullptr, rows_cap, nnz_cap};
+  try {
+    if (int rc = parse((const unsigned char*)text, nbytes, 0, true, (int)flags, max_rows,
+                       final != 0, o, result))
+      return rc;
+  } catch (const std::bad_alloc&) {
+    return psg::fail(PSG_ERR_OOM, "host allocation");
+  }
+  if (offset && (result->rows > rows_cap || result->nnz > nnz_cap))
+    return psg::fail(PSG_ERR_SIZE, "%llu rows and %llu entries, room for %zu and %zu",
+                     (unsigned long long)result->rows, (unsigned long long)result->nnz, rows_cap,
+                     nnz_cap);
+  return PSG_OK;
 }

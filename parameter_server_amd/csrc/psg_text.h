@@ -181,15 +181,18 @@ PSG_HD bool fast_slot(const unsigned char* p, uint32_t len, uint32_t* id) {
 // the '\n', or the last byte of the text (a final line without '\n'; a
 // partial line that is not final is not taken at all).  next: the byte after
 // c; at_end: there is none.
-PSG_HD bool grouped_gap(unsigned char c, unsigned char next, bool at_end) {
-  return c == ' ' || c == ':' || c == '\n' || (c == '\r' && (at_end || next == '\n'));
+// sep: the format's second separator, ':' for ADFEA and '|' for TERAFEA.
+PSG_HD bool grouped_gap(unsigned char c, unsigned char next, bool at_end,
+                        unsigned char sep = ':') {
+  return c == ' ' || c == sep || c == '\n' || (c == '\r' && (at_end || next == '\n'));
 }
 // the length of the token at p, up to max + 1; avail: the bytes from p to the
 // end of the text
-PSG_HD uint32_t grouped_field(const unsigned char* p, size_t avail, uint32_t max) {
+PSG_HD uint32_t grouped_field(const unsigned char* p, size_t avail, uint32_t max,
+                              unsigned char sep = ':') {
   uint32_t e = 0;
   while (e < avail && e <= max &&
-         !grouped_gap(p[e], e + 1 < avail ? p[e + 1] : (unsigned char)0, e + 1 == avail))
+         !grouped_gap(p[e], e + 1 < avail ? p[e + 1] : (unsigned char)0, e + 1 == avail, sep))
     ++e;
   return e;
 }
@@ -200,12 +203,14 @@ PSG_HD bool grouped_follows(const unsigned char* p, size_t avail) {
   while (i < avail && (p[i] == ' ' || p[i] == ':')) ++i;
   return i < avail && !grouped_gap(p[i], i + 1 < avail ? p[i + 1] : (unsigned char)0, i + 1 == avail);
 }
-PSG_HD int grouped_label(const unsigned char* p, size_t avail, double* y) {
-  const uint32_t e = grouped_field(p, avail, kMaxField);
+PSG_HD int grouped_label(const unsigned char* p, size_t avail, double* y,
+                         unsigned char sep = ':') {
+  const uint32_t e = grouped_field(p, avail, kMaxField, sep);
   return e <= kMaxField && fast_label(p, e, y) ? kFast : kSlow;
 }
-PSG_HD int grouped_key(const unsigned char* p, size_t avail, uint64_t* key) {
-  const uint32_t e = grouped_field(p, avail, kMaxField);
+PSG_HD int grouped_key(const unsigned char* p, size_t avail, uint64_t* key,
+                       unsigned char sep = ':') {
+  const uint32_t e = grouped_field(p, avail, kMaxField, sep);
   return e <= kMaxField && fast_u64(p, e, key) ? kFast : kSlow;
 }
 PSG_HD int grouped_slot(const unsigned char* p, size_t avail, uint32_t* id) {
@@ -219,9 +224,47 @@ PSG_HD size_t chopped_end(const unsigned char* t, size_t ls, size_t le) {
   return le;
 }
 
+// ---- TERAFEA (include/psg.h, "TERAFEA text ingest") ---------------------------
+// The grouped parse's line rule with the separators " |": token 0 is the
+// label (kAdfeaLabel), token 1 is skipped, every further token is a key
+// (kAdfeaKey).  The group of a key is its top 10 bits; group 0 is rejected.
+constexpr unsigned char kTerafeaSep = '|';
+constexpr int kGroupShift = 54;
+constexpr uint16_t kBetaSlot = 1023;  // FLAGS_add_beta_feature's group; its feature id is 0
+
+// MurmurHash3_x64_128 of one 8-byte key with the seed of -shuffle_fea_id,
+// folded h1 ^ h2.  Eight bytes are a tail and no body block: the key goes
+// through c1, rotl 31, c2 into h1; then the length, the two adds, the final
+// mix of both halves and the two adds again.
+PSG_HD uint64_t murmur_fmix64(uint64_t k) {
+  k ^= k >> 33;
+  k *= 0xff51afd7ed558ccdull;
+  k ^= k >> 33;
+  k *= 0xc4ceb9fe1a85ec53ull;
+  k ^= k >> 33;
+  return k;
+}
+PSG_HD uint64_t murmur_shuffle(uint64_t key) {
+  uint64_t h1 = 512927377ull, h2 = 512927377ull;
+  uint64_t k1 = key * 0x87c37b91114253d5ull;
+  k1 = (k1 << 31) | (k1 >> 33);
+  k1 *= 0x4cf5ad432745937full;
+  h1 ^= k1;
+  h1 ^= 8u;
+  h2 ^= 8u;
+  h1 += h2;
+  h2 += h1;
+  h1 = murmur_fmix64(h1);
+  h2 = murmur_fmix64(h2);
+  h1 += h2;
+  h2 += h1;
+  return h1 ^ h2;
+}
+
 // The slow tokens through libc (psg_text.cc; host only).  patch[i] is what
 // the reference's call makes of tok[i].
-// grouped: the tokens are cut by the grouped parse's line rule.
+// grouped: 1, the tokens are cut by the grouped parse's line rule; 2, by
+// TERAFEA's (the same rule with '|' for ':').
 void resolve_slow(const unsigned char* text, size_t nbytes, int format_libsvm, int grouped,
                   const SlowToken* tok, size_t n, SlowPatch* patch);
 

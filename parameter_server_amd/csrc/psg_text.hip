@@ -118,7 +118,9 @@ __device__ __forceinline__ bool lane_tok_start(const Lane& l, int libsvm, int ga
                                                uint64_t nbytes) {
   if (!ga) return tok_start(libsvm, prev, c);
   const unsigned char next = j + 1 < l.n ? l.at(j + 1) : l.next;
-  return !grouped_gap(c, next, l.i0 + j + 1 == nbytes) && (prev == '\n' || is_delim(0, prev));
+  const unsigned char sep = ga == 2 ? kTerafeaSep : ':';  // ga 2: TERAFEA, the same rule at " |"
+  return !grouped_gap(c, next, l.i0 + j + 1 == nbytes, sep) &&
+         (prev == '\n' || prev == ' ' || prev == sep);
 }
 
 // the lane's newlines, token starts, and token starts after its last newline
@@ -315,7 +317,19 @@ __device__ __forceinline__ void lane_walk(const unsigned char* __restrict__ text
     uint32_t dest = kNone;
     uint64_t key = 0;
     double val = 0.0;
-    if (libsvm) {
+    if (ga == 2) {  // TERAFEA: the label, the line id (skipped), then raw keys
+      if (ord == 0) {
+        verdict = grouped_label(p, avail, &val, kTerafeaSep);
+        kind = kAdfeaLabel;
+        dest = line;
+      } else if (ord >= 2) {
+        verdict = grouped_key(p, avail, &key, kTerafeaSep);
+        kind = kAdfeaKey;
+        dest = fpos + feat;
+        ++feat;
+        featm |= 1u << j;
+      }
+    } else if (libsvm) {
       float f = 0.0f;
       if (ord == 0) {
         verdict = libsvm_label(p, avail, &f);
@@ -384,7 +398,7 @@ __device__ __forceinline__ void lane_walk(const unsigned char* __restrict__ text
   *nfeat = feat;
   *nslow = slow;
   if (!kEmit || !l.n) return;
-  const uint32_t min_tok = libsvm ? 1u : 3u;
+  const uint32_t min_tok = libsvm || ga == 2 ? 1u : 3u;
   if (l.prev == '\n' && line0 <= rows) o.offset[line0] = fpos;  // a line starts the lane
   for (uint32_t m = nlm; m; m &= m - 1) {
     const uint32_t j = (uint32_t)__ffs((int)m) - 1;
@@ -545,15 +559,20 @@ size_t psg_text_chunk(void) { return psg::kChunk; }
 
 namespace {
 
+// format PSG_TEXT_TERAFEA (psg_mb_load_terafea only): grouped, with its flags
 int load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format, size_t max_rows,
-              int final, bool grouped, psg_text_result* result) {
+              int final, bool grouped, unsigned tflags, psg_text_result* result) {
   using namespace psg;
   if (!mb || !result || (nbytes && !text)) return fail(PSG_ERR_ARG, "null argument");
-  if (format != PSG_TEXT_ADFEA && format != PSG_TEXT_LIBSVM)
+  const bool tera = format == PSG_TEXT_TERAFEA;
+  if (format != PSG_TEXT_ADFEA && format != PSG_TEXT_LIBSVM && !tera)
     return fail(PSG_ERR_ARG, "text format %d", format);
+  if (tflags & ~(PSG_TERAFEA_SHUFFLE | PSG_TERAFEA_BETA))
+    return fail(PSG_ERR_ARG, "TERAFEA flags %#x", tflags);
   if (nbytes >= 0xffffffffull) return fail(PSG_ERR_SIZE, "%zu bytes of text >= 2^32 - 1", nbytes);
   const int libsvm = format == PSG_TEXT_LIBSVM;
-  const int ga = grouped && !libsvm;  // grouped ADFEA: the line rule changes, slot tokens are read
+  // grouped ADFEA (1), TERAFEA (2): the line rule changes; ADFEA's slot tokens are read
+  const int ga = tera ? 2 : (grouped && !libsvm ? 1 : 0);
   const uint32_t want_rows = (uint32_t)std::min<size_t>(max_rows, 0xfffffffeull);
   *result = psg_text_result{0, 0, 0, -1, 0, -1.0};
   HIP_TRY(hipSetDevice(mb->device));
@@ -587,7 +606,11 @@ int load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format, si
     HIP_TRY(hipMemcpyAsync(h, words, 4 * W_COUNT, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));  // the sizes
   }
-  const size_t rows = h[W_ROWS], n = h[W_NNZ], nslow = h[W_SLOW];
+  // nraw: the entries the tokeniser emits; n: the matrix's, the beta entries included
+  const size_t rows = h[W_ROWS], nraw = h[W_NNZ], nslow = h[W_SLOW];
+  const size_t n = nraw + (tflags & PSG_TERAFEA_BETA ? rows : 0);
+  if (n >= 0xffffffffull)
+    return fail(PSG_ERR_SIZE, "%zu entries and %zu rows reach 2^32 - 1", nraw, rows);
   if (int rc = mb_load_begin(mb, rows, n, libsvm != 0)) return rc;
   if (grouped)
     if (int rc = mb->need(B_SLOT, 2 * n)) return rc;
@@ -598,12 +621,17 @@ int load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format, si
     const unsigned char* d_text = mb->at<unsigned char>(B_TEXT);
     uint32_t* words = mb->at<uint32_t>(B_TX_WORDS);
     const Chunks ch = chunks_of(mb->at<uint32_t>(B_TX_CHUNK), nc);
-    const Emit o{mb->at<uint64_t>(B_OFFSET), mb->at<uint64_t>(B_INDEX), mb->at<double>(B_VALUE),
-                 mb->at<double>(B_Y), grouped ? mb->at<uint16_t>(B_SLOT) : nullptr,
+    // TERAFEA: the raw keys in line order into one side of the sort's
+    // ping-pong (8 * n bytes, free until psg_mb_uniq); index and slot are the
+    // finish kernel's
+    uint64_t* raw = tera ? mb->at<uint64_t>(B_KEY_A) : nullptr;
+    const Emit o{mb->at<uint64_t>(B_OFFSET), tera ? raw : mb->at<uint64_t>(B_INDEX),
+                 mb->at<double>(B_VALUE), mb->at<double>(B_Y),
+                 grouped && !tera ? mb->at<uint16_t>(B_SLOT) : nullptr,
                  mb->at<uint32_t>(B_TX_LINE_END), mb->at<SlowToken>(B_TX_SLOW),
-                 words, (uint32_t)n, (uint32_t)nslow};
+                 words, (uint32_t)nraw, (uint32_t)nslow};
     uint64_t* h_n = (uint64_t*)(h + W_COUNT);  // pinned, and not read into again
-    *h_n = n;
+    *h_n = nraw;
     HIP_TRY(hipMemcpyAsync(o.offset + rows, h_n, 8, hipMemcpyHostToDevice, s));
     LAUNCH(emit_kernel, nc, s, d_text, (uint64_t)nbytes, libsvm, ga, final, ch,
            mb->at<uint16_t>(B_TX_LANE), (uint32_t)rows, o);
@@ -621,7 +649,8 @@ int load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format, si
       SlowToken* h_tok = (SlowToken*)(h_patch + nslow);
       HIP_TRY(hipMemcpyAsync(h_tok, o.slow, sizeof(SlowToken) * nslow, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));  // the slow tokens
-      resolve_slow((const unsigned char*)text, nbytes, libsvm, grouped, h_tok, nslow, h_patch);
+      resolve_slow((const unsigned char*)text, nbytes, libsvm, tera ? 2 : (grouped ? 1 : 0), h_tok,
+                   nslow, h_patch);
       HIP_TRY(hipMemcpyAsync(mb->b[B_TX_PATCH].p, h_patch, sizeof(SlowPatch) * nslow,
                              hipMemcpyHostToDevice, s));
       LAUNCH(patch_kernel, blocks_of(nslow, 256), s, o.slow, mb->at<SlowPatch>(B_TX_PATCH),
@@ -630,11 +659,22 @@ int load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format, si
     if (libsvm && n > 1)
       LAUNCH(order_kernel, blocks_of(n - 1, 256), s, o.offset, o.index, (uint32_t)rows,
              (uint32_t)n, words);
+    if (tera)
+      if (int rc = terafea_check(raw, o.offset, (uint32_t)rows, (uint32_t)nraw, words + W_BAD, s))
+        return rc;
     LAUNCH(line_kernel, blocks_of(rows, 256), s, o.line_end, (uint32_t)rows, words);
     hipLaunchKernelGGL(verdict_kernel, dim3(1), dim3(64), 0, s, o.offset, o.line_end,
                        (uint32_t)rows, words);
+    if (tera) {  // all the lines taken: what a rejected line drops is cut off below
+      if (int rc = terafea_sort(raw, o.offset, (uint32_t)rows, (uint32_t)nraw, s)) return rc;
+      if (int rc = terafea_finish(raw, o.offset, (uint32_t)rows, (uint32_t)nraw, tflags,
+                                  mb->at<uint64_t>(B_INDEX), mb->at<uint16_t>(B_SLOT),
+                                  words + W_ROWS_OUT, words + W_NNZ_OUT, s))
+        return rc;
+    }
     if (grouped && n)
-      LAUNCH(slot_bits_kernel, std::min<uint32_t>(blocks_of(n, 256), 1024u), s, o.slot, words);
+      LAUNCH(slot_bits_kernel, std::min<uint32_t>(blocks_of(n, 256), 1024u), s,
+             mb->at<uint16_t>(B_SLOT), words);
     if (int rc = launched("text verdict")) return rc;
     HIP_TRY(hipMemcpyAsync(h, words, 4 * W_COUNT, hipMemcpyDeviceToHost, s));
   } else {
@@ -670,12 +710,19 @@ int load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format, si
 
 int psg_mb_load_text(psg_minibatch* mb, const char* text, size_t nbytes, int format,
                      size_t max_rows, int final, psg_text_result* result) {
-  return load_text(mb, text, nbytes, format, max_rows, final, false, result);
+  if (format == PSG_TEXT_TERAFEA) return fail(PSG_ERR_ARG, "text format %d", format);
+  return load_text(mb, text, nbytes, format, max_rows, final, false, 0, result);
 }
 
 int psg_mb_load_text_groups(psg_minibatch* mb, const char* text, size_t nbytes, int format,
                             size_t max_rows, int final, psg_text_result* result) {
-  return load_text(mb, text, nbytes, format, max_rows, final, true, result);
+  if (format == PSG_TEXT_TERAFEA) return fail(PSG_ERR_ARG, "text format %d", format);
+  return load_text(mb, text, nbytes, format, max_rows, final, true, 0, result);
+}
+
+int psg_mb_load_terafea(psg_minibatch* mb, const char* text, size_t nbytes, unsigned flags,
+                        size_t max_rows, int final, psg_text_result* result) {
+  return load_text(mb, text, nbytes, PSG_TEXT_TERAFEA, max_rows, final, true, flags, result);
 }
 
 }  // extern "C"

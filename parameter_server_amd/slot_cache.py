@@ -313,7 +313,8 @@ class CachedSlotReader:
     the device of context ``ctx`` (a PSG_F64 context)."""
 
     def __init__(self, ctx, cache_prefix: str, fmt, chunk_bytes: int = DEFAULT_CHUNK_BYTES,
-                 part_bytes: int = DEFAULT_PART_BYTES, skip_bad: bool = True):
+                 part_bytes: int = DEFAULT_PART_BYTES, skip_bad: bool = True,
+                 shuffle: bool = False, beta: bool = False):
         if chunk_bytes < MIN_CHUNK_BYTES:
             raise ValueError("chunk_bytes below %d" % MIN_CHUNK_BYTES)
         if part_bytes % 8:
@@ -321,7 +322,8 @@ class CachedSlotReader:
         self._ctx = ctx
         self.prefix = cache_prefix
         self.fmt = fmt
-        self.valued = _format(fmt) == _lib.PSG_TEXT_LIBSVM
+        self.valued = _format(fmt) == _lib.PSG_TEXT_LIBSVM  # ADFEA and TERAFEA are binary
+        self.shuffle, self.beta = bool(shuffle), bool(beta)  # fmt "terafea" only
         self.chunk_bytes, self.part_bytes, self.skip_bad = int(chunk_bytes), int(part_bytes), skip_bad
         self._sr: Optional[SlotReader] = None
         self._tmp: Optional[Minibatch] = None
@@ -386,7 +388,7 @@ class CachedSlotReader:
         line0 = 0
         for text, final in self._chunks(path):
             if text:
-                sr.read(text, self.fmt, self.skip_bad, final)
+                sr.read(text, self.fmt, self.skip_bad, final, self.shuffle, self.beta)
                 self.bad_lines += [(path, line0 + b) for b in sr.bad_lines]
                 line0 += text.count(b"\n") + (0 if text.endswith(b"\n") else 1)
                 if sr.num_ex:

@@ -25,19 +25,31 @@ import numpy as np
 
 from . import _lib
 from .kv_vector import _ptr
-from .worker import Minibatch, _format
+from .worker import Minibatch, _format, terafea_flags
 
 SLOT_MAX = 4096  # kSlotIDmax: the ids are 1 .. 4095
 
 
-def parse_text_groups_host(text: bytes, fmt, max_rows=None, final: bool = True):
+def parse_text_groups_host(text: bytes, fmt, max_rows=None, final: bool = True,
+                           shuffle: bool = False, beta: bool = False):
     """psg_text_parse_groups_host: (offset, index, value or None, y, slot,
-    result), parsed serially on the host."""
+    result), parsed serially on the host.  ``fmt`` "terafea" (with
+    ``shuffle`` / ``beta``) is psg_text_parse_terafea_host."""
     L = _lib.lib()
     text = bytes(text)
     f = _format(fmt)
     cap = (1 << 64) - 1 if max_rows is None else int(max_rows)
     r = _lib.TextResult()
+    if f == _lib.PSG_TEXT_TERAFEA:
+        fl, fin = terafea_flags(shuffle, beta), 1 if final else 0
+        _lib.check(L.psg_text_parse_terafea_host(text, len(text), fl, cap, fin, None, None, None,
+                                                 None, 0, 0, C.byref(r)))
+        offset, index = np.zeros(r.rows + 1, np.uint64), np.zeros(r.nnz, np.uint64)
+        y, slot = np.zeros(r.rows, np.float64), np.zeros(r.nnz, np.uint16)
+        _lib.check(L.psg_text_parse_terafea_host(text, len(text), fl, cap, fin, _ptr(offset),
+                                                 _ptr(index), _ptr(y), _ptr(slot), int(r.rows),
+                                                 int(r.nnz), C.byref(r)))
+        return offset, index, None, y, slot, r
     _lib.check(L.psg_text_parse_groups_host(text, len(text), f, cap, 1 if final else 0, None, None,
                                             None, None, None, 0, 0, C.byref(r)))
     offset = np.zeros(r.rows + 1, np.uint64)
@@ -83,10 +95,11 @@ class _Kept:
         del self.lines[i], self.orig[i]
 
 
-def _parse_kept(kept: _Kept, fmt, skip_bad: bool):
+def _parse_kept(kept: _Kept, fmt, skip_bad: bool, **tera):
     while True:
         # every kept line ends in '\n' or is the last: the buffer is final
-        offset, index, value, y, slot, r = parse_text_groups_host(kept.text(), fmt, None, True)
+        offset, index, value, y, slot, r = parse_text_groups_host(kept.text(), fmt, None, True,
+                                                                  **tera)
         if r.bad_line < 0:
             return offset, index, value, y, slot
         if not skip_bad:
@@ -95,7 +108,7 @@ def _parse_kept(kept: _Kept, fmt, skip_bad: bool):
         kept.drop(int(r.bad_line))
 
 
-def parse_groups_skipping(text: bytes, fmt, skip_bad: bool = True, final: bool = True):
+def parse_groups_skipping(text: bytes, fmt, skip_bad: bool = True, final: bool = True, **tera):
     """The grouped host parse of all of ``text`` with SlotReader's skip
     (slot_reader.cc:148): a line the parse rejects is cut out of the buffer
     and the buffer is parsed again, so a skipped line has no effect.  Returns
@@ -103,7 +116,7 @@ def parse_groups_skipping(text: bytes, fmt, skip_bad: bool = True, final: bool =
     skipped lines' numbers in ``text``.  Without ``skip_bad`` a rejected line
     raises PSGError(PSG_ERR_ARG)."""
     kept = _Kept(text, final)
-    return _parse_kept(kept, fmt, skip_bad) + (list(kept.bad),)
+    return _parse_kept(kept, fmt, skip_bad, **tera) + (list(kept.bad),)
 
 
 def info_dict(s: "_lib.SlotInfo") -> dict:
@@ -150,9 +163,10 @@ class SlotReader:
     def close(self):
         self.mb.close()
 
-    def read(self, text: bytes, fmt, skip_bad: bool = True, final: bool = True) -> List[dict]:
-        """The grouped load of ``text`` ("adfea", "libsvm" or a PSG_TEXT_* id)
-        and psg_mb_groups.  With ``skip_bad`` a line that either stage
+    def read(self, text: bytes, fmt, skip_bad: bool = True, final: bool = True,
+             shuffle: bool = False, beta: bool = False) -> List[dict]:
+        """The grouped load of ``text`` ("adfea", "libsvm", "terafea" with its
+        ``shuffle`` / ``beta``, or a PSG_TEXT_* id) and psg_mb_groups.  With ``skip_bad`` a line that either stage
         reports (the parse: a rejected line; the grouping: a slot id in two
         separate runs of a row) is cut out of the host buffer and the buffer
         is read again, so a skipped line has no effect; the skipped lines'
@@ -163,7 +177,10 @@ class SlotReader:
         kept = _Kept(text, final)
         while True:
             # every kept line ends in '\n' or is the last: the buffer is final
-            r = self.mb.load_text_groups(kept.text(), fmt, None, True)
+            if _format(fmt) == _lib.PSG_TEXT_TERAFEA:
+                r = self.mb.load_terafea(kept.text(), shuffle, beta, None, True)
+            else:
+                r = self.mb.load_text_groups(kept.text(), fmt, None, True)
             bad, why = int(r.bad_line), "is rejected"
             if bad < 0:
                 info, bad = mb_groups(self.mb)  # every kept line is a row: row r is kept line r

@@ -58,7 +58,18 @@ def text_chunk() -> int:
 
 
 def _format(fmt) -> int:
+    if fmt == "terafea":  # the grouped path's own calls (load_terafea); no entry of FORMATS
+        return _lib.PSG_TEXT_TERAFEA
     return FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+
+
+def terafea_tile() -> int:
+    """Entries per workgroup of the TERAFEA row sort (psg_terafea_tile)."""
+    return int(_lib.lib().psg_terafea_tile())
+
+
+def terafea_flags(shuffle: bool, beta: bool) -> int:
+    return (_lib.PSG_TERAFEA_SHUFFLE if shuffle else 0) | (_lib.PSG_TERAFEA_BETA if beta else 0)
 
 
 def parse_text_host(text: bytes, fmt, max_rows=None, final: bool = True):
@@ -154,6 +165,21 @@ class Minibatch:
         r = _lib.TextResult()
         _lib.check(self._L.psg_mb_load_text_groups(self._h, text, len(text), _format(fmt), cap,
                                                    1 if final else 0, C.byref(r)))
+        self.rows, self.nnz = int(r.rows), int(r.nnz)
+        self.n_uniq = self.ndict = 0
+        return r
+
+    def load_terafea(self, text: bytes, shuffle: bool = False, beta: bool = False, max_rows=None,
+                     final: bool = True):
+        """psg_mb_load_terafea: TERAFEA lines parsed on the device, every
+        line's keys sorted, split by group and (``shuffle``) hashed, with the
+        ``beta`` entry; leaves the minibatch as ``load_text_groups`` does."""
+        text = bytes(text) if not isinstance(text, bytes) else text
+        cap = (1 << 64) - 1 if max_rows is None else int(max_rows)
+        r = _lib.TextResult()
+        _lib.check(self._L.psg_mb_load_terafea(self._h, text, len(text),
+                                               terafea_flags(shuffle, beta), cap,
+                                               1 if final else 0, C.byref(r)))
         self.rows, self.nnz = int(r.rows), int(r.nnz)
         self.n_uniq = self.ndict = 0
         return r
