@@ -769,6 +769,70 @@ int psg_ftrl_export_state_dev(psg_ctx* ctx, const uint64_t* range, uint64_t* key
 int psg_ftrl_frozen(psg_ctx* ctx, int* frozen);
 
 /* ------------------------------------------------------------------ */
+/* Multi-model FTRL: m settings (alpha, beta, lambda1, lambda2) per    */
+/* key in one table, what ftrl_model.h:51 leaves as                    */
+/* `TODO ... support multi-model`.  One pass over a message updates    */
+/* all m models of every key.                                          */
+/* ------------------------------------------------------------------ */
+/* 1 <= m <= PSG_FTRL_MAX_MODELS.  Every row-valued array is row-major
+ * [n][m]: model j of key i at [i * m + j].  Column j of everything below is
+ * bit for bit what a psg_ftrl_* model with setting p[j] gives for the same
+ * messages: setValue (ftrl_model.h:80-112) runs for every (key, j) with p[j],
+ * grad_norm (:60-63) of the shared counts once per key, and pos / neg are
+ * added once per key.  The multi-model is independent of the context's
+ * psg_ftrl_* model (both may live in one context); it needs a PSG_F64 context
+ * and every call before psg_ftrlm_init is PSG_ERR_ARG.  Messages apply in call
+ * order whatever streams the device forms are given.
+ * Defined deviations, as for psg_ftrl_*:
+ *  - a pull does not insert (ftrl_model.h:76); `entries` counts the keys
+ *    touched by a push;
+ *  - norm1[j] / norm2[j] are a device reduction over the rows of the table
+ *    computed by psg_ftrlm_status, each within entries * 2^-53 * (the exact
+ *    sum) of it.  Rows are numbered in the order the device claimed them, so
+ *    the reduction order, and with it the last bits of the norms, can differ
+ *    from run to run of the same messages; entries and every nnz[j] are exact;
+ *  - a pushed message must be strictly increasing; one that is not is
+ *    rejected whole by a device check that runs ahead of the update, reported
+ *    once as PSG_ERR_UNSORTED by the next psg_ftrlm_pull, psg_ftrlm_status or
+ *    psg_ftrlm_export, and then cleared; later messages apply normally.
+ *    psg_ftrlm_lookup neither reports nor clears it;
+ *  - psg_ftrlm_export's order is unspecified; the Python mirror sorts by key.
+ * Not built for the multi-model: checkpoint and whole-state export
+ * (psg_ftrl_import / psg_ftrl_export_state), the frozen weights-only form,
+ * and the C++ adapter. */
+#define PSG_FTRL_MAX_MODELS 32
+/* A fresh, empty multi-model of p[m], sized for capacity_hint keys (0: a
+ * default; the table grows: the index is rebuilt, the rows are copied).
+ * m < 1 or m > PSG_FTRL_MAX_MODELS is PSG_ERR_ARG. */
+int psg_ftrlm_init(psg_ctx* ctx, const psg_ftrl_param* p, int m, size_t capacity_hint);
+/* Room for `entries` keys: pushes allocate nothing and read no device count
+ * until the keys pushed could number more than that. */
+int psg_ftrlm_reserve(psg_ctx* ctx, size_t entries);
+/* setValue for all m models: keys[n], pos[n], neg[n], grad[n * m].  Host
+ * arrays, free on return; asynchronous on the context's stream. */
+int psg_ftrlm_push(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint32_t* pos,
+                   const uint32_t* neg, const double* grad);
+/* The same with device arrays, enqueued on `stream`; allocates nothing and
+ * waits for nothing while the model has room (psg_ftrlm_reserve). */
+int psg_ftrlm_push_dev(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint32_t* pos,
+                       const uint32_t* neg, const double* grad, void* stream);
+/* getValue (ftrl_model.h:72-78): out[n * m] = the w rows, +0.0 for a key
+ * never pushed.  Keys in any order, repeats allowed. */
+int psg_ftrlm_pull(psg_ctx* ctx, const uint64_t* keys, size_t n, double* out);
+int psg_ftrlm_pull_dev(psg_ctx* ctx, const uint64_t* keys, size_t n, double* out, void* stream);
+/* entries = model_.size(); nnz[m], norm1[m], norm2[m] per model (ftrl_model.h
+ * :31-32).  Any output may be NULL.  Synchronises. */
+int psg_ftrlm_status(psg_ctx* ctx, size_t* entries, size_t* nnz, double* norm1, double* norm2);
+/* Whole entries (tests): found[i] = 1 and pos[i], neg[i], w[i * m + j],
+ * z[i * m + j] of keys[i], or 0 and zeros.  Any output may be NULL. */
+int psg_ftrlm_lookup(psg_ctx* ctx, const uint64_t* keys, size_t n, uint64_t* pos, uint64_t* neg,
+                     double* w, double* z, uint8_t* found);
+/* writeToFile's content (ftrl_model.h:24-29) for model j: (key, w) of every
+ * key whose model-j weight is nonzero, order unspecified.  *n = their count;
+ * PSG_ERR_SIZE (nothing copied) if that exceeds cap. */
+int psg_ftrlm_export(psg_ctx* ctx, int j, uint64_t* keys, double* w, size_t cap, size_t* n);
+
+/* ------------------------------------------------------------------ */
 /* Online worker step: FTRL::updateModel's minibatch loop              */
 /* (src/linear_method/ftrl.cc:88-151) on a minibatch resident in HBM:  */
 /* Localizer (src/base/localizer.h), FTRL::countKeys, Xw = Z * w,      */
@@ -835,6 +899,34 @@ int psg_mb_trans_times(psg_minibatch* mb, const double* c_dev, double* g_dev, vo
 #define PSG_LOSS_LOGIT 0
 int psg_mb_gradient(psg_minibatch* mb, int loss, const double* w_dev, const double** grad_dev,
                     double* objv, void* stream);
+/* The same three for m models at once (a sweep of FTRL settings over one
+ * minibatch; the server side is psg_ftrlm_*).  Row-valued arrays are row-major:
+ * x[ndict * m], xw[rows * m], c[rows * m], g[ndict * m], model j of item i at
+ * [i * m + j]; 1 <= m <= PSG_FTRL_MAX_MODELS.  Each runs after psg_mb_localize
+ * (PSG_ERR_ARG before it) and obeys the minibatch's call order; their buffers
+ * live with the minibatch and only grow.  Column j of every output is bit for
+ * bit what psg_mb_times, psg_mb_trans_times and psg_mb_gradient give for
+ * column j alone: one rounded multiply and one rounded add per entry in the
+ * reference's order, and objv[j] by the same fixed-order reduction (a tree
+ * over each 256 rows, then over those sums).  The defined deviations of the
+ * scalar calls hold (an empty row, ndict == 0, LOGIT only, an unsorted
+ * dictionary reported by psg_mb_gradient_rows as PSG_ERR_UNSORTED).
+ * psg_mb_gradient_rows: *grad_dev = the device gradient [ndict * m], objv[m]
+ * on the host; synchronises.  It does not touch the arrays of psg_mb_gradient
+ * (psg_mb_read's XW, TAU, LOSS, GRAD); psg_mb_rows_read reads its own. */
+int psg_mb_times_rows(psg_minibatch* mb, const double* x_dev, int m, double* xw_dev, void* stream);
+int psg_mb_trans_times_rows(psg_minibatch* mb, const double* c_dev, int m, double* g_dev,
+                            void* stream);
+int psg_mb_gradient_rows(psg_minibatch* mb, int loss, const double* w_dev, int m,
+                         const double** grad_dev, double* objv, void* stream);
+/* Tests: one row-valued array of the last psg_mb_gradient_rows to the host,
+ * as psg_mb_read; PSG_ERR_ARG when no psg_mb_gradient_rows has run since the
+ * last psg_mb_localize. */
+#define PSG_MB_ROWS_XW 0    /* double[rows * m] */
+#define PSG_MB_ROWS_TAU 1   /* double[rows * m] */
+#define PSG_MB_ROWS_LOSS 2  /* double[rows * m] */
+#define PSG_MB_ROWS_GRAD 3  /* double[ndict * m] */
+int psg_mb_rows_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t* n);
 /* Tests and checkpoints: one internal array to the host, after a wait.  *n =
  * its element count; PSG_ERR_SIZE (nothing copied) if cap_bytes is short. */
 #define PSG_MB_SORTED_KEY 0  /* uint64[nnz]: the sorted pairs' keys */

@@ -68,6 +68,9 @@ PSG_LOSS_LOGIT = 0
 (PSG_MB_SORTED_KEY, PSG_MB_SORTED_POS, PSG_MB_UNIQ_KEY, PSG_MB_KEY_CNT, PSG_MB_NEW_OFFSET,
  PSG_MB_NEW_INDEX, PSG_MB_NEW_VALUE, PSG_MB_POS, PSG_MB_NEG, PSG_MB_XW, PSG_MB_TAU, PSG_MB_LOSS,
  PSG_MB_GRAD, PSG_MB_RUN_START, PSG_MB_REMAPPED, PSG_MB_ROW_OF, PSG_MB_SCRATCH) = range(17)
+# psg_ftrlm_*'s model count and psg_mb_rows_read's arrays
+PSG_FTRL_MAX_MODELS = 32
+PSG_MB_ROWS_XW, PSG_MB_ROWS_TAU, PSG_MB_ROWS_LOSS, PSG_MB_ROWS_GRAD = range(4)
 # psg_auc_evaluate's modes
 PSG_AUC_BY_KEY, PSG_AUC_AS_WRITTEN = 0, 1
 # ... and the Darling worker's state (psg_mb_darling_*)
@@ -291,6 +294,15 @@ SIGNATURES = {
     "psg_ftrl_export_state": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _psz]),
     "psg_ftrl_export_state_dev": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "psg_ftrl_frozen": (C.c_int, [_p, C.POINTER(C.c_int)]),
+    "psg_ftrlm_init": (C.c_int, [_p, _p, C.c_int, _sz]),
+    "psg_ftrlm_reserve": (C.c_int, [_p, _sz]),
+    "psg_ftrlm_push": (C.c_int, [_p, _p, _sz, _p, _p, _p]),
+    "psg_ftrlm_push_dev": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p]),
+    "psg_ftrlm_pull": (C.c_int, [_p, _p, _sz, _p]),
+    "psg_ftrlm_pull_dev": (C.c_int, [_p, _p, _sz, _p, _p]),
+    "psg_ftrlm_status": (C.c_int, [_p, _psz, _p, _p, _p]),
+    "psg_ftrlm_lookup": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _p]),
+    "psg_ftrlm_export": (C.c_int, [_p, C.c_int, _p, _p, _sz, _psz]),
     "psg_mb_create": (C.c_int, [_p, C.POINTER(_p)]),
     "psg_mb_destroy": (None, [_p]),
     "psg_mb_load": (C.c_int, [_p, _p, _sz, _p, _p, _p]),
@@ -299,6 +311,10 @@ SIGNATURES = {
     "psg_mb_times": (C.c_int, [_p, _p, _p, _p]),
     "psg_mb_trans_times": (C.c_int, [_p, _p, _p, _p]),
     "psg_mb_gradient": (C.c_int, [_p, C.c_int, _p, C.POINTER(_p), C.POINTER(C.c_double), _p]),
+    "psg_mb_times_rows": (C.c_int, [_p, _p, C.c_int, _p, _p]),
+    "psg_mb_trans_times_rows": (C.c_int, [_p, _p, C.c_int, _p, _p]),
+    "psg_mb_gradient_rows": (C.c_int, [_p, C.c_int, _p, C.c_int, C.POINTER(_p), _p, _p]),
+    "psg_mb_rows_read": (C.c_int, [_p, C.c_int, _p, _sz, _psz]),
     "psg_mb_read": (C.c_int, [_p, C.c_int, _p, _sz, _psz]),
     "psg_mb_scratch": (C.c_int, [_p, C.c_int, _sz, C.POINTER(_p)]),
     "psg_mb_profile": (C.c_int, [_p, C.c_int]),

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/psg.h"
+#include "psg_ftrl_rows.h"
 #include "psg_host.h"
 #include "psg_internal.h"
 #include "psg_jobtable.h"
@@ -240,6 +241,33 @@ struct Ftrl {
   }
 };
 
+// The multi-model FTRL of the context (psg_ftrlm_*): m settings per key over
+// the index and row store of psg_ftrl_rows.h.  Independent of `Ftrl`.
+struct Ftrlm {
+  bool on = false;
+  int m = 0;
+  psg::FtrlmSlot* d_idx = nullptr;
+  uint64_t nslots = 0;  // a power of two
+  uint64_t* d_cnt = nullptr;
+  double* d_w = nullptr;
+  double* d_z = nullptr;
+  psg::FtrlmHead* d_head = nullptr;
+  size_t bound = 0;  // as Ftrl::bound
+  hipEvent_t last = nullptr;
+  hipStream_t last_s = nullptr;
+  // at most half of the slots are taken; row 0 is key 0's
+  size_t limit() const { return (size_t)(nslots / 2); }
+  uint64_t row_cap() const { return nslots / 2 + 1; }
+  psg::FtrlmTable table() const {
+    return psg::FtrlmTable{d_idx, nslots - 1, d_cnt, d_w, d_z, row_cap(), d_head, (uint32_t)m,
+                           psg::group_shift(m)};
+  }
+  static uint64_t slots_for(size_t entries) {
+    uint64_t ns = 8;  // one 128-B line
+    while (ns / 2 < entries) ns *= 2;
+    return ns;
+  }
+};
 
 #ifndef PSG_SPIN
 #define PSG_SPIN 1
@@ -269,6 +297,7 @@ inline hipError_t spin_wait(hipEvent_t e) {
 // defined with their sections, called by psg_destroy
 void filter_release(psg_ctx* c, Filter& F);
 void ftrl_release(psg_ctx* c);
+void ftrlm_release(psg_ctx* c);
 
 }  // namespace psg
 
@@ -290,6 +319,7 @@ struct psg_ctx {
   std::map<CacheKey, CacheEntry> kcache;
   std::unordered_map<int, Filter> ff;
   Ftrl ftrl;
+  Ftrlm ftrlm;
   JobTable table;
   unsigned long long* d_small = nullptr;  // 32 device words: counters, crc args
   unsigned long long* d_vio_slots = nullptr;  // psg::kVioSlots x 64 B, zero between updates

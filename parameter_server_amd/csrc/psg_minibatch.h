@@ -27,6 +27,9 @@ enum BufId {
   // streams (pack) or the staged rowsiz / value / label (load); the
   // partitions' tables and the verdicts; the compressor's or decoder's scratch
   B_CA_RAW, B_CA_OUT, B_CA_TAB, B_CA_SCR,
+  // psg_worker_rows.hip: Xw, tau, c, loss [rows][m], the loss partials
+  // [workgroups][m], the gradient [ndict][m], objv [m], the term rows [nnz][m]
+  B_R_XW, B_R_TAU, B_R_C, B_R_LOSS, B_R_PARTIAL, B_R_GRAD, B_R_OBJV, B_R_TERM,
   B_COUNT
 };
 
@@ -47,6 +50,8 @@ struct psg_minibatch : psg::DeviceBlocks<B_COUNT> {
   // (g): set by psg_mb_darling_init, cleared by psg_mb_load and psg_mb_localize
   bool darling = false;
   bool xw_own = false;  // psg_mb_times has run into the minibatch's own Xw (psg_mb_labels)
+  // the m of the last psg_mb_gradient_rows since the load and the localize (0: none)
+  int rows_m = 0;
   const uint32_t* row_pair = nullptr;  // the rows' lists (one side of their ping-pong)
   // host: pair_lo[k] = the first sorted pair of the first of keys k, k + 1, ...
   // that has a run (nnz: none); pair_hi[k] = the end of the last run among

@@ -112,6 +112,7 @@ int psg_destroy(psg_ctx* c) {
   for (auto& kv : c->ff) filter_release(c, kv.second);
   c->ff.clear();
   ftrl_release(c);
+  ftrlm_release(c);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   for (auto& f : c->fly) c->free_ev.push_back(f.ev);
   c->fly.clear();

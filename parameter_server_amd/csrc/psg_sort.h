@@ -17,6 +17,9 @@
 #ifndef PSG_SORT_KPT
 #define PSG_SORT_KPT 8  // A/B builds: 4, 16, 32
 #endif
+#ifndef PSG_LONG_RUN
+#define PSG_LONG_RUN 32  // A/B builds: 8, 256
+#endif
 
 namespace psg {
 namespace {
@@ -25,6 +28,11 @@ constexpr int kSortKPT = PSG_SORT_KPT;           // pairs per lane per tile
 constexpr uint32_t kSortTile = 256 * kSortKPT;   // pairs per workgroup
 constexpr uint32_t kWaveSpan = 64 * kSortKPT;    // pairs per wave
 constexpr uint32_t kFlagTile = 2048;             // elements per workgroup of the flag scans
+// The long runs of a localized minibatch: psg_worker.hip lists them at
+// localize and sums them a wave each, and psg_worker_rows.hip walks the same
+// list, so both read the split from here.
+constexpr uint32_t kLongGrid = 1024;             // workgroups (of 4 waves) over the long runs
+constexpr uint32_t kLongRun = PSG_LONG_RUN;      // runs longer than this go to the whole wave
 
 // XCD-contiguous runs of consecutive tiles: tiles next to each other write
 // next to each other in every digit's output range, and their partial lines

@@ -78,11 +78,7 @@
 namespace psg {
 namespace {
 
-#ifndef PSG_LONG_RUN
-#define PSG_LONG_RUN 32  // A/B builds: 8, 256
-#endif
-constexpr uint32_t kLongGrid = 1024;             // workgroups (of 4 waves) over the long runs
-constexpr uint32_t kLongRun = PSG_LONG_RUN;      // runs longer than this go to the whole wave
+// kLongRun and kLongGrid: psg_sort.h
 
 struct KeptFlag {  // position i survives the dictionary
   const uint32_t* remapped;
@@ -765,6 +761,7 @@ int mb_load_begin(psg_minibatch* mb, size_t rows, size_t n, bool valued) {
   mb->state = S_NEW;
   mb->darling = false;
   mb->xw_own = false;
+  mb->rows_m = 0;
   mb->has_slots = mb->groups_ok = false;
   mb_drop_sharing(mb);
   const size_t ntiles = blocks_of(n, kSortTile);
@@ -919,6 +916,7 @@ int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
   mb->state = S_UNIQ;
   mb->darling = false;
   mb->xw_own = false;
+  mb->rows_m = 0;
   const uint32_t n = (uint32_t)mb->nnz, nu = (uint32_t)mb->n_uniq, nd = (uint32_t)ndict;
   const uint32_t rows = (uint32_t)mb->rows;
   uint32_t* before = mb->at<uint32_t>(B_BEFORE);

@@ -323,3 +323,102 @@ class FTRLModel:
         with open(path, "w") as f:
             for k, v in zip(keys.tolist(), w.tolist()):
                 f.write("%d\t%s\n" % (k, format_weight(v)))
+
+
+class FTRLMultiModel:
+    """m FTRL models over one key set, resident in HBM (``psg_ftrlm_*``): a
+    sweep of (alpha, beta, lambda1, lambda2) trained in one pass.
+
+    ``params``: a list of m dicts with the keys ``alpha``, ``beta``,
+    ``lambda1``, ``lambda2`` (1 <= m <= 32).  Row-valued arrays are
+    ``[n, m]``; column j is bit for bit what an ``FTRLModel`` with
+    ``params[j]`` gives for the same messages.  Checkpoints, the frozen form
+    and the C++ adapter are not built for it (include/psg.h)."""
+
+    def __init__(self, params, device: int = 0, capacity_hint: int = 0, flags: int = 0):
+        self._L = _lib.lib()
+        self.params = [{k: float(p[k]) for k in _STATE_PARAMS} for p in params]
+        self.m = len(self.params)
+        h = C.c_void_p()
+        _lib.check(self._L.psg_create(device, PSG_F64, flags, C.byref(h)))
+        self._h = h
+        arr = (_lib.FtrlParam * max(self.m, 1))(
+            *[_lib.FtrlParam(*(p[k] for k in _STATE_PARAMS)) for p in self.params])
+        rc = self._L.psg_ftrlm_init(h, arr, self.m, capacity_hint)
+        if rc != _lib.PSG_OK:
+            self.close()
+            _lib.check(rc)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psg_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _model(self):
+        return self._h
+
+    def reserve(self, entries: int) -> None:
+        _lib.check(self._L.psg_ftrlm_reserve(self._h, entries))
+
+    def push(self, keys, pos, neg, grad) -> None:
+        """setValue for all m models: ``grad`` is ``[n, m]``."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        pos = np.ascontiguousarray(pos, dtype=np.uint32)
+        neg = np.ascontiguousarray(neg, dtype=np.uint32)
+        grad = np.ascontiguousarray(grad, dtype=np.float64)
+        if pos.size != keys.size or neg.size != keys.size or grad.size != keys.size * self.m:
+            raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"values for {keys.size} keys x {self.m} models")
+        if keys.size:
+            _lib.check(self._L.psg_ftrlm_push(self._h, _ptr(keys), keys.size, _ptr(pos),
+                                              _ptr(neg), _ptr(grad)))
+
+    def pull(self, keys) -> np.ndarray:
+        """getValue: the ``[n, m]`` weights, +0.0 for a key never pushed."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        out = np.zeros((keys.size, self.m), np.float64)
+        if keys.size:
+            _lib.check(self._L.psg_ftrlm_pull(self._h, _ptr(keys), keys.size, _ptr(out)))
+        return out
+
+    def status(self):
+        """(entries, nnz[m], norm1[m], norm2[m]) of psg_ftrlm_status."""
+        e = C.c_size_t()
+        nnz = np.zeros(self.m, np.uintp)
+        n1, n2 = np.zeros(self.m, np.float64), np.zeros(self.m, np.float64)
+        _lib.check(self._L.psg_ftrlm_status(self._h, C.byref(e), _ptr(nnz), _ptr(n1), _ptr(n2)))
+        return e.value, nnz.astype(np.int64), n1, n2
+
+    def objv(self) -> np.ndarray:
+        _, _, n1, n2 = self.status()
+        return np.array([a * p["lambda1"] + .5 * p["lambda2"] * math.sqrt(b)
+                         for a, b, p in zip(n1, n2, self.params)])
+
+    def lookup(self, keys):
+        """Whole entries: pos[n], neg[n], w[n, m], z[n, m], found[n]."""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        pos, neg = np.zeros(k.size, np.uint64), np.zeros(k.size, np.uint64)
+        w, z = np.zeros((k.size, self.m), np.float64), np.zeros((k.size, self.m), np.float64)
+        found = np.zeros(k.size, np.uint8)
+        if k.size:
+            _lib.check(self._L.psg_ftrlm_lookup(self._h, _ptr(k), k.size, _ptr(pos), _ptr(neg),
+                                                _ptr(w), _ptr(z), _ptr(found)))
+        return pos, neg, w, z, found
+
+    def export(self, j: int):
+        """(keys, w) of model j's nonzero weights, sorted by key."""
+        n = C.c_size_t()
+        rc = self._L.psg_ftrlm_export(self._h, j, None, None, 0, C.byref(n))
+        if rc not in (_lib.PSG_OK, _lib.PSG_ERR_SIZE):
+            _lib.check(rc)
+        keys, w = np.empty(n.value, np.uint64), np.empty(n.value, np.float64)
+        if n.value:
+            _lib.check(self._L.psg_ftrlm_export(self._h, j, _ptr(keys), _ptr(w), n.value,
+                                                C.byref(n)))
+        order = np.argsort(keys, kind="stable")
+        return keys[order], w[order]

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _lib
 from .auc import exact_auc
-from .ftrl import FTRLModel, load_state
+from .ftrl import FTRLModel, FTRLMultiModel, load_state
 from .kv_vector import _ptr
 
 # psg_mb_read's arrays: name -> (id, dtype)
@@ -112,6 +112,7 @@ class Minibatch:
         self.stream = s.value  # the context's
         self.uniq_key_dev = self.key_cnt_dev = None
         self.pos_dev = self.neg_dev = self.grad_dev = None
+        self.grad_rows_dev, self.rows_m = None, 1
 
     def close(self):
         if getattr(self, "_h", None):
@@ -218,6 +219,38 @@ class Minibatch:
         self.grad_dev = g.value
         return objv.value
 
+    def times_rows(self, x_dev, m: int, xw_dev, stream=None) -> None:
+        """psg_mb_times_rows: xw[rows, m] = Z * x[ndict, m]."""
+        _lib.check(self._L.psg_mb_times_rows(self._h, x_dev, m, xw_dev, stream))
+
+    def trans_times_rows(self, c_dev, m: int, g_dev, stream=None) -> None:
+        """psg_mb_trans_times_rows: g[ndict, m] = Z' * c[rows, m]."""
+        _lib.check(self._L.psg_mb_trans_times_rows(self._h, c_dev, m, g_dev, stream))
+
+    def gradient_rows(self, w_dev, m: int, loss: int = _lib.PSG_LOSS_LOGIT,
+                      stream=None) -> np.ndarray:
+        """psg_mb_gradient_rows for w[ndict, m]: objv[m]; the device gradient
+        [ndict, m] is grad_rows_dev."""
+        g, objv = C.c_void_p(), np.zeros(m, np.float64)
+        _lib.check(self._L.psg_mb_gradient_rows(self._h, loss, w_dev, m, C.byref(g), _ptr(objv),
+                                                stream))
+        self.grad_rows_dev, self.rows_m = g.value, m
+        return objv
+
+    def read_rows(self, name: str) -> np.ndarray:
+        """A host copy of one array of the last gradient_rows: "xw", "tau",
+        "loss" ([rows, m]) or "grad" ([ndict, m])."""
+        what = {"xw": _lib.PSG_MB_ROWS_XW, "tau": _lib.PSG_MB_ROWS_TAU,
+                "loss": _lib.PSG_MB_ROWS_LOSS, "grad": _lib.PSG_MB_ROWS_GRAD}[name]
+        n = C.c_size_t()
+        rc = self._L.psg_mb_rows_read(self._h, what, None, 0, C.byref(n))
+        if rc not in (_lib.PSG_OK, _lib.PSG_ERR_SIZE):
+            _lib.check(rc)
+        out = np.empty(n.value, np.float64)
+        if n.value:
+            _lib.check(self._L.psg_mb_rows_read(self._h, what, _ptr(out), out.nbytes, C.byref(n)))
+        return out.reshape(-1, self.rows_m)
+
     def scratch(self, slot: int, nbytes: int) -> int:
         """A device block of the minibatch's (psg_mb_scratch)."""
         p = C.c_void_p()
@@ -255,15 +288,42 @@ class Minibatch:
         return a[:count].view(dtype)
 
 
-class FTRLWorker:
+class _TailFilteredWorker:
+    """What ``FTRLWorker`` and ``FTRLMultiWorker`` share: the minibatch's
+    scratch slots and the dictionary of a step, its unique keys passed through
+    the tail filter (ftrl.cc:96-106)."""
+
+    _DICT, _W, _FILTER, _WORD = 0, 1, 2, 3  # scratch slots
+
+    def _dictionary(self):
+        """(keys_dev, ndict) of the loaded minibatch, on its stream."""
+        L, mb = self._L, self.mb
+        n = mb.uniq()                                                      # ftrl.cc:96
+        if not (self.freq > 0 and n):
+            return mb.uniq_key_dev, n
+        keys = mb.scratch(self._DICT, 8 * n)                               # :99-106
+        word = mb.scratch(self._WORD, 8)
+        fs = mb.scratch(self._FILTER, L.psg_freq_query_scratch_bytes(n))
+        _lib.check(L.psg_freq_insert_dev(self._ctx, self.chl, mb.uniq_key_dev, mb.key_cnt_dev, n,
+                                         mb.stream))
+        _lib.check(L.psg_freq_query_dev(self._ctx, self.chl, mb.uniq_key_dev, n, self.freq, keys,
+                                        word, fs, mb.stream))
+        return keys, int(mb.read_scratch(self._WORD, np.uint64, 1)[0])
+
+    def last_dict(self) -> np.ndarray:
+        """The dictionary of the last step, for tests and checkpoints."""
+        if self.freq > 0 and self.mb.n_uniq:
+            return self.mb.read_scratch(self._DICT, np.uint64, self.ndict).copy()
+        return self.mb.read("uniq_key")
+
+
+class FTRLWorker(_TailFilteredWorker):
     """The worker of the online solver (ftrl.cc:88-151) for one model.
 
     ``tail_feature_freq`` > 0 turns the tail filter on: a minibatch's keys
     are inserted with their counts and only those whose estimate exceeds it
     are kept (shared_parameter.h:114-133), in a CountMin of ``countmin_n``
     counters and ``countmin_k`` probes on channel ``chl`` of the context."""
-
-    _DICT, _W, _FILTER, _WORD = 0, 1, 2, 3  # scratch slots
 
     def __init__(self, model: FTRLModel, tail_feature_freq: int = 0, countmin_n: int = 1 << 20,
                  countmin_k: int = 2, chl: int = 0):
@@ -333,18 +393,7 @@ class FTRLWorker:
     def _step_loaded(self, auc=None) -> Tuple[float, int]:
         L, mb = self._L, self.mb
         st = mb.stream  # every enqueue of the step, in order
-        n = mb.uniq()                                                      # ftrl.cc:96
-        if self.freq > 0 and n:                                            # :99-106
-            keys = mb.scratch(self._DICT, 8 * n)
-            word = mb.scratch(self._WORD, 8)
-            fs = mb.scratch(self._FILTER, L.psg_freq_query_scratch_bytes(n))
-            _lib.check(L.psg_freq_insert_dev(self._ctx, self.chl, mb.uniq_key_dev,
-                                             mb.key_cnt_dev, n, st))
-            _lib.check(L.psg_freq_query_dev(self._ctx, self.chl, mb.uniq_key_dev, n, self.freq,
-                                            keys, word, fs, st))
-            ndict = int(mb.read_scratch(self._WORD, np.uint64, 1)[0])
-        else:
-            keys, ndict = mb.uniq_key_dev, n
+        keys, ndict = self._dictionary()                                   # ftrl.cc:96-106
         w = mb.scratch(self._W, 8 * ndict)
         _lib.check(L.psg_ftrl_pull_dev(self._ctx, keys, ndict, w, st))   # :108-111
         mb.localize(keys, ndict)                                           # :113-119
@@ -360,11 +409,6 @@ class FTRLWorker:
         return objv, mb.rows
 
     # -- what the last step used, for tests and checkpoints ------------------
-    def last_dict(self) -> np.ndarray:
-        if self.freq > 0 and self.mb.n_uniq:
-            return self.mb.read_scratch(self._DICT, np.uint64, self.ndict).copy()
-        return self.mb.read("uniq_key")
-
     def last_w(self) -> np.ndarray:
         return self.mb.read_scratch(self._W, np.float64, self.ndict).copy()
 
@@ -406,6 +450,84 @@ class FTRLWorker:
         wk.objv = float(st["objv"])
         wk.num_ex = int(st["num_ex"])
         return wk
+
+
+class FTRLMultiWorker(_TailFilteredWorker):
+    """``FTRLWorker`` for the m models of an ``FTRLMultiModel``: one unique,
+    one filter insert and query, one localize and one countKeys per minibatch,
+    then the three row calls (``psg_mb_gradient_rows``) and one row-valued
+    push.  ``step`` returns (objv[m], examples); column j is bit for bit what
+    an ``FTRLWorker`` on an ``FTRLModel`` with ``params[j]`` gives.
+
+    The ``auc=`` hook of ``FTRLWorker.step`` is not offered: the AUC takes a
+    dense Xw[rows], and Xw here is [rows, m]."""
+
+    def __init__(self, model: FTRLMultiModel, tail_feature_freq: int = 0,
+                 countmin_n: int = 1 << 20, countmin_k: int = 2, chl: int = 0):
+        self._L = _lib.lib()
+        self.model, self.m = model, model.m
+        self._ctx = model._model()
+        self.freq = int(tail_feature_freq)
+        self.chl = chl
+        if self.freq > 0:
+            _lib.check(self._L.psg_freq_resize(self._ctx, chl, countmin_n, countmin_k))
+        self.mb = Minibatch(self._ctx)
+        self.objv = np.zeros(self.m, np.float64)  # status_.objv per model
+        self.num_ex = 0
+        self.ndict = 0
+
+    def close(self):
+        self.mb.close()
+
+    def _pull(self, insert: bool):
+        mb = self.mb
+        if insert:
+            keys, ndict = self._dictionary()
+        else:
+            ndict = mb.uniq()
+            keys = mb.uniq_key_dev
+        w = mb.scratch(self._W, 8 * ndict * self.m)
+        _lib.check(self._L.psg_ftrlm_pull_dev(self._ctx, keys, ndict, w, mb.stream))
+        mb.localize(keys, ndict)
+        self.ndict = ndict
+        return keys, w
+
+    def _step_loaded(self) -> Tuple[np.ndarray, int]:
+        mb = self.mb
+        keys, w = self._pull(True)                                         # ftrl.cc:96-119
+        objv = mb.gradient_rows(w, self.m)                                 # :128-138
+        _lib.check(self._L.psg_ftrlm_push_dev(self._ctx, keys, self.ndict, mb.pos_dev,
+                                              mb.neg_dev, mb.grad_rows_dev, mb.stream))
+        self.objv += objv
+        self.num_ex += mb.rows
+        return objv, mb.rows
+
+    def step(self, offset, index, value, y) -> Tuple[np.ndarray, int]:
+        self.mb.load(offset, index, value, y)
+        return self._step_loaded()
+
+    def step_text(self, text: bytes, fmt, max_rows=None, final: bool = True):
+        """(objv[m], examples, bytes consumed), as ``FTRLWorker.step_text``."""
+        r = self.mb.load_text(text, fmt, max_rows, final)
+        objv, rows = self._step_loaded()
+        return objv, rows, int(r.consumed)
+
+    def _predict_loaded(self) -> np.ndarray:
+        mb = self.mb
+        _, w = self._pull(False)
+        xw = mb.scratch(self._FILTER, 8 * max(mb.rows, 1) * self.m)
+        mb.times_rows(w, self.m, xw)
+        return mb.read_scratch(self._FILTER, np.float64, mb.rows * self.m).reshape(-1, self.m).copy()
+
+    def predict(self, offset, index, value, y) -> np.ndarray:
+        """Xw[rows, m] of one minibatch against the models as they are: no
+        filter insert, no push."""
+        self.mb.load(offset, index, value, y)
+        return self._predict_loaded()
+
+    def predict_text(self, text: bytes, fmt, max_rows=None, final: bool = True):
+        r = self.mb.load_text(text, fmt, max_rows, final)
+        return self._predict_loaded(), int(r.consumed)
 
 
 def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device: int = 0,
