@@ -919,6 +919,11 @@ int psg_mb_trans_times_rows(psg_minibatch* mb, const double* c_dev, int m, doubl
                             void* stream);
 int psg_mb_gradient_rows(psg_minibatch* mb, int loss, const double* w_dev, int m,
                          const double** grad_dev, double* objv, void* stream);
+/* psg_mb_labels for the row calls: the label array and Xw[rows * m] of the
+ * last psg_mb_gradient_rows with its m, valid until the next psg_mb_load
+ * (what psg_auc_rows_add_dev takes); PSG_ERR_ARG when none has run since the
+ * last psg_mb_localize. */
+int psg_mb_rows_labels(psg_minibatch* mb, const double** y_dev, const double** xw_dev, int* m);
 /* Tests: one row-valued array of the last psg_mb_gradient_rows to the host,
  * as psg_mb_read; PSG_ERR_ARG when no psg_mb_gradient_rows has run since the
  * last psg_mb_localize. */
@@ -1469,6 +1474,44 @@ int psg_auc_evaluate_data(const int64_t* tp_key, const uint64_t* tp_count, size_
 /* psg_auc_data, then the function above.  Synchronise. */
 int psg_auc_accuracy(psg_auc* h, double threshold, double* v);
 int psg_auc_evaluate(psg_auc* h, int mode, double* v);
+
+/* A psg_auc_rows is m such histograms, 1 <= m <= PSG_FTRL_MAX_MODELS, of one
+ * goodness: one for each model of a sweep (psg_ftrlm_*, psg_mb_gradient_rows).
+ * They are one table resident in HBM, ordered by (model, key), that one sort,
+ * one run pass and one union per add update together.  predict is double
+ * [n * m] row-major, model j of example i at [i * m + j] (the layout
+ * psg_mb_times_rows and psg_mb_gradient_rows write); y is double[n], shared by
+ * the models.
+ * The contract: for every j, after any sequence of adds, merges and clears,
+ * psg_auc_rows_data(h, j) is byte for byte what psg_auc_data gives for a
+ * psg_auc of the same goodness that was fed column j alone through the same
+ * sequence; accuracy and evaluate of model j are the scalar handle's bits.
+ * Everything said of a psg_auc above holds, its defined deviations included,
+ * with these differences: the host's bound of the distinct keys counts all
+ * models (an add raises it by n * m); n * m >= 2^32 - 1 is PSG_ERR_SIZE (the
+ * payload of the shared sort is uint32); a batch whose keys span too many bits
+ * to sort with the model id beside them (a key of INT64_MIN next to ordinary
+ * keys, or a large goodness) is added model by model, which waits m + 1 times
+ * where an add otherwise waits once; m out of range and j out of range are
+ * PSG_ERR_ARG. */
+typedef struct psg_auc_rows psg_auc_rows;
+int psg_auc_rows_create(psg_ctx* ctx, int64_t goodness, int m, psg_auc_rows** h);
+void psg_auc_rows_destroy(psg_auc_rows* h);
+int psg_auc_rows_clear(psg_auc_rows* h);
+int psg_auc_rows_set_goodness(psg_auc_rows* h, int64_t goodness);
+int psg_auc_rows_add_dev(psg_auc_rows* h, const double* y_dev, const double* predict_dev, size_t n,
+                         void* stream);
+int psg_auc_rows_add(psg_auc_rows* h, const double* y, const double* predict, size_t n);
+/* psg_auc_merge into model j's histogram. */
+int psg_auc_rows_merge(psg_auc_rows* h, int j, const int64_t* tp_key, const uint64_t* tp_count,
+                       size_t ntp, const int64_t* fp_key, const uint64_t* fp_count, size_t nfp);
+/* psg_auc_data of model j. */
+int psg_auc_rows_data(psg_auc_rows* h, int j, int64_t* tp_key, uint64_t* tp_count, size_t tp_cap,
+                      size_t* ntp, int64_t* fp_key, uint64_t* fp_count, size_t fp_cap, size_t* nfp);
+/* v[m]: psg_auc_rows_data of each model, then psg_auc_accuracy_data /
+ * psg_auc_evaluate_data.  Synchronise. */
+int psg_auc_rows_accuracy(psg_auc_rows* h, double threshold, double* v);
+int psg_auc_rows_evaluate(psg_auc_rows* h, int mode, double* v);
 /* Evaluation<double>::auc (evaluation.h:17-44) on device arrays: a stable sort
  * by prediction, A = the sum over the negatives (y <= 0 or NaN) of the
  * positives sorted before them, in uint64 (exact), then area = (double)A /

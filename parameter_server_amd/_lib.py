@@ -368,6 +368,17 @@ SIGNATURES = {
     "psg_auc_evaluate": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
     "psg_auc_exact_dev": (C.c_int, [_p, _p, _p, _sz, C.POINTER(C.c_double), _p]),
     "psg_auc_exact": (C.c_int, [_p, _p, _p, _sz, C.POINTER(C.c_double)]),
+    "psg_mb_rows_labels": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(C.c_int)]),
+    "psg_auc_rows_create": (C.c_int, [_p, C.c_int64, C.c_int, C.POINTER(_p)]),
+    "psg_auc_rows_destroy": (None, [_p]),
+    "psg_auc_rows_clear": (C.c_int, [_p]),
+    "psg_auc_rows_set_goodness": (C.c_int, [_p, C.c_int64]),
+    "psg_auc_rows_add_dev": (C.c_int, [_p, _p, _p, _sz, _p]),
+    "psg_auc_rows_add": (C.c_int, [_p, _p, _p, _sz]),
+    "psg_auc_rows_merge": (C.c_int, [_p, C.c_int, _p, _p, _sz, _p, _p, _sz]),
+    "psg_auc_rows_data": (C.c_int, [_p, C.c_int, _p, _p, _sz, _psz, _p, _p, _sz, _psz]),
+    "psg_auc_rows_accuracy": (C.c_int, [_p, C.c_double, _p]),
+    "psg_auc_rows_evaluate": (C.c_int, [_p, C.c_int, _p]),
 }
 
 _LIB = None

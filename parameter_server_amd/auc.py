@@ -122,6 +122,83 @@ class AUC:
         _lib.check(self._L.psg_auc_clear(self._h))
 
 
+class AUCRows:
+    """``m`` such histograms of one goodness, one per model of a sweep
+    (``FTRLMultiModel``), as one table on the device that one sort and one
+    union per ``add`` update together (``psg_auc_rows_*``).  Model ``j`` is
+    bit for bit an ``AUC`` fed column ``j`` alone."""
+
+    def __init__(self, ctx, m: int, goodness: int = 100000):
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        _lib.check(self._L.psg_auc_rows_create(ctx, goodness, m, C.byref(h)))
+        self._h = h
+        self.m = int(m)
+        self.goodness = int(goodness)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.psg_auc_rows_destroy(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def setGoodness(self, goodness: int) -> None:
+        _lib.check(self._L.psg_auc_rows_set_goodness(self._h, goodness))
+        self.goodness = int(goodness)
+
+    def add(self, y, predict) -> None:
+        """compute + merge of host arrays y[n], predict[n, m] (psg_auc_rows_add)."""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        predict = np.ascontiguousarray(predict, dtype=np.float64)
+        if predict.size != y.size * self.m:
+            raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"{y.size} labels, {predict.size} predictions "
+                                f"of {self.m} models")
+        _lib.check(self._L.psg_auc_rows_add(self._h, _ptr(y), _ptr(predict), y.size))
+
+    def add_dev(self, y_dev, predict_dev, n: int, stream=None) -> None:
+        """The same with device pointers (psg_auc_rows_add_dev)."""
+        _lib.check(self._L.psg_auc_rows_add_dev(self._h, y_dev, predict_dev, n, stream))
+
+    def merge(self, j: int, tp_key, tp_count, fp_key, fp_count) -> None:
+        """merge(AUCData) into model j's histogram (psg_auc_rows_merge)."""
+        tk, tc, fk, fc = _lists(tp_key, tp_count, fp_key, fp_count)
+        _lib.check(self._L.psg_auc_rows_merge(self._h, j, _ptr(tk), _ptr(tc), tk.size, _ptr(fk),
+                                              _ptr(fc), fk.size))
+
+    def data(self, j: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Model j's (tp_key, tp_count, fp_key, fp_count), as ``AUC.data``."""
+        nt, nf = C.c_size_t(), C.c_size_t()
+        rc = self._L.psg_auc_rows_data(self._h, j, None, None, 0, C.byref(nt), None, None, 0,
+                                       C.byref(nf))
+        if rc not in (_lib.PSG_OK, _lib.PSG_ERR_SIZE):
+            _lib.check(rc)
+        tk, tc = np.empty(nt.value, np.int64), np.empty(nt.value, np.uint64)
+        fk, fc = np.empty(nf.value, np.int64), np.empty(nf.value, np.uint64)
+        if nt.value or nf.value:
+            _lib.check(self._L.psg_auc_rows_data(self._h, j, _ptr(tk), _ptr(tc), tk.size,
+                                                 C.byref(nt), _ptr(fk), _ptr(fc), fk.size,
+                                                 C.byref(nf)))
+        return tk, tc, fk, fc
+
+    def accuracy(self, threshold: float = 0) -> np.ndarray:
+        """accuracy[m]: ``accuracy_data`` over each model's export."""
+        return np.array([accuracy_data(self.goodness, *self.data(j), threshold=threshold)
+                         for j in range(self.m)], np.float64)
+
+    def evaluate(self, as_written: bool = False) -> np.ndarray:
+        """evaluate[m]: ``evaluate_data`` over each model's export."""
+        return np.array([evaluate_data(*self.data(j), as_written=as_written)
+                         for j in range(self.m)], np.float64)
+
+    def clear(self) -> None:
+        _lib.check(self._L.psg_auc_rows_clear(self._h))
+
+
 def exact_auc(ctx, y, predict) -> float:
     """Evaluation<double>::auc of host arrays (psg_auc_exact)."""
     y = np.ascontiguousarray(y, dtype=np.float64)

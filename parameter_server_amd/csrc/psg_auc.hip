@@ -26,7 +26,8 @@
 // weight.  No float is summed anywhere on the device.  The radix passes and
 // their shape, the count / scan / emit, the binary search and the ballot fold
 // are psg_sort.h's, which psg_worker.hip includes too; the handle's blocks
-// are psg_blocks.h's.
+// are psg_blocks.h's; the key of a prediction and the span's fold are
+// psg_auc_dev.h's, which psg_auc_rows.hip includes too.
 //
 // The exact AUC: an order-preserving key of the prediction's bits (-0.0 and
 // +0.0 share one), the same sort, an exclusive scan of the "positive" flag in
@@ -41,36 +42,13 @@
 #include <vector>
 
 #include "../../include/psg.h"
+#include "psg_auc_dev.h"
 #include "psg_blocks.h"
 #include "psg_host.h"
 #include "psg_sort.h"
 
 namespace psg {
 namespace {
-
-constexpr uint64_t kSignBit = 1ull << 63;
-constexpr uint32_t kGridCap = 2048;  // workgroups of a grid-stride launch
-
-// auc.h:75 on x86-64: a NaN product or one of magnitude >= 2^63 converts to
-// INT64_MIN there (the device's own conversion saturates)
-__device__ __forceinline__ uint64_t biased_key(double predict, double goodness) {
-  const double p = predict * goodness;
-  const long long k = fabs(p) < 9223372036854775808.0 ? (long long)p : (long long)kSignBit;
-  return (uint64_t)k ^ kSignBit;
-}
-
-__device__ __forceinline__ void fold_min_max(uint64_t lo, uint64_t hi,
-                                             unsigned long long* __restrict__ minmax) {
-  for (int s = 32; s >= 1; s >>= 1) {
-    const uint64_t a = __shfl_xor(lo, s, 64), b = __shfl_xor(hi, s, 64);
-    lo = a < lo ? a : lo;
-    hi = b > hi ? b : hi;
-  }
-  if ((threadIdx.x & 63u) == 0) {
-    atomicMin(minmax, (unsigned long long)lo);
-    atomicMax(minmax + 1, (unsigned long long)hi);
-  }
-}
 
 // ---- (a) ------------------------------------------------------------------
 // wkey null: examples; else the keys of weighted entries
@@ -247,14 +225,6 @@ __global__ __launch_bounds__(256) void sum_u32_kernel(const uint32_t* __restrict
     a += v[i];
   for (int s = 32; s >= 1; s >>= 1) a += __shfl_xor(a, s, 64);
   if ((threadIdx.x & 63u) == 0 && a) atomicAdd(total, (unsigned long long)a);
-}
-
-// every bit up to the highest one of `span`: the digits two keys within that
-// span of each other can differ in (after the smallest is subtracted)
-inline uint64_t bits_up_to(uint64_t span) {
-  uint64_t b = 0;
-  while (b < span) b = (b << 1) | 1u;
-  return b;
 }
 
 }  // namespace

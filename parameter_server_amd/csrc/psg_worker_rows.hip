@@ -387,6 +387,16 @@ int psg_mb_gradient_rows(psg_minibatch* mb, int loss, const double* w_dev, int m
   return PSG_OK;
 }
 
+int psg_mb_rows_labels(psg_minibatch* mb, const double** y_dev, const double** xw_dev, int* m) {
+  if (!mb) return fail(PSG_ERR_ARG, "null argument");
+  if (mb->state < S_LOCAL || mb->rows_m == 0)
+    return fail(PSG_ERR_ARG, "psg_mb_rows_labels before psg_mb_gradient_rows");
+  if (y_dev) *y_dev = mb->at<double>(B_Y);
+  if (xw_dev) *xw_dev = mb->at<double>(B_R_XW);
+  if (m) *m = mb->rows_m;
+  return PSG_OK;
+}
+
 int psg_mb_rows_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t* n_out) {
   if (!mb || !n_out) return fail(PSG_ERR_ARG, "null argument");
   *n_out = 0;

@@ -237,6 +237,13 @@ class Minibatch:
         self.grad_rows_dev, self.rows_m = g.value, m
         return objv
 
+    def rows_labels(self) -> Tuple[int, int]:
+        """psg_mb_rows_labels: the device pointers of y and of Xw[rows, m] of
+        the last gradient_rows."""
+        y, xw, m = C.c_void_p(), C.c_void_p(), C.c_int()
+        _lib.check(self._L.psg_mb_rows_labels(self._h, C.byref(y), C.byref(xw), C.byref(m)))
+        return y.value, xw.value
+
     def read_rows(self, name: str) -> np.ndarray:
         """A host copy of one array of the last gradient_rows: "xw", "tau",
         "loss" ([rows, m]) or "grad" ([ndict, m])."""
@@ -459,8 +466,11 @@ class FTRLMultiWorker(_TailFilteredWorker):
     push.  ``step`` returns (objv[m], examples); column j is bit for bit what
     an ``FTRLWorker`` on an ``FTRLModel`` with ``params[j]`` gives.
 
-    The ``auc=`` hook of ``FTRLWorker.step`` is not offered: the AUC takes a
-    dense Xw[rows], and Xw here is [rows, m]."""
+    ``step(..., auc=)`` takes an ``AUCRows`` of this context with the worker's
+    ``m``: it adds (y, Xw[rows, m]) of the minibatch after the gradient and
+    before the push, from the minibatch's own arrays on its stream, so model
+    j's histogram is the progressive-validation AUC that ``FTRLWorker.step``'s
+    hook keeps for one model."""
 
     def __init__(self, model: FTRLMultiModel, tail_feature_freq: int = 0,
                  countmin_n: int = 1 << 20, countmin_k: int = 2, chl: int = 0):
@@ -492,24 +502,29 @@ class FTRLMultiWorker(_TailFilteredWorker):
         self.ndict = ndict
         return keys, w
 
-    def _step_loaded(self) -> Tuple[np.ndarray, int]:
+    def _step_loaded(self, auc=None) -> Tuple[np.ndarray, int]:
         mb = self.mb
+        if auc is not None and auc.m != self.m:
+            raise ValueError(f"an AUCRows of {auc.m} models for a worker of {self.m}")
         keys, w = self._pull(True)                                         # ftrl.cc:96-119
         objv = mb.gradient_rows(w, self.m)                                 # :128-138
+        if auc is not None:  # Xw of weights that have not seen the minibatch
+            y_dev, xw_dev = mb.rows_labels()
+            auc.add_dev(y_dev, xw_dev, mb.rows, mb.stream)
         _lib.check(self._L.psg_ftrlm_push_dev(self._ctx, keys, self.ndict, mb.pos_dev,
                                               mb.neg_dev, mb.grad_rows_dev, mb.stream))
         self.objv += objv
         self.num_ex += mb.rows
         return objv, mb.rows
 
-    def step(self, offset, index, value, y) -> Tuple[np.ndarray, int]:
+    def step(self, offset, index, value, y, auc=None) -> Tuple[np.ndarray, int]:
         self.mb.load(offset, index, value, y)
-        return self._step_loaded()
+        return self._step_loaded(auc)
 
-    def step_text(self, text: bytes, fmt, max_rows=None, final: bool = True):
+    def step_text(self, text: bytes, fmt, max_rows=None, final: bool = True, auc=None):
         """(objv[m], examples, bytes consumed), as ``FTRLWorker.step_text``."""
         r = self.mb.load_text(text, fmt, max_rows, final)
-        objv, rows = self._step_loaded()
+        objv, rows = self._step_loaded(auc)
         return objv, rows, int(r.consumed)
 
     def _predict_loaded(self) -> np.ndarray:
