@@ -1526,6 +1526,25 @@ int psg_auc_rows_evaluate(psg_auc_rows* h, int mode, double* v);
 int psg_auc_exact_dev(psg_ctx* ctx, const double* y_dev, const double* predict_dev, size_t n,
                       double* auc, void* stream);
 int psg_auc_exact(psg_ctx* ctx, const double* y, const double* predict, size_t n, double* auc);
+/* The exact AUC of every model of a sweep in one call.
+ * auc[j], j < m: psg_auc_exact of (y, column j of predict[n * m], row-major:
+ * model j of example i at [i * m + j]), bit for bit.  1 <= m <= PSG_FTRL_MAX_MODELS.
+ * predict is the layout psg_mb_times_rows writes and psg_mb_rows_labels hands
+ * out: nothing is copied or de-interleaved by the caller.  One allocation, one
+ * key / transpose launch, one segmented radix sort whose launches cover all m
+ * models (a digit is skipped only if it is the same in every key of every
+ * model), one batched area pass, and two host waits whatever m is.
+ * Everything said of psg_auc_exact_dev holds column by column (ties keep their
+ * example order, -0.0 equals +0.0, one class absent or n == 0 gives NaN in
+ * every auc[j]), with these differences: a NaN prediction in any column is
+ * PSG_ERR_ARG, the message names the first such column and its NaN count and
+ * auc is left unwritten; m out of range is PSG_ERR_ARG; n * m >= 2^32 - 1 is
+ * PSG_ERR_SIZE.  auc[m] is a host array.  Synchronises. */
+int psg_auc_exact_rows_dev(psg_ctx* ctx, const double* y_dev, const double* predict_dev,
+                           size_t n, int m, double* auc /* host, m */, void* stream);
+int psg_auc_exact_rows(psg_ctx* ctx, const double* y, const double* predict,
+                       size_t n, int m, double* auc);
+size_t psg_auc_exact_rows_tile(void);  /* rows per transpose tile; tests size around it */
 
 /* ------------------------------------------------------------------ */
 /* Wire ingress: key signatures of the key cache                       */

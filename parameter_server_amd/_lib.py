@@ -368,6 +368,9 @@ SIGNATURES = {
     "psg_auc_evaluate": (C.c_int, [_p, C.c_int, C.POINTER(C.c_double)]),
     "psg_auc_exact_dev": (C.c_int, [_p, _p, _p, _sz, C.POINTER(C.c_double), _p]),
     "psg_auc_exact": (C.c_int, [_p, _p, _p, _sz, C.POINTER(C.c_double)]),
+    "psg_auc_exact_rows_dev": (C.c_int, [_p, _p, _p, _sz, C.c_int, _p, _p]),
+    "psg_auc_exact_rows": (C.c_int, [_p, _p, _p, _sz, C.c_int, _p]),
+    "psg_auc_exact_rows_tile": (_sz, []),
     "psg_mb_rows_labels": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(C.c_int)]),
     "psg_auc_rows_create": (C.c_int, [_p, C.c_int64, C.c_int, C.POINTER(_p)]),
     "psg_auc_rows_destroy": (None, [_p]),

@@ -8,7 +8,8 @@ defined deviations; the one a caller meets first: ``evaluate`` walks the
 positives by KEY by default, where auc.h:49 compares their counts, and
 ``as_written=True`` gives the reference's own number).
 
-``exact_auc`` is ``Evaluation<double>::auc`` (src/base/evaluation.h:17-44).
+``exact_auc`` is ``Evaluation<double>::auc`` (src/base/evaluation.h:17-44);
+``exact_auc_rows`` is that for every column of predict[n, m] in one call.
 """
 from __future__ import annotations
 
@@ -215,3 +216,25 @@ def exact_auc_dev(ctx, y_dev, predict_dev, n: int, stream=None) -> float:
     v = C.c_double()
     _lib.check(_lib.lib().psg_auc_exact_dev(ctx, y_dev, predict_dev, n, C.byref(v), stream))
     return v.value
+
+
+def exact_auc_rows(ctx, y, predict) -> np.ndarray:
+    """auc[m]: ``exact_auc`` of every column of the host array predict[n, m]
+    (the m models of a sweep) in one call (psg_auc_exact_rows)."""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    predict = np.ascontiguousarray(predict, dtype=np.float64)
+    if predict.ndim != 2:
+        raise ValueError(f"predict of shape {predict.shape}: (n, m) is wanted")
+    n, m = predict.shape
+    if y.size != n:
+        raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"{y.size} labels, {n} rows of predictions")
+    out = np.empty(max(m, 0), np.float64)
+    _lib.check(_lib.lib().psg_auc_exact_rows(ctx, _ptr(y), _ptr(predict), n, m, _ptr(out)))
+    return out
+
+
+def exact_auc_rows_dev(ctx, y_dev, predict_dev, n: int, m: int, stream=None) -> np.ndarray:
+    """The same with device pointers (psg_auc_exact_rows_dev)."""
+    out = np.empty(max(m, 0), np.float64)
+    _lib.check(_lib.lib().psg_auc_exact_rows_dev(ctx, y_dev, predict_dev, n, m, _ptr(out), stream))
+    return out

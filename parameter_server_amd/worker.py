@@ -21,7 +21,7 @@ from typing import Tuple
 import numpy as np
 
 from . import _lib
-from .auc import exact_auc
+from .auc import exact_auc, exact_auc_rows_dev
 from .ftrl import FTRLModel, FTRLMultiModel, load_state
 from .kv_vector import _ptr
 
@@ -543,6 +543,18 @@ class FTRLMultiWorker(_TailFilteredWorker):
     def predict_text(self, text: bytes, fmt, max_rows=None, final: bool = True):
         r = self.mb.load_text(text, fmt, max_rows, final)
         return self._predict_loaded(), int(r.consumed)
+
+    def exact_auc(self, offset, index, value, y) -> np.ndarray:
+        """auc[m]: the exact rank AUC of every model on one minibatch, scored
+        as ``predict`` scores it (no filter insert, no push).  The minibatch's
+        device labels and Xw[rows, m] go straight to psg_auc_exact_rows_dev on
+        its stream: no prediction comes to the host."""
+        mb = self.mb
+        mb.load(offset, index, value, y)
+        _, w = self._pull(False)
+        xw = mb.scratch(self._FILTER, 8 * max(mb.rows, 1) * self.m)
+        mb.times_rows(w, self.m, xw)
+        return exact_auc_rows_dev(self._ctx, mb.labels()[0], xw, mb.rows, self.m, mb.stream)
 
 
 def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device: int = 0,
