@@ -793,13 +793,11 @@ int psg_ftrl_frozen(psg_ctx* ctx, int* frozen);
  *    from run to run of the same messages; entries and every nnz[j] are exact;
  *  - a pushed message must be strictly increasing; one that is not is
  *    rejected whole by a device check that runs ahead of the update, reported
- *    once as PSG_ERR_UNSORTED by the next psg_ftrlm_pull, psg_ftrlm_status or
- *    psg_ftrlm_export, and then cleared; later messages apply normally.
- *    psg_ftrlm_lookup neither reports nor clears it;
+ *    once as PSG_ERR_UNSORTED by the next psg_ftrlm_pull, psg_ftrlm_status,
+ *    psg_ftrlm_export or psg_ftrlm_export_state, and then cleared; later
+ *    messages apply normally.  psg_ftrlm_lookup neither reports nor clears it;
  *  - psg_ftrlm_export's order is unspecified; the Python mirror sorts by key.
- * Not built for the multi-model: checkpoint and whole-state export
- * (psg_ftrl_import / psg_ftrl_export_state), the frozen weights-only form,
- * and the C++ adapter. */
+ * Not built for the multi-model: the C++ adapter. */
 #define PSG_FTRL_MAX_MODELS 32
 /* A fresh, empty multi-model of p[m], sized for capacity_hint keys (0: a
  * default; the table grows: the index is rebuilt, the rows are copied).
@@ -831,6 +829,69 @@ int psg_ftrlm_lookup(psg_ctx* ctx, const uint64_t* keys, size_t n, uint64_t* pos
  * key whose model-j weight is nonzero, order unspecified.  *n = their count;
  * PSG_ERR_SIZE (nothing copied) if that exceeds cap. */
 int psg_ftrlm_export(psg_ctx* ctx, int j, uint64_t* keys, double* w, size_t cap, size_t* n);
+/* Checkpoint and restore of the sweep, as psg_ftrl_import /
+ * psg_ftrl_export_state are for one model; an entry is a key's shared counts
+ * and its two rows: {pos, neg, w[m], z[m]}.
+ *
+ * psg_ftrlm_import: an upsert of n whole entries keys[n], pos[n], neg[n],
+ * w[n * m], z[n * m].  All five arrays are required: a NULL one is
+ * PSG_ERR_ARG.  A key already present has its counts and both rows replaced
+ * (the last one wins), an absent one is inserted.  Every bit is stored as
+ * given (-0.0, NaN payloads, counts past 2^32); entries and every nnz[j] stay
+ * exact (nnz by ftrl_model.h:106-110's comparisons: -0.0 is zero, a NaN weight
+ * is not).  Host arrays, free on return; asynchronous on the context's stream
+ * and in the model's call order, like psg_ftrlm_push; the table grows when n
+ * needs it.
+ * Defined deviations, the scalar model's:
+ *  - sorted import only: the message must be strictly increasing, and one
+ *    that is not applies nothing and is reported once as PSG_ERR_UNSORTED by
+ *    the next synchronising call, exactly as for a push;
+ *  - after a restore the model equals the saved one entry for entry, and
+ *    entries and nnz[j] are exact, but norm1[j] / norm2[j] of psg_ftrlm_status
+ *    are a reduction in row order: they agree with the saved model's within
+ *    the bound above (entries * 2^-53 * the sum), not bit for bit. */
+int psg_ftrlm_import(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint64_t* pos,
+                     const uint64_t* neg, const double* w, const double* z);
+/* The same with device arrays, enqueued on `stream`; allocates nothing and
+ * waits for nothing while the model has room (psg_ftrlm_reserve). */
+int psg_ftrlm_import_dev(psg_ctx* ctx, const uint64_t* keys, size_t n, const uint64_t* pos,
+                         const uint64_t* neg, const double* w, const double* z, void* stream);
+/* The weights-only import, by column: the load of model j's `key w` files
+ * (model_evaluation.h:16-27).  By column and not by row because the m files of
+ * a saved sweep hold different key sets (writeToFile keeps nonzero weights
+ * only).  w[row][j] of every key is set; the other columns, z and the counts
+ * of a key already present stay, and a fresh key's are (0, 0, +0.0 ..., +0.0
+ * ...).  Order check, growth and the entries / nnz[j] accounting are
+ * psg_ftrlm_import's.  j outside [0, m) is PSG_ERR_ARG.  The call freezes the
+ * model (below; also one of n == 0, an empty model file). */
+int psg_ftrlm_import_weights(psg_ctx* ctx, int j, const uint64_t* keys, size_t n,
+                             const double* w);
+int psg_ftrlm_import_weights_dev(psg_ctx* ctx, int j, const uint64_t* keys, size_t n,
+                                 const double* w, void* stream);
+/* Every key the model holds (rows whose weights are all +-0 and key 0's
+ * included) whose key lies in the closed interval range[0] <= key <= range[1]
+ * (NULL: every key; range[0] > range[1]: PSG_ERR_ARG), sorted by key on the
+ * device: keys[n], pos[n], neg[n], w[n * m], z[n * m].  The image of a given
+ * model is the same bytes on every run, whatever the index size, the slot
+ * order, the row numbering and the history of growth.  *n = the count;
+ * PSG_ERR_SIZE (nothing copied) if that exceeds cap, or for an index of
+ * 2^32 - 1 slots or more.  Any output array may be NULL.  Synchronises, and
+ * reports a rejected message as psg_ftrlm_status does. */
+int psg_ftrlm_export_state(psg_ctx* ctx, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                           uint64_t* neg, double* w, double* z, size_t cap, size_t* n);
+/* The same into device arrays of cap entries on `stream`; *n_dev (a device
+ * word) = the count.  The host waits once for that count (it shapes the
+ * sort's launches) and takes its work blocks from the context's pool. */
+int psg_ftrlm_export_state_dev(psg_ctx* ctx, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                               uint64_t* neg, double* w, double* z, size_t cap,
+                               unsigned long long* n_dev, void* stream);
+/* *frozen = 1 after psg_ftrlm_import_weights: the sweep is evaluation-only (z
+ * is unknown, and a push would recompute w from it).  psg_ftrlm_push and
+ * psg_ftrlm_push_dev then return PSG_ERR_ARG; pulls, status, lookups, exports
+ * and imports work.  The flag is host state, set by the weights-only call
+ * itself (also one whose message the device check then rejects).
+ * psg_ftrlm_init makes a fresh, unfrozen model. */
+int psg_ftrlm_frozen(psg_ctx* ctx, int* frozen);
 
 /* ------------------------------------------------------------------ */
 /* Online worker step: FTRL::updateModel's minibatch loop              */

@@ -303,6 +303,13 @@ SIGNATURES = {
     "psg_ftrlm_status": (C.c_int, [_p, _psz, _p, _p, _p]),
     "psg_ftrlm_lookup": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _p]),
     "psg_ftrlm_export": (C.c_int, [_p, C.c_int, _p, _p, _sz, _psz]),
+    "psg_ftrlm_import": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p]),
+    "psg_ftrlm_import_dev": (C.c_int, [_p, _p, _sz, _p, _p, _p, _p, _p]),
+    "psg_ftrlm_import_weights": (C.c_int, [_p, C.c_int, _p, _sz, _p]),
+    "psg_ftrlm_import_weights_dev": (C.c_int, [_p, C.c_int, _p, _sz, _p, _p]),
+    "psg_ftrlm_export_state": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _psz]),
+    "psg_ftrlm_export_state_dev": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "psg_ftrlm_frozen": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "psg_mb_create": (C.c_int, [_p, C.POINTER(_p)]),
     "psg_mb_destroy": (None, [_p]),
     "psg_mb_load": (C.c_int, [_p, _p, _sz, _p, _p, _p]),

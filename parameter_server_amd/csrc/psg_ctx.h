@@ -253,6 +253,8 @@ struct Ftrlm {
   double* d_z = nullptr;
   psg::FtrlmHead* d_head = nullptr;
   size_t bound = 0;  // as Ftrl::bound
+  // evaluation only, as Ftrl::frozen: set by psg_ftrlm_import_weights
+  bool frozen = false;
   hipEvent_t last = nullptr;
   hipStream_t last_s = nullptr;
   // at most half of the slots are taken; row 0 is key 0's

@@ -122,6 +122,71 @@ int ftrlm_report(psg_ctx* c, Ftrlm* F, unsigned long long rejected) {
               "increasing: those messages were not applied", rejected);
 }
 
+// a push into an evaluation-only model (psg_ftrlm_import_weights)
+int ftrlm_unfrozen(Ftrlm* F) {
+  if (F->frozen)
+    return fail(PSG_ERR_ARG, "the multi-model FTRL is frozen: it was loaded by a weights-only "
+                "import (evaluation only), z is unknown and a push would recompute w from it");
+  return PSG_OK;
+}
+
+// The pinned host words of a state export: OR, AND, count, err.  They are
+// psg_ctx_ftrl.hip's of the scalar export: either call reads them before it
+// returns, under the context's lock.
+constexpr int kStateWords = 20;
+
+// Step 1 of a state export on stream s: *blk (state_count_bytes) holds the
+// three device words and, from byte 64, the scan's tile sums; the host then
+// knows the count, the key bits that differ and the rejected messages.  Waits.
+size_t ftrlm_state_count_bytes(Ftrlm* F) { return 64 + 4 * psg::ftrlm_state_count_words(F->table()); }
+int ftrlm_state_count(psg_ctx* c, Ftrlm* F, uint64_t lo, uint64_t hi, hipStream_t s, char** blk,
+                size_t* n, uint64_t* differ, unsigned long long* rejected) {
+  if (int rc = ftrlm_order(F, s)) return rc;
+  if (int rc = c->dev_get(ftrlm_state_count_bytes(F), (void**)blk, s)) return rc;
+  unsigned long long* small = (unsigned long long*)*blk;
+  unsigned long long* h = c->h_small + kStateWords;
+  if (int rc = psg::launch_ftrlm_state_count(F->table(), lo, hi, (uint32_t*)(*blk + 64), small, s))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(h, small, 24, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h + 3, &F->d_head->err, 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n = (size_t)(h[2] & 0xffffffffull);
+  *differ = h[0] ^ h[1];
+  *rejected = h[3];
+  return PSG_OK;
+}
+
+// a block used on stream s goes back to the pool, whose release events are
+// recorded on the context's stream: that stream first waits for the model's
+// last event (recorded on s after the block's last use)
+void ftrlm_state_put(psg_ctx* c, Ftrlm* F, hipStream_t s, void* blk, size_t bytes) {
+  if (!blk) return;
+  if (s != c->stream && F->last) (void)hipStreamWaitEvent(c->stream, F->last, 0);
+  c->dev_put(blk, bytes);
+}
+
+// Step 2: the n entries of [lo, hi] sorted by key into device arrays.
+int ftrlm_state_emit(psg_ctx* c, Ftrlm* F, uint64_t lo, uint64_t hi, size_t n, uint64_t differ,
+               const char* count_blk, uint64_t* keys, uint64_t* pos, uint64_t* neg, double* w,
+               double* z, hipStream_t s) {
+  if (n == 0) return PSG_OK;
+  const size_t wb = psg::ftrlm_state_work_bytes(n);
+  void* work = nullptr;
+  if (int rc = c->dev_get(wb, &work, s)) return rc;
+  int rc = psg::launch_ftrlm_state(F->table(), lo, hi, n, differ,
+                                   (const uint32_t*)(count_blk + 64), work, keys, pos, neg, w, z, s);
+  const int rm = ftrlm_mark(c, F, s);
+  ftrlm_state_put(c, F, s, work, wb);
+  return rc ? rc : rm;
+}
+
+int ftrlm_state_range(const uint64_t* range, uint64_t* lo, uint64_t* hi) {
+  *lo = range ? range[0] : 0;
+  *hi = range ? range[1] : ~0ull;
+  if (*lo > *hi) return fail(PSG_ERR_ARG, "multi-model FTRL state export: range[0] > range[1]");
+  return PSG_OK;
+}
+
 }  // namespace
 
 int psg_ftrlm_init(psg_ctx* c, const psg_ftrl_param* p, int m, size_t capacity_hint) {
@@ -174,6 +239,7 @@ int psg_ftrlm_push_dev(psg_ctx* c, const uint64_t* keys, size_t n, const uint32_
   std::lock_guard<std::mutex> l(c->mu);
   Ftrlm* F;
   if (int rc = ftrlm_of(c, &F)) return rc;
+  if (int rc = ftrlm_unfrozen(F)) return rc;
   if (n == 0) return PSG_OK;
   if (int rc = set_dev(c->device)) return rc;
   if (int rc = ftrlm_room(c, F, n)) return rc;
@@ -188,6 +254,7 @@ int psg_ftrlm_push(psg_ctx* c, const uint64_t* keys, size_t n, const uint32_t* p
   std::lock_guard<std::mutex> l(c->mu);
   Ftrlm* F;
   if (int rc = ftrlm_of(c, &F)) return rc;
+  if (int rc = ftrlm_unfrozen(F)) return rc;
   if (n == 0) return PSG_OK;
   if (int rc = set_dev(c->device)) return rc;
   if (int rc = ftrlm_room(c, F, n)) return rc;
@@ -310,6 +377,191 @@ int psg_ftrlm_export(psg_ctx* c, int j, uint64_t* keys, double* w, size_t cap, s
     HIP_TRY(hipMemcpyAsync(w, d_w, 8 * need, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
   }
+  return ftrlm_report(c, F, rejected);
+}
+
+int psg_ftrlm_import_dev(psg_ctx* c, const uint64_t* keys, size_t n, const uint64_t* pos,
+                         const uint64_t* neg, const double* w, const double* z, void* stream) {
+  if (!c || !keys || !pos || !neg || !w || !z)
+    return fail(PSG_ERR_ARG, "multi-model FTRL import: keys, pos, neg, w and z are all required");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  if (n == 0) return PSG_OK;
+  if (int rc = set_dev(c->device)) return rc;
+  if (int rc = ftrlm_room(c, F, n)) return rc;
+  if (int rc = ftrlm_order(F, (hipStream_t)stream)) return rc;
+  HIP_TRY(psg::launch_ftrlm_import(F->table(), keys, pos, neg, w, z, n, (hipStream_t)stream));
+  return ftrlm_mark(c, F, (hipStream_t)stream);
+}
+
+int psg_ftrlm_import(psg_ctx* c, const uint64_t* keys, size_t n, const uint64_t* pos,
+                     const uint64_t* neg, const double* w, const double* z) {
+  if (!c || !keys || !pos || !neg || !w || !z)
+    return fail(PSG_ERR_ARG, "multi-model FTRL import: keys, pos, neg, w and z are all required");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  if (n == 0) return PSG_OK;
+  if (int rc = set_dev(c->device)) return rc;
+  if (int rc = ftrlm_room(c, F, n)) return rc;
+  // one staging block for the five arrays, back to the pool after the kernels
+  const size_t kb = align_up(8 * n, 256), rb = align_up(8 * n * F->m, 256), b = 3 * kb + 2 * rb;
+  char* blk = nullptr;
+  if (int rc = c->dev_get(b, (void**)&blk, c->copy)) return rc;
+  int rc = c->h2d(blk, keys, 8 * n);
+  if (rc == PSG_OK) rc = c->h2d(blk + kb, pos, 8 * n);
+  if (rc == PSG_OK) rc = c->h2d(blk + 2 * kb, neg, 8 * n);
+  if (rc == PSG_OK) rc = c->h2d(blk + 3 * kb, w, 8 * n * F->m);
+  if (rc == PSG_OK) rc = c->h2d(blk + 3 * kb + rb, z, 8 * n * F->m);
+  if (rc == PSG_OK) rc = c->join_copy();
+  if (rc == PSG_OK) rc = ftrlm_order(F, c->stream);
+  if (rc == PSG_OK) {
+    const hipError_t e = psg::launch_ftrlm_import(
+        F->table(), (const uint64_t*)blk, (const uint64_t*)(blk + kb),
+        (const uint64_t*)(blk + 2 * kb), (const double*)(blk + 3 * kb),
+        (const double*)(blk + 3 * kb + rb), n, c->stream);
+    if (e != hipSuccess) rc = fail(PSG_ERR_DEVICE, "ftrlm import: %s", hipGetErrorString(e));
+  }
+  if (rc == PSG_OK) rc = ftrlm_mark(c, F, c->stream);
+  c->dev_put(blk, b);
+  const int rf = c->h2d_finish();
+  return rc ? rc : rf;
+}
+
+int psg_ftrlm_import_weights_dev(psg_ctx* c, int j, const uint64_t* keys, size_t n,
+                                 const double* w, void* stream) {
+  if (!c || (n && (!keys || !w))) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  if (j < 0 || j >= F->m) return fail(PSG_ERR_ARG, "model %d of %d", j, F->m);
+  if (n == 0) {  // an empty model file still freezes
+    F->frozen = true;
+    return PSG_OK;
+  }
+  if (int rc = set_dev(c->device)) return rc;
+  if (int rc = ftrlm_room(c, F, n)) return rc;
+  if (int rc = ftrlm_order(F, (hipStream_t)stream)) return rc;
+  HIP_TRY(psg::launch_ftrlm_import_weights(F->table(), j, keys, w, n, (hipStream_t)stream));
+  F->frozen = true;
+  return ftrlm_mark(c, F, (hipStream_t)stream);
+}
+
+int psg_ftrlm_import_weights(psg_ctx* c, int j, const uint64_t* keys, size_t n, const double* w) {
+  if (!c || (n && (!keys || !w))) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  if (j < 0 || j >= F->m) return fail(PSG_ERR_ARG, "model %d of %d", j, F->m);
+  if (n == 0) {  // an empty model file still freezes
+    F->frozen = true;
+    return PSG_OK;
+  }
+  if (int rc = set_dev(c->device)) return rc;
+  if (int rc = ftrlm_room(c, F, n)) return rc;
+  const size_t kb = align_up(8 * n, 256), b = 2 * kb;
+  char* blk = nullptr;
+  if (int rc = c->dev_get(b, (void**)&blk, c->copy)) return rc;
+  int rc = c->h2d(blk, keys, 8 * n);
+  if (rc == PSG_OK) rc = c->h2d(blk + kb, w, 8 * n);
+  if (rc == PSG_OK) rc = c->join_copy();
+  if (rc == PSG_OK) rc = ftrlm_order(F, c->stream);
+  if (rc == PSG_OK) {
+    const hipError_t e = psg::launch_ftrlm_import_weights(
+        F->table(), j, (const uint64_t*)blk, (const double*)(blk + kb), n, c->stream);
+    if (e != hipSuccess) rc = fail(PSG_ERR_DEVICE, "ftrlm import: %s", hipGetErrorString(e));
+  }
+  if (rc == PSG_OK) F->frozen = true;
+  if (rc == PSG_OK) rc = ftrlm_mark(c, F, c->stream);
+  c->dev_put(blk, b);
+  const int rf = c->h2d_finish();
+  return rc ? rc : rf;
+}
+
+int psg_ftrlm_frozen(psg_ctx* c, int* frozen) {
+  if (!c || !frozen) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  *frozen = F->frozen ? 1 : 0;
+  return PSG_OK;
+}
+
+int psg_ftrlm_export_state_dev(psg_ctx* c, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                               uint64_t* neg, double* w, double* z, size_t cap,
+                               unsigned long long* n_dev, void* stream) {
+  if (!c || !n_dev) return fail(PSG_ERR_ARG, "null argument");
+  uint64_t lo, hi;
+  if (int rc = ftrlm_state_range(range, &lo, &hi)) return rc;
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  if (int rc = set_dev(c->device)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* cb = nullptr;
+  const size_t cbytes = ftrlm_state_count_bytes(F);
+  size_t n = 0;
+  uint64_t differ = 0;
+  unsigned long long rejected = 0;
+  int rc = ftrlm_state_count(c, F, lo, hi, s, &cb, &n, &differ, &rejected);
+  if (rc == PSG_OK && hipMemcpyAsync(n_dev, cb + 16, 8, hipMemcpyDeviceToDevice, s) != hipSuccess)
+    rc = fail(PSG_ERR_DEVICE, "ftrlm state export: count copy");
+  if (rc == PSG_OK && n > cap)
+    rc = fail(PSG_ERR_SIZE, "multi-model FTRL state export: %zu entries, room for %zu", n, cap);
+  else if (rc == PSG_OK)
+    rc = ftrlm_state_emit(c, F, lo, hi, n, differ, cb, keys, pos, neg, w, z, s);
+  const int rm = ftrlm_mark(c, F, s);
+  ftrlm_state_put(c, F, s, cb, cbytes);
+  if (rc != PSG_OK || rm != PSG_OK) return rc ? rc : rm;
+  return ftrlm_report(c, F, rejected);
+}
+
+int psg_ftrlm_export_state(psg_ctx* c, const uint64_t* range, uint64_t* keys, uint64_t* pos,
+                           uint64_t* neg, double* w, double* z, size_t cap, size_t* n_out) {
+  if (!c || !n_out) return fail(PSG_ERR_ARG, "null argument");
+  uint64_t lo, hi;
+  if (int rc = ftrlm_state_range(range, &lo, &hi)) return rc;
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  if (int rc = set_dev(c->device)) return rc;
+  *n_out = 0;
+  hipStream_t s = c->stream;
+  char* cb = nullptr;
+  const size_t cbytes = ftrlm_state_count_bytes(F);
+  size_t n = 0;
+  uint64_t differ = 0;
+  unsigned long long rejected = 0;
+  int rc = ftrlm_state_count(c, F, lo, hi, s, &cb, &n, &differ, &rejected);
+  if (rc == PSG_OK) *n_out = n;
+  if (rc == PSG_OK && n > cap)
+    rc = fail(PSG_ERR_SIZE, "multi-model FTRL state export: %zu entries, room for %zu", n, cap);
+  void* const dst[5] = {keys, pos, neg, w, z};
+  const bool any = keys || pos || neg || w || z;
+  if (rc == PSG_OK && n && any) {
+    // keys, pos, neg of 8 n bytes, then the w and z rows of 8 n m bytes
+    const size_t kb = align_up(8 * n, 256), rb = align_up(8 * n * F->m, 256);
+    const size_t off[5] = {0, kb, 2 * kb, 3 * kb, 3 * kb + rb};
+    const size_t len[5] = {8 * n, 8 * n, 8 * n, 8 * n * F->m, 8 * n * F->m};
+    char* ob = nullptr;
+    rc = c->dev_get(3 * kb + 2 * rb, (void**)&ob, s);
+    if (rc == PSG_OK) {
+      void* d[5];
+      for (int i = 0; i < 5; ++i) d[i] = dst[i] ? ob + off[i] : nullptr;
+      rc = ftrlm_state_emit(c, F, lo, hi, n, differ, cb, (uint64_t*)d[0], (uint64_t*)d[1],
+                      (uint64_t*)d[2], (double*)d[3], (double*)d[4], s);
+      for (int i = 0; i < 5 && rc == PSG_OK; ++i)
+        if (dst[i] &&
+            hipMemcpyAsync(dst[i], d[i], len[i], hipMemcpyDeviceToHost, s) != hipSuccess)
+          rc = fail(PSG_ERR_DEVICE, "ftrlm state export: copy to the host");
+      if (hipStreamSynchronize(s) != hipSuccess && rc == PSG_OK)
+        rc = fail(PSG_ERR_DEVICE, "ftrlm state export: wait");
+      c->dev_put(ob, 3 * kb + 2 * rb);
+    }
+  }
+  c->dev_put(cb, cbytes);
+  if (rc != PSG_OK) return rc;
   return ftrlm_report(c, F, rejected);
 }
 

@@ -82,4 +82,28 @@ hipError_t launch_ftrlm_status(const FtrlmTable& T, hipStream_t s);
 hipError_t launch_ftrlm_export(const FtrlmTable& T, int j, uint64_t* keys, double* w, uint64_t cap,
                                hipStream_t s);
 
+// ---- checkpoint and restore ------------------------------
+// Upsert of n whole entries keys[n], pos[n], neg[n], w[n][m], z[n][m]: the
+// order check, then every key's counts and both rows replaced; applies nothing
+// unless the check passed.
+hipError_t launch_ftrlm_import(const FtrlmTable& T, const uint64_t* keys, const uint64_t* pos,
+                               const uint64_t* neg, const double* w, const double* z, uint64_t n,
+                               hipStream_t s);
+// The same for one column: w[row][j] of every key; a fresh row is zeros elsewhere.
+hipError_t launch_ftrlm_import_weights(const FtrlmTable& T, int j, const uint64_t* keys,
+                                       const double* w, uint64_t n, hipStream_t s);
+// Whole-state export in two steps, with the host's one wait between them.
+// Step 1: small[0] = OR, small[1] = AND, small[2] = count of the keys that hold
+// a row and lie in [lo, hi]; tile_sum (ftrlm_state_count_words words) is left
+// as step 2's tile bases.  PSG_ERR_SIZE for an index of 2^32 - 1 slots or more.
+size_t ftrlm_state_count_words(const FtrlmTable& T);
+int launch_ftrlm_state_count(const FtrlmTable& T, uint64_t lo, uint64_t hi, uint32_t* tile_sum,
+                             unsigned long long* small, hipStream_t s);
+// Step 2: those n entries sorted by key into keys[n], pos[n], neg[n], w[n][m],
+// z[n][m] (any may be null); differ = OR ^ AND; work: ftrlm_state_work_bytes(n).
+size_t ftrlm_state_work_bytes(uint64_t n);
+int launch_ftrlm_state(const FtrlmTable& T, uint64_t lo, uint64_t hi, uint64_t n, uint64_t differ,
+                       const uint32_t* tile_base, void* work, uint64_t* keys, uint64_t* pos,
+                       uint64_t* neg, double* w, double* z, hipStream_t s);
+
 }  // namespace psg

@@ -17,6 +17,11 @@
 // per-model nnz deltas fold across the wave's groups by shuffles, across the
 // workgroup's waves through LDS, and leave by integer atomics on one of
 // kFtrlmSlots counter lines.  No float atomics.
+//
+// Checkpoint and restore are further down: the import
+// kernels, which walk the index one lane per key and take a workgroup's row
+// ids from one atomic, and the whole-state export (flag scan over the index,
+// sort by key, row gather by groups of G lanes).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -343,6 +348,273 @@ __global__ __launch_bounds__(256) void ftrlm_export_kernel(FtrlmTable T, uint32_
   }
 }
 
+// ---- import -----------------------------------------------
+constexpr uint64_t kFreshBit = 1ull << 62;  // row ids are below 2^32
+
+// Phase 1 of both import kernels: lane t of the workgroup owns key t of its
+// 256 (`in`: there is one; every lane comes here).  The row is found, or
+// claimed by the update kernel's walk and CAS; the workgroup's fresh keys are
+// counted by a scan and take consecutive row ids from ONE integer atomic on
+// head->rows_used.  (One atomic per wave, as the update kernel has it, is what
+// bounds a launch of few keys per wave: every wave waits its turn on that one
+// address.)  Key 0 is row 0.  Returns the row, or kFtrlmNoRow; *fresh_row: the
+// row held no entry before (its store is zeros).
+__device__ __forceinline__ uint64_t ftrlm_block_rows(const FtrlmTable& T, uint64_t key, bool in,
+                                                     uint32_t* ws, unsigned long long* base,
+                                                     bool* fresh_row) {
+  FtrlmHead* head = T.head;
+  uint64_t row = kFtrlmNoRow;
+  FtrlmSlot* slot = nullptr;
+  bool fresh = false, fresh0 = false;
+  if (in) {
+    if (key == 0) {  // at most one lane of the launch: the keys are unique
+      row = 0;
+      fresh0 = head->zero_present == 0;
+      if (fresh0) head->zero_present = 1;
+    } else {
+      slot = ftrlm_claim(T, key, &fresh);
+      if (!slot) atomicAdd(&head->overflow, 1ull);
+      else if (!fresh) row = slot->row != 0 && slot->row < T.row_cap ? slot->row : kFtrlmNoRow;
+    }
+  }
+  uint32_t total;
+  const uint32_t before = block_exscan(fresh ? 1u : 0u, ws, &total);
+  if (threadIdx.x == 0 && total) *base = atomicAdd(&head->rows_used, (unsigned long long)total);
+  __syncthreads();
+  if (fresh) {
+    const uint64_t r = 1 + *base + before;
+    if (r < T.row_cap) {
+      slot->row = r;
+      row = r;
+    } else {
+      atomicAdd(&head->overflow, 1ull);
+    }
+  }
+  *fresh_row = fresh0 || (fresh && row != kFtrlmNoRow);
+  return row;
+}
+
+// (w_new != 0) - (w_old != 0) with ftrl_model.h:106-110's comparisons: -0.0 is
+// zero, a NaN weight is not
+__device__ __forceinline__ int nnz_step(double w_new, double w_old) {
+  return (w_new != 0 ? 1 : 0) - (w_old != 0 ? 1 : 0);
+}
+
+// A workgroup owns 256 entries of the image whatever m is.  Phase 1: one lane
+// per key finds or claims the row (above) and stores the two counts; the row
+// ids wait in LDS.  Phase 2: the workgroup walks its keys 256 / G at a time, a
+// group of G lanes per key, lane j replacing w[row][j] and z[row][j]: the
+// image's rows are read and the store's rows written as contiguous 8 m bytes,
+// and the rows of a workgroup's fresh keys are neighbours.  Every bit is
+// stored as given.  The nnz deltas leave as the update kernel's do.
+__global__ __launch_bounds__(256) void ftrlm_import_kernel(FtrlmTable T,
+                                                           const uint64_t* __restrict__ keys,
+                                                           const uint64_t* __restrict__ pos,
+                                                           const uint64_t* __restrict__ neg,
+                                                           const double* __restrict__ w,
+                                                           const double* __restrict__ z,
+                                                           uint64_t n) {
+  FtrlmHead* head = T.head;
+  __shared__ int part[4][kFtrlmMax];
+  __shared__ uint64_t rows[256];
+  __shared__ uint32_t ws[4];
+  __shared__ unsigned long long base;
+  if (head->verdict) return;  // the message is rejected whole (workgroup-uniform)
+  const uint32_t lane = threadIdx.x & 63u, G = 1u << T.gs, j = lane & (G - 1), m = T.m;
+  const uint64_t i0 = (uint64_t)blockIdx.x * 256u, i = i0 + threadIdx.x;
+  const bool in = i < n;
+  bool fresh;
+  const uint64_t row = ftrlm_block_rows(T, in ? keys[i] : 0, in, ws, &base, &fresh);
+  if (in && row != kFtrlmNoRow) {
+    T.cnt[2 * row] = pos[i];
+    T.cnt[2 * row + 1] = neg[i];
+  }
+  rows[threadIdx.x] = row == kFtrlmNoRow ? row : row | (fresh ? kFreshBit : 0);
+  __syncthreads();
+  const uint32_t nkeys = (uint32_t)(n - i0 < 256u ? n - i0 : 256u);
+  int d_nnz = 0;
+  if (j < m)
+    for (uint32_t t = threadIdx.x >> T.gs; t < nkeys; t += 256u >> T.gs) {
+      const uint64_t r = rows[t];
+      if (r == kFtrlmNoRow) continue;
+      const uint64_t at = (r & ~kFreshBit) * m + j, from = (i0 + t) * m + j;
+      const double w_old = (r & kFreshBit) ? 0.0 : T.w[at], w_new = w[from];
+      T.w[at] = w_new;
+      T.z[at] = z[from];
+      d_nnz += nnz_step(w_new, w_old);
+    }
+  for (uint32_t s = G; s < 64; s <<= 1) d_nnz += __shfl_xor(d_nnz, (int)s, 64);
+  if (lane < G) part[threadIdx.x >> 6][lane] = d_nnz;
+  __syncthreads();
+  if (threadIdx.x < m) {
+    const long long d = (long long)part[0][threadIdx.x] + part[1][threadIdx.x] +
+                        part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (d)  // two's complement: the slots' sum is the signed total
+      __hip_atomic_fetch_add(
+          &head->nnz_slots[(blockIdx.x % kFtrlmSlots) * kFtrlmMax + threadIdx.x],
+          (unsigned long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Column jm alone, one lane per key throughout: w[row][jm] is replaced, the
+// row's other columns, its z and its counts stay (zeros in a fresh row: the
+// store is zeroed when it is allocated).
+__global__ __launch_bounds__(256) void ftrlm_import_weights_kernel(
+    FtrlmTable T, uint32_t jm, const uint64_t* __restrict__ keys, const double* __restrict__ w,
+    uint64_t n) {
+  FtrlmHead* head = T.head;
+  __shared__ int part[4];
+  __shared__ uint32_t ws[4];
+  __shared__ unsigned long long base;
+  if (head->verdict) return;
+  const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const bool in = i < n;
+  bool fresh;
+  const uint64_t row = ftrlm_block_rows(T, in ? keys[i] : 0, in, ws, &base, &fresh);
+  int d_nnz = 0;
+  if (in && row != kFtrlmNoRow) {
+    const uint64_t at = row * T.m + jm;
+    const double w_old = fresh ? 0.0 : T.w[at], w_new = w[i];
+    T.w[at] = w_new;
+    d_nnz = nnz_step(w_new, w_old);
+  }
+  for (int s = 32; s >= 1; s >>= 1) d_nnz += __shfl_xor(d_nnz, s, 64);
+  if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = d_nnz;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const long long d = (long long)part[0] + part[1] + part[2] + part[3];
+    if (d)
+      __hip_atomic_fetch_add(&head->nnz_slots[(blockIdx.x % kFtrlmSlots) * kFtrlmMax + jm],
+                             (unsigned long long)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---- whole-state export -----------------------------------
+// Element i < slots of the flag scans is an index slot, element `slots` the
+// side entry (key 0, row 0).  Flagged: holds a row and lo <= key <= hi.
+struct RowsFlag {
+  FtrlmTable T;
+  uint64_t lo, hi;
+  uint32_t nslots;
+  __device__ bool entry(uint32_t i, uint64_t* key, uint32_t* row) const {
+    if (i < nslots) {
+      const FtrlmSlot s = T.idx[i];
+      *key = s.key;
+      *row = (uint32_t)s.row;
+      return s.key != 0 && s.row != 0 && s.row < T.row_cap && s.key >= lo && s.key <= hi;
+    }
+    *key = 0;
+    *row = 0;
+    return T.head->zero_present != 0 && lo == 0;
+  }
+  __device__ bool operator()(uint32_t i) const {
+    uint64_t k;
+    uint32_t r;
+    return entry(i, &k, &r);
+  }
+};
+
+// the compacted (key, row id) of the flagged elements, in slot order
+struct RowsEmit {
+  RowsFlag f;
+  uint64_t* ckey;
+  uint32_t* crow;
+  uint32_t cap;
+  __device__ void operator()(uint32_t i, uint32_t ex, bool flagged, uint32_t) const {
+    if (!flagged || ex >= cap) return;  // ex < cap always, by the count
+    uint64_t k;
+    uint32_t r;
+    (void)f.entry(i, &k, &r);
+    ckey[ex] = k;
+    crow[ex] = r;
+  }
+};
+
+__global__ void ftrlm_state_init_kernel(unsigned long long* small) {
+  small[0] = 0;
+  small[1] = ~0ull;
+  small[2] = 0;
+}
+
+// One pass over the index in flag_count_kernel's tile shape (a lane owns 8
+// consecutive slots, one 128-B line): the tile's flag count for the scan, and
+// orand[0] |= / orand[1] &= every flagged key, folded over the wave first.
+__global__ __launch_bounds__(256) void ftrlm_state_count_kernel(
+    RowsFlag f, uint32_t n, uint32_t* __restrict__ tile_sum,
+    unsigned long long* __restrict__ orand) {
+  __shared__ uint32_t ws[4];
+  const uint64_t i0 = (uint64_t)blockIdx.x * kFlagTile + threadIdx.x * 8u;
+  uint32_t c = 0;
+  uint64_t o = 0, a = ~0ull;
+  for (uint32_t j = 0; j < 8; ++j)
+    if (i0 + j < n) {
+      uint64_t k;
+      uint32_t r;
+      if (f.entry((uint32_t)(i0 + j), &k, &r)) {
+        ++c;
+        o |= k;
+        a &= k;
+      }
+    }
+  for (int s = 32; s >= 1; s >>= 1) {
+    o |= __shfl_xor(o, s, 64);
+    a &= __shfl_xor(a, s, 64);
+  }
+  if ((threadIdx.x & 63u) == 0 && (o | ~a)) {
+    atomicOr(orand, (unsigned long long)o);
+    atomicAnd(orand + 1, (unsigned long long)a);
+  }
+  uint32_t tot;
+  (void)block_exscan(c, ws, &tot);
+  if (threadIdx.x == 0) tile_sum[blockIdx.x] = tot;
+}
+
+// A group of G lanes owns output entry i, the i-th key in key order.  Its
+// first lane reads the sorted pair's place, the row id there and the row's
+// counts; the row id goes round by shuffle and lane j copies w[row][j] and
+// z[row][j]: whole rows read, whole rows of the image written.
+__global__ __launch_bounds__(256) void ftrlm_state_gather_kernel(
+    FtrlmTable T, const uint64_t* __restrict__ skey, const uint32_t* __restrict__ spos,
+    const uint32_t* __restrict__ crow, uint32_t n, uint64_t* __restrict__ keys,
+    uint64_t* __restrict__ pos, uint64_t* __restrict__ neg, double* __restrict__ w,
+    double* __restrict__ z) {
+  const uint32_t lane = threadIdx.x & 63u, G = 1u << T.gs, j = lane & (G - 1), m = T.m;
+  const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) >> T.gs;
+  const bool in = i < n;
+  uint64_t row = kFtrlmNoRow;
+  if (in && j == 0) {
+    const uint32_t at = spos[i];
+    if (at < n && crow[at] < T.row_cap) row = crow[at];  // always: a permutation, a live row
+    if (row != kFtrlmNoRow) {
+      if (keys) keys[i] = skey[i];
+      if (pos) pos[i] = T.cnt[2 * row];
+      if (neg) neg[i] = T.cnt[2 * row + 1];
+    }
+  }
+  row = __shfl(row, (int)(lane & ~(G - 1)), 64);
+  if (in && j < m && row != kFtrlmNoRow) {
+    if (w) w[i * m + j] = T.w[row * m + j];
+    if (z) z[i * m + j] = T.z[row * m + j];
+  }
+}
+
+// the blocks of launch_ftrlm_state's work area for n entries
+struct RowsWork {
+  size_t ckey, key_a, key_b, crow, pos_a, pos_b, counts, dtotal, end;
+  explicit RowsWork(uint64_t n) {
+    const size_t k8 = (size_t)(8 * n + 255) & ~(size_t)255, k4 = (size_t)(4 * n + 255) & ~(size_t)255;
+    ckey = 0;
+    key_a = ckey + k8;
+    key_b = key_a + k8;
+    crow = key_b + k8;
+    pos_a = crow + k4;
+    pos_b = pos_a + k4;
+    counts = pos_b + k4;
+    dtotal = counts + 4 * 256 * (size_t)blocks_of(n, kSortTile);
+    end = dtotal + 4 * 256;
+  }
+};
+
 // lanes per key -> keys per workgroup of 256
 inline uint32_t group_blocks(const FtrlmTable& T, uint64_t n) { return blocks_of(n, 256u >> T.gs); }
 
@@ -401,6 +673,73 @@ hipError_t launch_ftrlm_export(const FtrlmTable& T, int j, uint64_t* keys, doubl
   hipLaunchKernelGGL(ftrlm_export_kernel, dim3(blocks_of(T.mask + 2, 256)), dim3(256), 0, s, T,
                      (uint32_t)j, keys, w, cap);
   return hipGetLastError();
+}
+
+hipError_t launch_ftrlm_import(const FtrlmTable& T, const uint64_t* keys, const uint64_t* pos,
+                               const uint64_t* neg, const double* w, const double* z, uint64_t n,
+                               hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ftrlm_clear_kernel, dim3(1), dim3(1), 0, s, &T.head->verdict);
+  if (n > 1)
+    hipLaunchKernelGGL(ftrlm_check_kernel, dim3(blocks_of(n - 1, 256)), dim3(256), 0, s, keys, n,
+                       T.head);
+  hipLaunchKernelGGL(ftrlm_import_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, T, keys, pos,
+                     neg, w, z, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_ftrlm_import_weights(const FtrlmTable& T, int j, const uint64_t* keys,
+                                       const double* w, uint64_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(ftrlm_clear_kernel, dim3(1), dim3(1), 0, s, &T.head->verdict);
+  if (n > 1)
+    hipLaunchKernelGGL(ftrlm_check_kernel, dim3(blocks_of(n - 1, 256)), dim3(256), 0, s, keys, n,
+                       T.head);
+  hipLaunchKernelGGL(ftrlm_import_weights_kernel, dim3(blocks_of(n, 256)), dim3(256), 0, s, T,
+                     (uint32_t)j, keys, w, n);
+  return hipGetLastError();
+}
+
+size_t ftrlm_state_count_words(const FtrlmTable& T) { return blocks_of(T.mask + 2, kFlagTile); }
+
+int launch_ftrlm_state_count(const FtrlmTable& T, uint64_t lo, uint64_t hi, uint32_t* tile_sum,
+                             unsigned long long* small, hipStream_t s) {
+  const uint64_t nel = T.mask + 2;  // the slots and the side entry
+  if (nel > 0xffffffffull)  // the sort's payload and the scans' element ids are 32 bits
+    return fail(PSG_ERR_SIZE, "multi-model FTRL state export: an index of %llu slots >= 2^32 - 1",
+                (unsigned long long)(nel - 1));
+  const RowsFlag f{T, lo, hi, (uint32_t)(nel - 1)};
+  const uint32_t nt = blocks_of(nel, kFlagTile);
+  hipLaunchKernelGGL(ftrlm_state_init_kernel, dim3(1), dim3(1), 0, s, small);
+  LAUNCH(ftrlm_state_count_kernel, nt, s, f, (uint32_t)nel, tile_sum, small);
+  LAUNCH(row_scan_kernel, 1, s, tile_sum, nt, (uint32_t*)(small + 2));
+  return launched("ftrlm state count");
+}
+
+size_t ftrlm_state_work_bytes(uint64_t n) { return RowsWork(n).end; }
+
+int launch_ftrlm_state(const FtrlmTable& T, uint64_t lo, uint64_t hi, uint64_t n, uint64_t differ,
+                       const uint32_t* tile_base, void* work, uint64_t* keys, uint64_t* pos,
+                       uint64_t* neg, double* w, double* z, hipStream_t s) {
+  if (n == 0) return PSG_OK;
+  const uint64_t nel = T.mask + 2;
+  const RowsWork W(n);
+  char* base = (char*)work;
+  uint64_t* ckey = (uint64_t*)(base + W.ckey);
+  uint32_t* crow = (uint32_t*)(base + W.crow);
+  const RowsFlag f{T, lo, hi, (uint32_t)(nel - 1)};
+  const RowsEmit em{f, ckey, crow, (uint32_t)n};
+  LAUNCH((flag_emit_kernel<RowsFlag, RowsEmit>), blocks_of(nel, kFlagTile), s, f, em,
+         (uint32_t)nel, tile_base);
+  const SortBuffers sb{(uint64_t*)(base + W.key_a), (uint64_t*)(base + W.key_b),
+                       (uint32_t*)(base + W.pos_a), (uint32_t*)(base + W.pos_b),
+                       (uint32_t*)(base + W.counts), (uint32_t*)(base + W.dtotal)};
+  const uint64_t* skey = nullptr;
+  const uint32_t* spos = nullptr;
+  if (int rc = enqueue_radix_sort(ckey, (uint32_t)n, differ, sb, &skey, &spos, s)) return rc;
+  LAUNCH(ftrlm_state_gather_kernel, group_blocks(T, n), s, T, skey, spos, crow, (uint32_t)n, keys,
+         pos, neg, w, z);
+  return launched("ftrlm state export");
 }
 
 }  // namespace psg

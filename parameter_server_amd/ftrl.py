@@ -104,12 +104,62 @@ def save_state(path, keys, pos, neg, w, z, alpha, beta, lambda1, lambda2, frozen
 def load_state(path) -> dict:
     """The fields ``save_state`` wrote, by name; rejects any other version."""
     with np.load(path, allow_pickle=False) as f:
+        if MULTI_VERSION_FIELD in f.files:
+            raise ValueError(f"{path}: a multi-model FTRL image; load_multi_state reads it")
         if "format_version" not in f.files:
             raise ValueError(f"{path}: no FTRL model image (no format_version)")
         version = int(f["format_version"])
         if version != STATE_VERSION:
             raise ValueError(f"{path}: format version {version}, this reader knows "
                              f"{STATE_VERSION}")
+        return {name: f[name] for name in f.files}
+
+
+# The image of an FTRLMultiModel: the five arrays (w and z are [n, m]), the m
+# parameter sets as four float64 arrays of length m, m, frozen, and a format
+# version under a field name of its own, so that neither loader takes the
+# other's file.
+MULTI_STATE_VERSION = 1
+MULTI_VERSION_FIELD = "multi_format_version"
+
+
+def save_multi_state(path, keys, pos, neg, w, z, params, frozen=False, **extra) -> None:
+    """One ``.npz`` at exactly ``path``: the image of an ``FTRLMultiModel``
+    (``state``), ``params`` (its m dicts), ``frozen``, the format version and
+    the caller's ``extra`` arrays."""
+    m = len(params)
+    arrays = {name: np.ascontiguousarray(a, dtype=dt)
+              for (name, dt), a in zip(_STATE_ARRAYS, (keys, pos, neg, w, z))}
+    n = arrays["keys"].size
+    if arrays["pos"].shape != (n,) or arrays["neg"].shape != (n,) or \
+            arrays["w"].shape != (n, m) or arrays["z"].shape != (n, m):
+        raise ValueError(f"a multi-model image of {n} keys has pos[n], neg[n], w[n, {m}], "
+                         f"z[n, {m}]")
+    for name in _STATE_PARAMS:
+        arrays[name] = np.array([p[name] for p in params], dtype=np.float64)
+    arrays["m"] = np.array(m, dtype=np.int64)
+    arrays["frozen"] = np.array(1 if frozen else 0, dtype=np.int64)
+    arrays[MULTI_VERSION_FIELD] = np.array(MULTI_STATE_VERSION, dtype=np.int64)
+    for name, v in extra.items():
+        if name in arrays or name == "format_version":
+            raise ValueError(f"{name} is a field of the format")
+        arrays[name] = np.asarray(v)
+    with open(path, "wb") as f:
+        np.savez(f, **arrays)
+
+
+def load_multi_state(path) -> dict:
+    """The fields ``save_multi_state`` wrote, by name; rejects a scalar image
+    and any other version."""
+    with np.load(path, allow_pickle=False) as f:
+        if MULTI_VERSION_FIELD not in f.files:
+            if "format_version" in f.files:
+                raise ValueError(f"{path}: a single-model FTRL image; load_state reads it")
+            raise ValueError(f"{path}: no multi-model FTRL image (no {MULTI_VERSION_FIELD})")
+        version = int(f[MULTI_VERSION_FIELD])
+        if version != MULTI_STATE_VERSION:
+            raise ValueError(f"{path}: multi-model format version {version}, this reader knows "
+                             f"{MULTI_STATE_VERSION}")
         return {name: f[name] for name in f.files}
 
 
@@ -332,8 +382,9 @@ class FTRLMultiModel:
     ``params``: a list of m dicts with the keys ``alpha``, ``beta``,
     ``lambda1``, ``lambda2`` (1 <= m <= 32).  Row-valued arrays are
     ``[n, m]``; column j is bit for bit what an ``FTRLModel`` with
-    ``params[j]`` gives for the same messages.  Checkpoints, the frozen form
-    and the C++ adapter are not built for it (include/psg.h)."""
+    ``params[j]`` gives for the same messages.  ``state`` / ``restore`` /
+    ``save`` / ``load`` checkpoint the sweep, ``readFromFiles`` loads a saved
+    one for scoring; the C++ adapter is not built for it (include/psg.h)."""
 
     def __init__(self, params, device: int = 0, capacity_hint: int = 0, flags: int = 0):
         self._L = _lib.lib()
@@ -422,3 +473,93 @@ class FTRLMultiModel:
                                                 C.byref(n)))
         order = np.argsort(keys, kind="stable")
         return keys[order], w[order]
+
+    # -- checkpoint: psg_ftrlm_export_state / psg_ftrlm_import ----------------
+    def state(self, range=None):
+        """(keys, pos, neg, w[n, m], z[n, m]) of every key the sweep holds in
+        the closed interval ``range = (first, last)`` (None: all), sorted by
+        key on the device."""
+        r = None
+        if range is not None:
+            r = (C.c_uint64 * 2)(int(range[0]), int(range[1]))
+        n = C.c_size_t()
+        rc = self._L.psg_ftrlm_export_state(self._h, r, None, None, None, None, None, 0,
+                                            C.byref(n))
+        if rc not in (_lib.PSG_OK, _lib.PSG_ERR_SIZE):
+            _lib.check(rc)
+        out = [np.empty(n.value if i < 3 else (n.value, self.m), dt)
+               for i, (_, dt) in enumerate(_STATE_ARRAYS)]
+        if n.value:
+            _lib.check(self._L.psg_ftrlm_export_state(self._h, r, *[_ptr(a) for a in out],
+                                                      n.value, C.byref(n)))
+        return tuple(out)
+
+    def restore(self, keys, pos, neg, w, z) -> None:
+        """An upsert of whole entries, strictly increasing by key
+        (psg_ftrlm_import); ``w`` and ``z`` are ``[n, m]``."""
+        if any(a is None for a in (keys, pos, neg, w, z)):
+            raise _lib.PSGError(_lib.PSG_ERR_ARG, "restore needs keys, pos, neg, w and z")
+        arrays = [np.ascontiguousarray(a, dtype=dt)
+                  for (_, dt), a in zip(_STATE_ARRAYS, (keys, pos, neg, w, z))]
+        n = arrays[0].size
+        if [a.size for a in arrays[1:]] != [n, n, n * self.m, n * self.m]:
+            raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"values for {n} keys x {self.m} models")
+        if n:
+            _lib.check(self._L.psg_ftrlm_import(self._h, _ptr(arrays[0]), n,
+                                                *[_ptr(a) for a in arrays[1:]]))
+
+    def restore_weights(self, j: int, keys, w) -> None:
+        """Model j's weights alone (psg_ftrlm_import_weights): the other
+        columns of a key already present stay.  Freezes the sweep."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.size != keys.size:
+            raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"{w.size} values for {keys.size} keys")
+        _lib.check(self._L.psg_ftrlm_import_weights(self._h, int(j), _ptr(keys), keys.size,
+                                                    _ptr(w)))
+
+    @property
+    def frozen(self) -> bool:
+        """Evaluation only: loaded by ``restore_weights`` (psg_ftrlm_frozen)."""
+        f = C.c_int()
+        _lib.check(self._L.psg_ftrlm_frozen(self._h, C.byref(f)))
+        return bool(f.value)
+
+    def save(self, path, **extra) -> None:
+        """The sweep's image, its m parameter sets and ``extra`` arrays in one
+        ``.npz`` (``save_multi_state``)."""
+        frozen = self.frozen
+        save_multi_state(path, *self.state(), self.params, frozen=frozen, **extra)
+
+    @classmethod
+    def from_state(cls, st: dict, device: int = 0, flags: int = 0) -> "FTRLMultiModel":
+        """A sweep holding what ``load_multi_state`` read: the parameters and
+        every entry by bits; a frozen one comes back frozen."""
+        params = [dict(zip(_STATE_PARAMS, (float(st[k][j]) for k in _STATE_PARAMS)))
+                  for j in np.arange(int(st["m"]))]
+        mm = cls(params, device, capacity_hint=int(st["keys"].size), flags=flags)
+        mm.restore(st["keys"], st["pos"], st["neg"], st["w"], st["z"])
+        if int(st["frozen"]):  # an empty weights-only import sets the flag and nothing else
+            mm.restore_weights(0, np.zeros(0, np.uint64), np.zeros(0, np.float64))
+        return mm
+
+    @classmethod
+    def load(cls, path, device: int = 0) -> "FTRLMultiModel":
+        return cls.from_state(load_multi_state(path), device)
+
+    def readFromFiles(self, paths_per_model, real=np.float64) -> None:
+        """A saved sweep for scoring: ``paths_per_model[j]`` are model j's
+        ``key w`` files (``read_model_text``), loaded into column j.  The m
+        key sets may differ; a key some file lacks is +0.0 in that column."""
+        if len(paths_per_model) != self.m:
+            raise ValueError(f"{len(paths_per_model)} path lists for {self.m} models")
+        for j, paths in enumerate(paths_per_model):
+            self.restore_weights(j, *read_model_text(paths, real))
+
+    def writeToFile(self, j: int, path: str) -> None:
+        """Model j's nonzero weights, one ``key\\tw`` line each, sorted by key,
+        as ``FTRLModel.writeToFile`` writes one model's."""
+        keys, w = self.export(j)
+        with open(path, "w") as f:
+            for k, v in zip(keys.tolist(), w.tolist()):
+                f.write("%d\t%s\n" % (k, format_weight(v)))

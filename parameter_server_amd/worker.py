@@ -21,8 +21,8 @@ from typing import Tuple
 import numpy as np
 
 from . import _lib
-from .auc import exact_auc, exact_auc_rows_dev
-from .ftrl import FTRLModel, FTRLMultiModel, load_state
+from .auc import exact_auc, exact_auc_rows, exact_auc_rows_dev
+from .ftrl import FTRLModel, FTRLMultiModel, load_multi_state, load_state
 from .kv_vector import _ptr
 
 # psg_mb_read's arrays: name -> (id, dtype)
@@ -323,6 +323,24 @@ class _TailFilteredWorker:
             return self.mb.read_scratch(self._DICT, np.uint64, self.ndict).copy()
         return self.mb.read("uniq_key")
 
+    def freq_table(self) -> np.ndarray:
+        """The tail filter's CountMin counters (psg_freq_table)."""
+        out = np.zeros(self.countmin_n, np.uint8)
+        _lib.check(self._L.psg_freq_table(self._ctx, self.chl, _ptr(out), out.size))
+        return out
+
+    def _filter_state(self) -> dict:
+        """The worker's part of a checkpoint: ``objv``, ``num_ex``, and with
+        the tail filter on its threshold and the CountMin table with its ``n``
+        and ``k``."""
+        extra = dict(objv=np.array(self.objv, np.float64), num_ex=np.array(self.num_ex, np.int64),
+                     tail_feature_freq=np.array(self.freq, np.int64))
+        if self.freq > 0:
+            extra.update(countmin_n=np.array(self.countmin_n, np.int64),
+                         countmin_k=np.array(self.countmin_k, np.int64),
+                         countmin_table=self.freq_table())
+        return extra
+
 
 class FTRLWorker(_TailFilteredWorker):
     """The worker of the online solver (ftrl.cc:88-151) for one model.
@@ -420,24 +438,12 @@ class FTRLWorker(_TailFilteredWorker):
         return self.mb.read_scratch(self._W, np.float64, self.ndict).copy()
 
     # -- checkpoint ----------------------------------------------------------
-    def freq_table(self) -> np.ndarray:
-        """The tail filter's CountMin counters (psg_freq_table)."""
-        out = np.zeros(self.countmin_n, np.uint8)
-        _lib.check(self._L.psg_freq_table(self._ctx, self.chl, _ptr(out), out.size))
-        return out
-
     def save(self, path) -> None:
         """Everything the next step depends on, in one ``.npz``
         (``ftrl.save_state``): the model's image and parameters, ``objv`` and
         ``num_ex``, and with the tail filter on its threshold and the CountMin
         table with its ``n`` and ``k``."""
-        extra = dict(objv=np.array(self.objv, np.float64), num_ex=np.array(self.num_ex, np.int64),
-                     tail_feature_freq=np.array(self.freq, np.int64))
-        if self.freq > 0:
-            extra.update(countmin_n=np.array(self.countmin_n, np.int64),
-                         countmin_k=np.array(self.countmin_k, np.int64),
-                         countmin_table=self.freq_table())
-        self.model.save(path, **extra)
+        self.model.save(path, **self._filter_state())
 
     @classmethod
     def load(cls, path, device: int = 0, chl: int = 0) -> "FTRLWorker":
@@ -479,6 +485,9 @@ class FTRLMultiWorker(_TailFilteredWorker):
         self._ctx = model._model()
         self.freq = int(tail_feature_freq)
         self.chl = chl
+        # CountMin::resize's n_ and k_ (countmin.h:14-19)
+        self.countmin_n = max(int(countmin_n), 64)
+        self.countmin_k = min(30, max(1, int(countmin_k)))
         if self.freq > 0:
             _lib.check(self._L.psg_freq_resize(self._ctx, chl, countmin_n, countmin_k))
         self.mb = Minibatch(self._ctx)
@@ -556,6 +565,33 @@ class FTRLMultiWorker(_TailFilteredWorker):
         mb.times_rows(w, self.m, xw)
         return exact_auc_rows_dev(self._ctx, mb.labels()[0], xw, mb.rows, self.m, mb.stream)
 
+    # -- checkpoint ----------------------------------------------------------
+    def save(self, path) -> None:
+        """Everything the next step depends on, in one ``.npz``
+        (``ftrl.save_multi_state``): the sweep's image and parameters,
+        ``objv[m]`` and ``num_ex``, and the tail filter as ``FTRLWorker.save``
+        keeps it."""
+        self.model.save(path, **self._filter_state())
+
+    @classmethod
+    def load(cls, path, device: int = 0, chl: int = 0) -> "FTRLMultiWorker":
+        """A worker, with a sweep of its own, that goes on where ``save``
+        stopped: the same steps give the same bits."""
+        st = load_multi_state(path)
+        if "tail_feature_freq" not in st:
+            raise ValueError(f"{path}: a multi-model image without a worker's state")
+        freq = int(st["tail_feature_freq"])
+        model = FTRLMultiModel.from_state(st, device)
+        if freq > 0:
+            wk = cls(model, freq, int(st["countmin_n"]), int(st["countmin_k"]), chl)
+            table = np.ascontiguousarray(st["countmin_table"], dtype=np.uint8)
+            _lib.check(wk._L.psg_freq_table_assign(wk._ctx, chl, _ptr(table), table.size))
+        else:
+            wk = cls(model, chl=chl)
+        wk.objv = np.array(st["objv"], np.float64)
+        wk.num_ex = int(st["num_ex"])
+        return wk
+
 
 def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device: int = 0,
                    real=np.float32):
@@ -588,6 +624,40 @@ def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device
         y = np.concatenate(labels) if labels else np.zeros(0, np.float64)
         xw = np.concatenate(predictions) if predictions else np.zeros(0, np.float64)
         return exact_auc(model._h, y, xw), y, xw
+    finally:
+        if wk is not None:
+            wk.close()
+        model.close()
+
+
+def evaluate_models(model_paths_per_model, text: bytes, fmt, max_rows: int = 100000,
+                    device: int = 0, real=np.float32):
+    """``evaluate_model`` for a saved sweep in one pass over the text:
+    ``model_paths_per_model[j]`` are model j's ``key w`` files, loaded into
+    column j of one frozen ``FTRLMultiModel`` (``readFromFiles``); the text is
+    walked with ``FTRLMultiWorker.predict_text`` and all columns are scored by
+    ``exact_auc_rows``.  Returns (auc[m], labels, predictions[rows, m]); column
+    j is bit for bit what ``evaluate_model`` gives for model j's files."""
+    m = len(model_paths_per_model)
+    model = FTRLMultiModel([dict(alpha=1.0, beta=1.0, lambda1=0.0, lambda2=0.0)] * m, device)
+    wk = None
+    try:
+        model.readFromFiles(model_paths_per_model, real=real)
+        wk = FTRLMultiWorker(model)
+        text = bytes(text)
+        labels, predictions = [], []
+        at = 0
+        while at < len(text):
+            xw, consumed = wk.predict_text(text[at:], fmt, max_rows)
+            if wk.mb.rows:
+                labels.append(wk.mb.read("y"))
+                predictions.append(xw)
+            if consumed == 0:
+                break
+            at += consumed
+        y = np.concatenate(labels) if labels else np.zeros(0, np.float64)
+        xw = np.concatenate(predictions) if predictions else np.zeros((0, m), np.float64)
+        return exact_auc_rows(model._h, y, xw), y, xw
     finally:
         if wk is not None:
             wk.close()
