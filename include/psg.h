@@ -1457,6 +1457,42 @@ int psg_mb_darling_share_dual(psg_minibatch* mb, psg_minibatch* owner);
  * bits are the same unless v is an infinity or a NaN. */
 int psg_mb_labels(psg_minibatch* mb, const double** y_dev, const double** xw_dev);
 
+/* The direct scorer: Xw of a loaded minibatch against the context's resident
+ * model by one hash probe per entry, which is the reference's loop
+ * (model_evaluation.h:48-57).  Per row i: re = +0.0; for j from offset[i] to
+ * offset[i+1], in that order: if index[j] has an entry in the table,
+ * re = re + w * value[j] (a binary minibatch: re + w).  An absent key adds
+ * nothing; an entry whose weight is zero is present and is added; key 0 is
+ * looked up like any other.  PSG_SCORE_F64: one rounded double multiply and
+ * one rounded double add per present entry.  PSG_SCORE_F32: the reference's
+ * Real = float (:12): w and value rounded to float, one rounded float multiply
+ * and one rounded float add per present entry, the float sum widened to double
+ * on store.
+ * psg_ftrl_score_dev scores against the psg_ftrl_* model into xw_dev[rows];
+ * xw_dev == NULL is the minibatch's own Xw (the block psg_mb_labels returns;
+ * psg_mb_read(PSG_MB_XW) then reads it).  psg_ftrlm_score_dev scores against
+ * the psg_ftrlm_* sweep into xw_dev[rows * m], row-major; column j is bit for
+ * bit the scalar call on a scalar model that holds column j.
+ * The minibatch must be loaded (any load) and its state is not changed: no
+ * sort, unique pass, localize or dictionary is needed or touched, only
+ * scratch blocks of the scorer's own.  The model is neither written nor
+ * inserted into, and may be frozen.  The work is enqueued on `stream` (NULL:
+ * the context's) with no host wait, in the model's and the minibatch's call
+ * order.  PSG_ERR_ARG: an unknown `real`, a minibatch that is not loaded or is
+ * another context's, a context without the model in question.
+ * Defined deviation from the psg_mb_times path above: that one pulls +0.0
+ * for an absent key and adds 0 * v, this one skips the entry.  With finite
+ * values the bits are the same (a sum that starts at +0.0 never becomes -0.0
+ * by adding +-0.0); with an infinite or NaN value on an absent key the times
+ * path gives NaN and the scorer, like the reference, does not see the entry.
+ * psg_score_tile: the entries per workgroup tile of the kernel that serves m
+ * models in `real` (m = 0: the scalar model's kernel), for tests. */
+#define PSG_SCORE_F64 0
+#define PSG_SCORE_F32 1
+int psg_ftrl_score_dev(psg_ctx* ctx, psg_minibatch* mb, int real, double* xw_dev, void* stream);
+int psg_ftrlm_score_dev(psg_ctx* ctx, psg_minibatch* mb, int real, double* xw_dev, void* stream);
+size_t psg_score_tile(int m, int real);
+
 /* A psg_auc is the root's two maps (auc.h:101) as one histogram resident in
  * HBM: the distinct keys in ascending signed order, a uint64 positive and a
  * uint64 negative count per key.  A handle's calls run in call order whatever

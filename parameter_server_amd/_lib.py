@@ -65,6 +65,7 @@ MAX_VALUE_ARRAYS = 4
 MB_STAGES = ("sort", "run_length", "localize", "count_keys", "times", "logit", "trans_times")
 # psg_mb_gradient's loss and psg_mb_read's arrays
 PSG_LOSS_LOGIT = 0
+PSG_SCORE_F64, PSG_SCORE_F32 = 0, 1
 (PSG_MB_SORTED_KEY, PSG_MB_SORTED_POS, PSG_MB_UNIQ_KEY, PSG_MB_KEY_CNT, PSG_MB_NEW_OFFSET,
  PSG_MB_NEW_INDEX, PSG_MB_NEW_VALUE, PSG_MB_POS, PSG_MB_NEG, PSG_MB_XW, PSG_MB_TAU, PSG_MB_LOSS,
  PSG_MB_GRAD, PSG_MB_RUN_START, PSG_MB_REMAPPED, PSG_MB_ROW_OF, PSG_MB_SCRATCH) = range(17)
@@ -335,6 +336,9 @@ SIGNATURES = {
     "psg_mb_darling_objv": (C.c_int, [_p, C.POINTER(C.c_double), _p]),
     "psg_mb_darling_set_state": (C.c_int, [_p, _p, _p, _p, _p]),
     "psg_mb_labels": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
+    "psg_ftrl_score_dev": (C.c_int, [_p, _p, C.c_int, _p, _p]),
+    "psg_ftrlm_score_dev": (C.c_int, [_p, _p, C.c_int, _p, _p]),
+    "psg_score_tile": (_sz, [C.c_int, C.c_int]),
     "psg_mb_load_text": (C.c_int, [_p, _p, _sz, C.c_int, _sz, C.c_int, C.POINTER(TextResult)]),
     "psg_text_parse_host": (C.c_int, [_p, _sz, C.c_int, _sz, C.c_int, _p, _p, _p, _p, _sz, _sz,
                                       C.POINTER(TextResult)]),

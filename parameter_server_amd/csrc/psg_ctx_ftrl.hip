@@ -1,6 +1,7 @@
 // psg_ctx_ftrl.hip -- the FTRL model of a context (FTRLModel<uint64, double>:
 // psg_ftrl_*, include/psg.h) over the hash-table kernels of psg_ftrl.hip.
 #include "psg_ctx.h"
+#include "psg_score.h"
 
 extern "C" {
 
@@ -243,6 +244,19 @@ int psg_ftrl_pull_dev(psg_ctx* c, const uint64_t* keys, size_t n, double* out, v
   if (int rc = ftrl_order(F, (hipStream_t)stream)) return rc;
   HIP_TRY(psg::launch_ftrl_pull(F->table(), keys, n, out, (hipStream_t)stream));
   return ftrl_mark(c, F, (hipStream_t)stream);
+}
+
+int psg_ftrl_score_dev(psg_ctx* c, psg_minibatch* mb, int real, double* xw_dev, void* stream) {
+  if (!c || !mb) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrl* F;
+  if (int rc = ftrl_of(c, &F)) return rc;
+  if (int rc = set_dev(c->device)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (int rc = ftrl_order(F, s)) return rc;
+  const psg::FtrlTable T = F->table();
+  if (int rc = psg::mb_score(mb, c, &T, nullptr, real, xw_dev, s)) return rc;
+  return ftrl_mark(c, F, s);
 }
 
 int psg_ftrl_pull(psg_ctx* c, const uint64_t* keys, size_t n, double* out) {

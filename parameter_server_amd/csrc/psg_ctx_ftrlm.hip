@@ -4,6 +4,7 @@
 // allocates nothing and waits for nothing while the model has room, and a
 // rejected message is reported once by the next call that synchronises.
 #include "psg_ctx.h"
+#include "psg_score.h"
 
 extern "C" {
 
@@ -291,6 +292,19 @@ int psg_ftrlm_pull_dev(psg_ctx* c, const uint64_t* keys, size_t n, double* out, 
   if (int rc = ftrlm_order(F, (hipStream_t)stream)) return rc;
   HIP_TRY(psg::launch_ftrlm_pull(F->table(), keys, n, out, (hipStream_t)stream));
   return ftrlm_mark(c, F, (hipStream_t)stream);
+}
+
+int psg_ftrlm_score_dev(psg_ctx* c, psg_minibatch* mb, int real, double* xw_dev, void* stream) {
+  if (!c || !mb) return fail(PSG_ERR_ARG, "null argument");
+  std::lock_guard<std::mutex> l(c->mu);
+  Ftrlm* F;
+  if (int rc = ftrlm_of(c, &F)) return rc;
+  if (int rc = set_dev(c->device)) return rc;
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (int rc = ftrlm_order(F, s)) return rc;
+  const psg::FtrlmTable T = F->table();
+  if (int rc = psg::mb_score(mb, c, nullptr, &T, real, xw_dev, s)) return rc;
+  return ftrlm_mark(c, F, s);
 }
 
 int psg_ftrlm_pull(psg_ctx* c, const uint64_t* keys, size_t n, double* out) {

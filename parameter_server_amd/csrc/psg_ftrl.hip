@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psg_ftrl_find.h"
 #include "psg_internal.h"
 #include "psg_sort.h"
 
@@ -49,38 +50,6 @@ namespace {
 #define PSG_FTRL_ILP 1  // A/B builds: 2, 4, 8
 #endif
 constexpr int kFtrlIlp = PSG_FTRL_ILP;
-
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {  // MurmurHash3 finaliser
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
-
-__device__ __forceinline__ uint64_t key_load(const uint64_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The entry of `key` (!= 0), or null.  k0: the key words of bucket b, as
-// read earlier in this launch (they only ever change from 0).
-__device__ __forceinline__ const FtrlEntry* ftrl_find(const FtrlTable& T, uint64_t key, uint64_t b,
-                                                      const uint64_t k0[3]) {
-  for (int s = 0; s < 3; ++s) {
-    if (k0[s] == key) return &T.b[b].e[s];
-    if (k0[s] == 0) return nullptr;
-  }
-  for (uint64_t probe = 0; probe < T.mask; ++probe) {
-    b = (b + 1) & T.mask;
-    for (int s = 0; s < 3; ++s) {
-      const uint64_t k = T.b[b].e[s].key;
-      if (k == key) return &T.b[b].e[s];
-      if (k == 0) return nullptr;
-    }
-  }
-  return nullptr;
-}
 
 // The entry of `key` (!= 0), claimed if absent (*fresh); null only when every
 // slot of the table is taken by other keys.

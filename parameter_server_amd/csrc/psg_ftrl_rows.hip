@@ -25,39 +25,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "psg_ftrl_find.h"
 #include "psg_ftrl_rows.h"
 #include "psg_sort.h"
 
 namespace psg {
 
 namespace {
-
-__device__ __forceinline__ uint64_t fmix64(uint64_t k) {  // MurmurHash3 finaliser
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
-
-__device__ __forceinline__ uint64_t key_load(const uint64_t* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The row of `key`, or kFtrlmNoRow.  A slot whose row word is 0 was claimed
-// by a key that found no row (an overflow, already counted): absent.
-__device__ __forceinline__ uint64_t ftrlm_find(const FtrlmTable& T, uint64_t key) {
-  if (key == 0) return T.head->zero_present ? 0 : kFtrlmNoRow;
-  uint64_t b = fmix64(key) & T.mask;
-  for (uint64_t probe = 0; probe <= T.mask; ++probe) {
-    const FtrlmSlot s = T.idx[b];
-    if (s.key == key) return s.row != 0 && s.row < T.row_cap ? s.row : kFtrlmNoRow;
-    if (s.key == 0) return kFtrlmNoRow;
-    b = (b + 1) & T.mask;
-  }
-  return kFtrlmNoRow;
-}
 
 // The slot of `key` (!= 0), claimed if absent (*fresh); null only when every
 // slot of the index is taken by other keys.

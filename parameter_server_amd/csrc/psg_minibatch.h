@@ -30,6 +30,8 @@ enum BufId {
   // psg_worker_rows.hip: Xw, tau, c, loss [rows][m], the loss partials
   // [workgroups][m], the gradient [ndict][m], objv [m], the term rows [nnz][m]
   B_R_XW, B_R_TAU, B_R_C, B_R_LOSS, B_R_PARTIAL, B_R_GRAD, B_R_OBJV, B_R_TERM,
+  // psg_score.hip: the cut rows' terms [nnz][m] and presence words, the tiles' cut rows
+  B_SC_TERM, B_SC_MASK, B_SC_CUT,
   B_COUNT
 };
 
@@ -50,6 +52,7 @@ struct psg_minibatch : psg::DeviceBlocks<B_COUNT> {
   // (g): set by psg_mb_darling_init, cleared by psg_mb_load and psg_mb_localize
   bool darling = false;
   bool xw_own = false;  // psg_mb_times has run into the minibatch's own Xw (psg_mb_labels)
+  bool xw_scored = false;  // psg_ftrl_score_dev has, since the load: no localize is needed to read it
   // the m of the last psg_mb_gradient_rows since the load and the localize (0: none)
   int rows_m = 0;
   const uint32_t* row_pair = nullptr;  // the rows' lists (one side of their ping-pong)

@@ -761,6 +761,7 @@ int mb_load_begin(psg_minibatch* mb, size_t rows, size_t n, bool valued) {
   mb->state = S_NEW;
   mb->darling = false;
   mb->xw_own = false;
+  mb->xw_scored = false;
   mb->rows_m = 0;
   mb->has_slots = mb->groups_ok = false;
   mb_drop_sharing(mb);
@@ -1133,7 +1134,9 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
     case PSG_MB_NEW_VALUE: need_state = S_LOCAL; id = B_NEW_VALUE; n = kept_unknown; break;
     case PSG_MB_POS: need_state = S_LOCAL; id = B_CNT_POS; n = mb->ndict; break;
     case PSG_MB_NEG: need_state = S_LOCAL; id = B_CNT_NEG; n = mb->ndict; break;
-    case PSG_MB_XW: need_state = mb->xw_own ? S_LOCAL : S_GRAD; id = B_XW; n = mb->rows; break;
+    case PSG_MB_XW:
+      need_state = mb->xw_scored ? S_LOADED : mb->xw_own ? S_LOCAL : S_GRAD; id = B_XW;
+      n = mb->rows; break;
     case PSG_MB_TAU: need_state = S_GRAD; id = B_TAU; n = mb->rows; break;
     case PSG_MB_LOSS: need_state = S_GRAD; id = B_LOSS; n = mb->rows; break;
     case PSG_MB_GRAD: need_state = S_GRAD; id = B_GRAD; n = mb->ndict; break;

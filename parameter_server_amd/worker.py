@@ -97,6 +97,22 @@ def sort_tile() -> int:
     return int(_lib.lib().psg_mb_sort_tile())
 
 
+def _score_real(real) -> int:
+    """PSG_SCORE_F64 / PSG_SCORE_F32 of a numpy float type."""
+    dt = np.dtype(real)
+    if dt == np.float64:
+        return _lib.PSG_SCORE_F64
+    if dt == np.float32:
+        return _lib.PSG_SCORE_F32
+    raise _lib.PSGError(_lib.PSG_ERR_ARG, f"score: real {dt} is neither float64 nor float32")
+
+
+def score_tile(m: int = 0, real=np.float64) -> int:
+    """Entries per workgroup tile of the direct scorer for a sweep of ``m``
+    models (0: the scalar model) in ``real`` (psg_score_tile)."""
+    return int(_lib.lib().psg_score_tile(int(m), _score_real(real)))
+
+
 class Minibatch:
     """One worker minibatch (row-major CSR with global ids) on the device of
     context ``ctx`` (a ``psg_ctx`` handle of a PSG_F64 context)."""
@@ -398,6 +414,29 @@ class FTRLWorker(_TailFilteredWorker):
         self.dict_dev, self.w_dev, self.ndict = keys, w, n
         return xw
 
+    def score(self, offset, index, value, y, real=np.float64) -> int:
+        """``predict`` by the direct scorer (psg_ftrl_score_dev): one hash
+        probe per entry and each row's sum in the row's own order, in ``real``
+        (float64, or the reference's ``Real`` = float32, widened on store); no
+        sort, localize or dictionary.  An absent key is skipped where
+        ``predict`` adds ``+0.0 * v``: the same bits unless that ``v`` is an
+        infinity or a NaN.  Returns the device pointer of Xw[rows], also
+        ``mb.read("xw")``."""
+        self.mb.load(offset, index, value, y)
+        return self._score_loaded(real)
+
+    def score_text(self, text: bytes, fmt, max_rows=None, final: bool = True, real=np.float64):
+        """``score`` on the next minibatch of a text buffer: (the device
+        pointer of Xw, the bytes consumed)."""
+        r = self.mb.load_text(text, fmt, max_rows, final)
+        return self._score_loaded(real), int(r.consumed)
+
+    def _score_loaded(self, real) -> int:
+        mb = self.mb
+        _lib.check(self._L.psg_ftrl_score_dev(self._ctx, mb._h, _score_real(real), None,
+                                              mb.stream))
+        return mb.labels()[1]
+
     def step(self, offset, index, value, y, auc=None) -> Tuple[float, int]:
         """One minibatch: (its objv, its number of examples).  ``auc``: an
         ``AUC`` of this context that takes (y, Xw) of the minibatch before
@@ -553,13 +592,44 @@ class FTRLMultiWorker(_TailFilteredWorker):
         r = self.mb.load_text(text, fmt, max_rows, final)
         return self._predict_loaded(), int(r.consumed)
 
-    def exact_auc(self, offset, index, value, y) -> np.ndarray:
+    def _score_loaded(self, real) -> int:
+        """The device pointer of Xw[rows, m] of the loaded minibatch by the
+        direct scorer (psg_ftrlm_score_dev), on the minibatch's stream."""
+        mb = self.mb
+        xw = mb.scratch(self._FILTER, 8 * max(mb.rows, 1) * self.m)
+        _lib.check(self._L.psg_ftrlm_score_dev(self._ctx, mb._h, _score_real(real), xw,
+                                               mb.stream))
+        return xw
+
+    def _read_scored(self) -> np.ndarray:
+        mb = self.mb
+        return mb.read_scratch(self._FILTER, np.float64, mb.rows * self.m).reshape(-1, self.m).copy()
+
+    def score(self, offset, index, value, y, real=np.float64) -> np.ndarray:
+        """``predict`` by the direct scorer, as ``FTRLWorker.score``: Xw[rows,
+        m], column j bit for bit what ``FTRLWorker.score`` gives on a model
+        that holds column j's weights."""
+        self.mb.load(offset, index, value, y)
+        self._score_loaded(real)
+        return self._read_scored()
+
+    def score_text(self, text: bytes, fmt, max_rows=None, final: bool = True, real=np.float64):
+        r = self.mb.load_text(text, fmt, max_rows, final)
+        self._score_loaded(real)
+        return self._read_scored(), int(r.consumed)
+
+    def exact_auc(self, offset, index, value, y, direct: bool = False,
+                  real=np.float64) -> np.ndarray:
         """auc[m]: the exact rank AUC of every model on one minibatch, scored
-        as ``predict`` scores it (no filter insert, no push).  The minibatch's
-        device labels and Xw[rows, m] go straight to psg_auc_exact_rows_dev on
-        its stream: no prediction comes to the host."""
+        as ``predict`` scores it (no filter insert, no push) or, with
+        ``direct``, as ``score`` does in ``real``.  The minibatch's device
+        labels and Xw[rows, m] go straight to psg_auc_exact_rows_dev on its
+        stream: no prediction comes to the host."""
         mb = self.mb
         mb.load(offset, index, value, y)
+        if direct:
+            xw = self._score_loaded(real)
+            return exact_auc_rows_dev(self._ctx, mb.labels()[0], xw, mb.rows, self.m, mb.stream)
         _, w = self._pull(False)
         xw = mb.scratch(self._FILTER, 8 * max(mb.rows, 1) * self.m)
         mb.times_rows(w, self.m, xw)
@@ -594,7 +664,7 @@ class FTRLMultiWorker(_TailFilteredWorker):
 
 
 def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device: int = 0,
-                   real=np.float32):
+                   real=np.float32, score: str = "localize"):
     """ModelEvaluation::run (reference src/linear_method/model_evaluation.h):
     the ``key w`` model files loaded into a frozen model (``readFromFile``;
     ``real``: the reference's ``Real`` is float), the text walked minibatch by
@@ -602,9 +672,15 @@ def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device
     ``y`` and ``Xw`` of each appended (:44,59), then the exact AUC of all of
     them (:66).  Returns (auc, labels, predictions).
 
-    Defined deviation: a prediction is accumulated in double by the ordered
-    product (one row's terms in the row's order), where the reference adds
-    floats (``Real re``, :49-57)."""
+    Defined deviation (``score="localize"``, the default): a prediction is
+    accumulated in double by the ordered product (one row's terms in the
+    row's order), where the reference adds floats (``Real re``, :49-57).
+    ``score="direct"`` walks the text with ``score_text`` and accumulates in
+    ``real``: with ``real=np.float32`` that deviation no longer applies, every
+    prediction is the reference's float loop bit for bit (widened to double),
+    and with ``real=np.float64`` the predictions are the default's."""
+    if score not in ("localize", "direct"):
+        raise ValueError(f"score={score!r}: \"localize\" or \"direct\"")
     model = FTRLModel(device)
     wk = None
     try:
@@ -614,7 +690,10 @@ def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device
         labels, predictions = [], []
         at = 0
         while at < len(text):
-            _, consumed = wk.predict_text(text[at:], fmt, max_rows)
+            if score == "direct":
+                _, consumed = wk.score_text(text[at:], fmt, max_rows, real=real)
+            else:
+                _, consumed = wk.predict_text(text[at:], fmt, max_rows)
             if wk.mb.rows:
                 labels.append(wk.mb.read("y"))
                 predictions.append(wk.mb.read("xw"))
@@ -631,13 +710,17 @@ def evaluate_model(model_paths, text: bytes, fmt, max_rows: int = 100000, device
 
 
 def evaluate_models(model_paths_per_model, text: bytes, fmt, max_rows: int = 100000,
-                    device: int = 0, real=np.float32):
+                    device: int = 0, real=np.float32, score: str = "localize"):
     """``evaluate_model`` for a saved sweep in one pass over the text:
     ``model_paths_per_model[j]`` are model j's ``key w`` files, loaded into
     column j of one frozen ``FTRLMultiModel`` (``readFromFiles``); the text is
     walked with ``FTRLMultiWorker.predict_text`` and all columns are scored by
     ``exact_auc_rows``.  Returns (auc[m], labels, predictions[rows, m]); column
-    j is bit for bit what ``evaluate_model`` gives for model j's files."""
+    j is bit for bit what ``evaluate_model`` gives for model j's files, with
+    the same ``score`` (``"direct"``: ``FTRLMultiWorker.score_text``,
+    accumulating in ``real``)."""
+    if score not in ("localize", "direct"):
+        raise ValueError(f"score={score!r}: \"localize\" or \"direct\"")
     m = len(model_paths_per_model)
     model = FTRLMultiModel([dict(alpha=1.0, beta=1.0, lambda1=0.0, lambda2=0.0)] * m, device)
     wk = None
@@ -648,7 +731,10 @@ def evaluate_models(model_paths_per_model, text: bytes, fmt, max_rows: int = 100
         labels, predictions = [], []
         at = 0
         while at < len(text):
-            xw, consumed = wk.predict_text(text[at:], fmt, max_rows)
+            if score == "direct":
+                xw, consumed = wk.score_text(text[at:], fmt, max_rows, real=real)
+            else:
+                xw, consumed = wk.predict_text(text[at:], fmt, max_rows)
             if wk.mb.rows:
                 labels.append(wk.mb.read("y"))
                 predictions.append(xw)
