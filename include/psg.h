@@ -993,6 +993,36 @@ int psg_mb_rows_labels(psg_minibatch* mb, const double** y_dev, const double** x
 #define PSG_MB_ROWS_LOSS 2  /* double[rows * m] */
 #define PSG_MB_ROWS_GRAD 3  /* double[ndict * m] */
 int psg_mb_rows_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t* n);
+/* The order of the per-key (column) sums of psg_mb_trans_times,
+ * psg_mb_gradient, psg_mb_trans_times_rows, psg_mb_gradient_rows and
+ * psg_mb_darling_gradients.  PSG_SUM_REFERENCE (the default) is the
+ * reference's serial chain.  PSG_SUM_BLOCKED is B(t[0 .. L)) over the run's L
+ * terms in the reference's order, every + one IEEE add:
+ *   L <= 32:   ((+0.0 + t0) + t1) + ...  (the reference's sum);
+ *   L <= 4096: 64 partials p_j = ((+0.0 + t[j]) + t[j + 64]) + ... (+0.0 with
+ *              no term), then for d = 32, 16, 8, 4, 2, 1: p_j = p_j + p_{j+d}
+ *              for j < d, the lower index on the left; the result is p_0;
+ *   L > 4096:  q_k = B(t[4096 k .. min(4096 (k + 1), L))), the result B(q).
+ * Segments count from the run's first term: B is a function of the run alone,
+ * the same bits whatever the minibatch around it.  An empty or absent column
+ * stays +0.0, an inactive Darling column the all-ones NaN.  The order belongs
+ * to the handle: legal in any state, kept across loads, in force from the next
+ * product call; an unknown value is PSG_ERR_ARG.  psg_mb_times, the dual
+ * update and the scoring entries do not read it.
+ * Defined deviation: in PSG_SUM_BLOCKED the sum of a run of more than 32
+ * terms is not the reference's (sparse_matrix.h:88-104, darling.cc:341-351)
+ * but B of the same terms: within gamma_{70 levels + 1} * sum |t| of the exact
+ * sum (levels = 1, 2, 3 for L <= 4096, 4096^2, 2^32), where the serial
+ * chain's bound is gamma_L.  A wave adds 64 partials side by side instead of
+ * one chain, and a run past 4096 terms is spread over one wave per segment. */
+#define PSG_SUM_REFERENCE 0
+#define PSG_SUM_BLOCKED 1
+int psg_mb_set_sum_order(psg_minibatch* mb, int order);
+int psg_mb_sum_order(psg_minibatch* mb, int* order);
+/* B of t[0], t[stride], ..., t[(n - 1) * stride] on the host (stride: one
+ * column of a row or pair array), for tests and callers that restate a
+ * blocked sum.  No HIP call.  PSG_ERR_ARG: a null argument, stride == 0. */
+int psg_sum_blocked_host(const double* t, size_t n, size_t stride, double* out);
 /* Tests and checkpoints: one internal array to the host, after a wait.  *n =
  * its element count; PSG_ERR_SIZE (nothing copied) if cap_bytes is short. */
 #define PSG_MB_SORTED_KEY 0  /* uint64[nnz]: the sorted pairs' keys */
@@ -1420,6 +1450,8 @@ int psg_mb_darling_set_state(psg_minibatch* mb, const double* dual, const double
 #define PSG_MB_DARLING_DELTA 34    /* double[ndict] */
 #define PSG_MB_DARLING_ACTIVE 35   /* uint8[ndict], 0 / 1 */
 #define PSG_MB_DARLING_DELTA_W 36  /* double[ce - cb] of the last psg_mb_darling_update_dual */
+#define PSG_MB_DARLING_TERMS 37    /* double[2 * nnz]: the (G, U) terms of every sorted pair; those of
+                                    * the last psg_mb_darling_gradients' active columns are written */
 /* One dual for the feature groups of a worker: in the reference dual_ is one
  * vector over the rows, created once (batch_solver.cc:344-349) and updated by
  * every group's updateDual (darling.cc:358-435).  After this call, made

@@ -65,6 +65,9 @@ MAX_VALUE_ARRAYS = 4
 MB_STAGES = ("sort", "run_length", "localize", "count_keys", "times", "logit", "trans_times")
 # psg_mb_gradient's loss and psg_mb_read's arrays
 PSG_LOSS_LOGIT = 0
+PSG_SUM_REFERENCE = 0
+PSG_SUM_BLOCKED = 1
+SUM_ORDERS = ("reference", "blocked")  # psg_mb_set_sum_order, by PSG_SUM_* value
 PSG_SCORE_F64, PSG_SCORE_F32 = 0, 1
 (PSG_MB_SORTED_KEY, PSG_MB_SORTED_POS, PSG_MB_UNIQ_KEY, PSG_MB_KEY_CNT, PSG_MB_NEW_OFFSET,
  PSG_MB_NEW_INDEX, PSG_MB_NEW_VALUE, PSG_MB_POS, PSG_MB_NEG, PSG_MB_XW, PSG_MB_TAU, PSG_MB_LOSS,
@@ -77,6 +80,7 @@ PSG_AUC_BY_KEY, PSG_AUC_AS_WRITTEN = 0, 1
 # ... and the Darling worker's state (psg_mb_darling_*)
 (PSG_MB_DARLING_DUAL, PSG_MB_DARLING_CUR_W, PSG_MB_DARLING_DELTA, PSG_MB_DARLING_ACTIVE,
  PSG_MB_DARLING_DELTA_W) = range(32, 37)
+PSG_MB_DARLING_TERMS = 37
 # ... and the loaded CSR
 PSG_MB_OFFSET, PSG_MB_INDEX, PSG_MB_VALUE, PSG_MB_Y = range(24, 28)
 # psg_mb_load_text's formats (DataConfig's values)
@@ -323,6 +327,9 @@ SIGNATURES = {
     "psg_mb_trans_times_rows": (C.c_int, [_p, _p, C.c_int, _p, _p]),
     "psg_mb_gradient_rows": (C.c_int, [_p, C.c_int, _p, C.c_int, C.POINTER(_p), _p, _p]),
     "psg_mb_rows_read": (C.c_int, [_p, C.c_int, _p, _sz, _psz]),
+    "psg_mb_set_sum_order": (C.c_int, [_p, C.c_int]),
+    "psg_mb_sum_order": (C.c_int, [_p, C.POINTER(C.c_int)]),
+    "psg_sum_blocked_host": (C.c_int, [_p, _sz, _sz, C.POINTER(C.c_double)]),
     "psg_mb_read": (C.c_int, [_p, C.c_int, _p, _sz, _psz]),
     "psg_mb_scratch": (C.c_int, [_p, C.c_int, _sz, C.POINTER(_p)]),
     "psg_mb_profile": (C.c_int, [_p, C.c_int]),

@@ -32,6 +32,9 @@ enum BufId {
   B_R_XW, B_R_TAU, B_R_C, B_R_LOSS, B_R_PARTIAL, B_R_GRAD, B_R_OBJV, B_R_TERM,
   // psg_score.hip: the cut rows' terms [nnz][m] and presence words, the tiles' cut rows
   B_SC_TERM, B_SC_MASK, B_SC_CUT,
+  // psg_colsum.hip: the control word, the huge runs' keys and first units, the
+  // units' runs at level 1 and 2, the units' partials at level 1 and 2
+  B_CS_CTL, B_CS_HKEY, B_CS_HBASE, B_CS_UNIT1, B_CS_UNIT2, B_CS_Q1, B_CS_Q2,
   B_COUNT
 };
 
@@ -55,6 +58,10 @@ struct psg_minibatch : psg::DeviceBlocks<B_COUNT> {
   bool xw_scored = false;  // psg_ftrl_score_dev has, since the load: no localize is needed to read it
   // the m of the last psg_mb_gradient_rows since the load and the localize (0: none)
   int rows_m = 0;
+  // psg_mb_set_sum_order, kept across loads; the huge runs' table of
+  // psg_colsum.hip has been built since the last psg_mb_localize
+  int sum_order = PSG_SUM_REFERENCE;
+  bool cs_ready = false;
   const uint32_t* row_pair = nullptr;  // the rows' lists (one side of their ping-pong)
   // host: pair_lo[k] = the first sorted pair of the first of keys k, k + 1, ...
   // that has a run (nnz: none); pair_hi[k] = the end of the last run among

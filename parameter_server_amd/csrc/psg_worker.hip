@@ -69,6 +69,7 @@
 
 #include "../../include/psg.h"
 #include "psg_blocks.h"
+#include "psg_colsum.h"
 #include "psg_device.h"
 #include "psg_host.h"
 #include "psg_internal.h"
@@ -958,8 +959,11 @@ int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
   }
   mb->tick(PSG_MB_STAGE_COUNT_KEYS, 1, s);
   if (int rc = launched("localize")) return rc;
-  if (int rc = mb->mark(s)) return rc;
   mb->ndict = ndict;
+  mb->cs_ready = false;  // the blocked order's table of huge runs: now, or at its first use
+  if (mb->sum_order == PSG_SUM_BLOCKED)
+    if (int rc = colsum_prepare(mb, s)) return rc;
+  if (int rc = mb->mark(s)) return rc;
   mb->state = S_LOCAL;
   if (pos_dev) *pos_dev = mb->at<uint32_t>(B_CNT_POS);
   if (neg_dev) *neg_dev = mb->at<uint32_t>(B_CNT_NEG);
@@ -984,11 +988,15 @@ int enqueue_trans_times(psg_minibatch* mb, const double* c, double* g, hipStream
              mb->binary ? nullptr : mb->at<double>(B_VALUE), c, n, mb->at<double>(B_TERM));
     LAUNCH(trans_times_short_kernel, blocks_of(nd, 256), s, mb->at<uint32_t>(B_DICT_RUN), nd,
            mb->at<uint32_t>(B_RUN_START), nu, n, mb->at<double>(B_TERM), g);
-    if (n)
+    if (n && mb->sum_order == PSG_SUM_BLOCKED) {
+      if (int rc = colsum_enqueue(mb, mb->at<double>(B_TERM), 1, g, nullptr, 0, nd, nullptr, nd, s))
+        return rc;
+    } else if (n) {
       LAUNCH(trans_times_long_kernel, std::min<uint32_t>(blocks_of(nd, 4), kLongGrid), s,
              mb->at<uint32_t>(B_LONG_LIST), (const uint32_t*)(mb->d_small + 5),
              mb->at<uint32_t>(B_DICT_RUN), nd, mb->at<uint32_t>(B_RUN_START), nu, n,
              mb->at<double>(B_TERM), g);
+    }
   }
   return launched("trans_times");
 }
@@ -1151,6 +1159,7 @@ int psg_mb_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t
     case PSG_MB_DARLING_DELTA_W:
       need_state = S_LOCAL; id = B_DELTA_W; n = mb->last_ce - mb->last_cb; first = mb->last_cb;
       break;
+    case PSG_MB_DARLING_TERMS: need_state = S_LOCAL; id = B_TERM2; n = 2 * mb->nnz; break;
     default: return fail(PSG_ERR_ARG, "psg_mb_read: array %d", what);
   }
   if (what >= PSG_MB_DARLING_DUAL && (!mb->darling || (mb->dual_owner && !mb->dual_owner->darling)))
@@ -1370,7 +1379,10 @@ int psg_mb_darling_gradients(psg_minibatch* mb, size_t cb, size_t ce, double* g_
   }
   LAUNCH(darling_sum_short_kernel, blocks_of(e - b, 256), s, mb->at<uint32_t>(B_DICT_RUN), nd,
          mb->at<uint32_t>(B_RUN_START), nu, n, active, b, e, term, g_dev, u_dev);
-  if (hi - lo > kLongRun && mb->n_long)
+  if (hi - lo > kLongRun && mb->n_long && mb->sum_order == PSG_SUM_BLOCKED) {
+    if (int rc = colsum_enqueue(mb, (const double*)term, 2, g_dev, u_dev, b, e, active, mb->n_long, s))
+      return rc;
+  } else if (hi - lo > kLongRun && mb->n_long)
     LAUNCH(darling_sum_long_kernel, std::min<uint32_t>(blocks_of(mb->n_long, 4), kLongGrid), s,
            mb->at<uint32_t>(B_LONG_LIST), (const uint32_t*)(mb->d_small + 5),
            mb->at<uint32_t>(B_DICT_RUN), nd, mb->at<uint32_t>(B_RUN_START), nu, n, active, b, e,

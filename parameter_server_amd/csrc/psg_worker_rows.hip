@@ -30,6 +30,7 @@
 
 #include "../../include/psg.h"
 #include "psg_blocks.h"
+#include "psg_colsum.h"
 #include "psg_device.h"
 #include "psg_ftrl_rows.h"
 #include "psg_host.h"
@@ -303,7 +304,9 @@ int enqueue_trans_times_rows(psg_minibatch* mb, const double* c, int m, double* 
     if (n) LAUNCH(terms_rows_kernel, blocks_of(n, 256u >> gs), s, P, c, (uint32_t)m, gs, term);
     LAUNCH(trans_rows_short_kernel, blocks_of(nd, 256u >> gs), s, mb->at<uint32_t>(B_DICT_RUN), nd,
            mb->at<uint32_t>(B_RUN_START), nu, n, term, (uint32_t)m, gs, g);
-    if (n)
+    if (n && mb->sum_order == PSG_SUM_BLOCKED) {
+      if (int rc = colsum_enqueue(mb, term, m, g, nullptr, 0, nd, nullptr, nd, s)) return rc;
+    } else if (n)
       LAUNCH(trans_rows_long_kernel, std::min<uint32_t>(blocks_of(nd, 4), kLongGrid), s,
              mb->at<uint32_t>(B_LONG_LIST), (const uint32_t*)(mb->d_small + 5),
              mb->at<uint32_t>(B_DICT_RUN), nd, mb->at<uint32_t>(B_RUN_START), nu, n, term,

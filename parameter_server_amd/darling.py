@@ -54,13 +54,15 @@ class DarlingWorker:
     _GU = 0           # scratch slot of the minibatch: (G, U) of a block
     _PULL = 1         # ... and the block's pulled weights (device forms)
 
-    def __init__(self, ctx, delta_init: float, delta_max: float, device: int = 0):
+    def __init__(self, ctx, delta_init: float, delta_max: float, device: int = 0,
+                 sum_order: str = "reference"):
         self._L = _lib.lib()
         self._ctx = ctx
         self.device = device
         self.delta_init = float(delta_init)
         self.delta_max = float(delta_max)
         self.mb = Minibatch(ctx)
+        self.mb.set_sum_order(sum_order)  # the order of G and U (psg_mb_set_sum_order)
         self._dev = {}
         self.dict_keys = np.zeros(0, np.uint64)
         self.ndict = 0

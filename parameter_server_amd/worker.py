@@ -130,6 +130,20 @@ class Minibatch:
         self.pos_dev = self.neg_dev = self.grad_dev = None
         self.grad_rows_dev, self.rows_m = None, 1
 
+    def set_sum_order(self, order: str) -> None:
+        """psg_mb_set_sum_order: ``"reference"`` (the serial chain, the
+        default) or ``"blocked"`` (``B`` of include/psg.h) for the per-key sums
+        of the product calls from the next one on."""
+        if order not in _lib.SUM_ORDERS:
+            raise ValueError(f"sum order {order!r}: one of {_lib.SUM_ORDERS}")
+        _lib.check(self._L.psg_mb_set_sum_order(self._h, _lib.SUM_ORDERS.index(order)))
+
+    @property
+    def sum_order(self) -> str:
+        o = C.c_int()
+        _lib.check(self._L.psg_mb_sum_order(self._h, C.byref(o)))
+        return _lib.SUM_ORDERS[o.value]
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.psg_mb_destroy(self._h)
@@ -350,7 +364,8 @@ class _TailFilteredWorker:
         the tail filter on its threshold and the CountMin table with its ``n``
         and ``k``."""
         extra = dict(objv=np.array(self.objv, np.float64), num_ex=np.array(self.num_ex, np.int64),
-                     tail_feature_freq=np.array(self.freq, np.int64))
+                     tail_feature_freq=np.array(self.freq, np.int64),
+                     sum_order=np.array(_lib.SUM_ORDERS.index(self.mb.sum_order), np.int64))
         if self.freq > 0:
             extra.update(countmin_n=np.array(self.countmin_n, np.int64),
                          countmin_k=np.array(self.countmin_k, np.int64),
@@ -367,7 +382,7 @@ class FTRLWorker(_TailFilteredWorker):
     counters and ``countmin_k`` probes on channel ``chl`` of the context."""
 
     def __init__(self, model: FTRLModel, tail_feature_freq: int = 0, countmin_n: int = 1 << 20,
-                 countmin_k: int = 2, chl: int = 0):
+                 countmin_k: int = 2, chl: int = 0, sum_order: str = "reference"):
         self._L = _lib.lib()
         self.model = model
         self._ctx = model._model()
@@ -379,6 +394,7 @@ class FTRLWorker(_TailFilteredWorker):
         if self.freq > 0:
             _lib.check(self._L.psg_freq_resize(self._ctx, chl, countmin_n, countmin_k))
         self.mb = Minibatch(self._ctx)
+        self.mb.set_sum_order(sum_order)
         self.objv = 0.0   # status_.objv
         self.num_ex = 0   # status_.num_ex
         self.ndict = 0
@@ -492,13 +508,14 @@ class FTRLWorker(_TailFilteredWorker):
         if "tail_feature_freq" not in st:
             raise ValueError(f"{path}: a model image without a worker's state")
         freq = int(st["tail_feature_freq"])
+        order = _lib.SUM_ORDERS[int(st["sum_order"])] if "sum_order" in st else "reference"
         model = FTRLModel.from_state(st, device)
         if freq > 0:
-            wk = cls(model, freq, int(st["countmin_n"]), int(st["countmin_k"]), chl)
+            wk = cls(model, freq, int(st["countmin_n"]), int(st["countmin_k"]), chl, order)
             table = np.ascontiguousarray(st["countmin_table"], dtype=np.uint8)
             _lib.check(wk._L.psg_freq_table_assign(wk._ctx, chl, _ptr(table), table.size))
         else:
-            wk = cls(model, chl=chl)
+            wk = cls(model, chl=chl, sum_order=order)
         wk.objv = float(st["objv"])
         wk.num_ex = int(st["num_ex"])
         return wk
@@ -518,7 +535,8 @@ class FTRLMultiWorker(_TailFilteredWorker):
     hook keeps for one model."""
 
     def __init__(self, model: FTRLMultiModel, tail_feature_freq: int = 0,
-                 countmin_n: int = 1 << 20, countmin_k: int = 2, chl: int = 0):
+                 countmin_n: int = 1 << 20, countmin_k: int = 2, chl: int = 0,
+                 sum_order: str = "reference"):
         self._L = _lib.lib()
         self.model, self.m = model, model.m
         self._ctx = model._model()
@@ -530,6 +548,7 @@ class FTRLMultiWorker(_TailFilteredWorker):
         if self.freq > 0:
             _lib.check(self._L.psg_freq_resize(self._ctx, chl, countmin_n, countmin_k))
         self.mb = Minibatch(self._ctx)
+        self.mb.set_sum_order(sum_order)
         self.objv = np.zeros(self.m, np.float64)  # status_.objv per model
         self.num_ex = 0
         self.ndict = 0
@@ -651,13 +670,14 @@ class FTRLMultiWorker(_TailFilteredWorker):
         if "tail_feature_freq" not in st:
             raise ValueError(f"{path}: a multi-model image without a worker's state")
         freq = int(st["tail_feature_freq"])
+        order = _lib.SUM_ORDERS[int(st["sum_order"])] if "sum_order" in st else "reference"
         model = FTRLMultiModel.from_state(st, device)
         if freq > 0:
-            wk = cls(model, freq, int(st["countmin_n"]), int(st["countmin_k"]), chl)
+            wk = cls(model, freq, int(st["countmin_n"]), int(st["countmin_k"]), chl, order)
             table = np.ascontiguousarray(st["countmin_table"], dtype=np.uint8)
             _lib.check(wk._L.psg_freq_table_assign(wk._ctx, chl, _ptr(table), table.size))
         else:
-            wk = cls(model, chl=chl)
+            wk = cls(model, chl=chl, sum_order=order)
         wk.objv = np.array(st["objv"], np.float64)
         wk.num_ex = int(st["num_ex"])
         return wk

@@ -49,6 +49,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sum-order", default="reference",
+                    help="reference, blocked, or a comma list of rounds measured one after the "
+                         "other in this process (an A/B: reference,blocked,reference,blocked)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "darling_worker.json"))
     a = ap.parse_args()
 
@@ -118,11 +121,23 @@ def main():
         for cb, ce in blocks:
             update(cb, ce, (i + 1) % 2)
 
-    init_ms = timed(lambda i: init(), a.steps, a.warmup)
-    pass_ms = timed(whole, a.steps, a.warmup)
-    g_ms = timed(only_g, a.steps, a.warmup)
-    u_ms = timed(only_u, a.steps, a.warmup)
-    one_ms = timed(lambda i: gradients(longest, longest + 1), a.steps, a.warmup)
+    def measure(order):
+        mb.set_sum_order(order)
+        init_ms = timed(lambda i: init(), a.steps, a.warmup)
+        pass_ms = timed(whole, a.steps, a.warmup)
+        g_ms = timed(only_g, a.steps, a.warmup)
+        u_ms = timed(only_u, a.steps, a.warmup)
+        one_ms = timed(lambda i: gradients(longest, longest + 1), a.steps, a.warmup)
+        return {"sum_order": order, "init_ms": init_ms[0], "init_ms_min": init_ms[1],
+                "pass_ms": pass_ms[0], "pass_ms_min": pass_ms[1],
+                "gradients_ms": g_ms[0], "gradients_ms_min": g_ms[1],
+                "update_dual_ms": u_ms[0], "update_dual_ms_min": u_ms[1],
+                "pairs_per_s_pass": nnz / (pass_ms[0] * 1e-3),
+                "longest_column": {"entries_share": float(counts.max() / nnz),
+                                   "gradients_ms": one_ms[0],
+                                   "share_of_gradients_ms": one_ms[0] / g_ms[0]}}
+
+    rounds = [measure(o) for o in a.sum_order.split(",")]
     objv = C.c_double()
     _lib.check(L.psg_mb_darling_objv(mb._h, C.byref(objv), None))
     out = {
@@ -134,17 +149,16 @@ def main():
                      "median_column": float(np.median(counts)), "seed": a.seed},
         "method": {"steps": a.steps, "warmup": a.warmup,
                    "timer": "host clock around enqueue + device wait", "figure": "median"},
-        "init_ms": init_ms[0], "init_ms_min": init_ms[1],
-        "pass_ms": pass_ms[0], "pass_ms_min": pass_ms[1],
-        "gradients_ms": g_ms[0], "gradients_ms_min": g_ms[1],
-        "update_dual_ms": u_ms[0], "update_dual_ms_min": u_ms[1],
-        "pairs_per_s_pass": nnz / (pass_ms[0] * 1e-3),
-        "longest_column": {"entries_share": float(counts.max() / nnz),
-                           "gradients_ms": one_ms[0],
-                           "share_of_gradients_ms": one_ms[0] / g_ms[0]},
+        **rounds[0],
         "last_objv": objv.value,
         "lib": os.path.basename(_lib.LIB_PATH),
     }
+    if len(rounds) > 1:  # an A/B: every round, and blocked over reference by the rounds' medians
+        out["rounds"] = rounds
+        med = {o: {k: float(np.median([r[k] for r in rounds if r["sum_order"] == o]))
+                   for k in ("pass_ms", "gradients_ms")} for o in ("reference", "blocked")}
+        out["blocked_over_reference"] = {k: med["blocked"][k] / med["reference"][k]
+                                         for k in ("pass_ms", "gradients_ms")}
     mb.close()
     L.psg_destroy(ctx)
     line = json.dumps(out)

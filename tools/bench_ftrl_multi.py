@@ -85,6 +85,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sum-order", default="reference",
+                    help="reference, blocked, or a comma list of worker rounds measured one after "
+                         "the other (an A/B: reference,blocked,reference,blocked); both the row "
+                         "and the scalar worker take the round's order")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ftrl_multi.json"))
     a = ap.parse_args()
 
@@ -179,37 +183,46 @@ def main():
         w = torch.randn(ndict * m, dtype=torch.float64, device="cuda:0") * 0.01
         w_cols = w.view(ndict, m).t().contiguous()  # column j alone, for the scalar calls
         torch.cuda.synchronize()
-        mb.profile(True)
-        t = {s: ([], []) for s in STAGES}
-        for r in range(rounds):
-            mb.gradient_rows(w.data_ptr(), m)
-            rows_ms = mb.stage_ms()
-            scalar_ms = dict.fromkeys(STAGES, 0.0)
-            for j in range(m):
-                mb.gradient(w_cols.data_ptr() + 8 * ndict * j)
-                ms = mb.stage_ms()
-                for s in STAGES:
-                    scalar_ms[s] += ms[s]
-            if r >= a.warmup:
-                for s in STAGES:
-                    t[s][0].append(rows_ms[s])
-                    t[s][1].append(scalar_ms[s])
-        mb.profile(False)
-        for s, (rows_ms, scalar_ms) in t.items():
-            res[s] = compare(rows_ms, scalar_ms)
-        # -- the whole step, host clock -----------------------------------------
-        rows_ms, scalar_ms = [], []
-        for r in range(rounds):
-            t0 = time.perf_counter()
-            worker.step(*batch)
-            t1 = time.perf_counter()
-            for _ in range(m):
-                sworker.step(*batch)
-            t2 = time.perf_counter()
-            if r >= a.warmup:
-                rows_ms.append((t1 - t0) * 1e3)
-                scalar_ms.append((t2 - t1) * 1e3)
-        res["step"] = compare(rows_ms, scalar_ms)
+        orders = a.sum_order.split(",")
+        for order in orders:
+            mb.set_sum_order(order)
+            sworker.mb.set_sum_order(order)
+            wres = {"sum_order": order}
+            mb.profile(True)
+            t = {s: ([], []) for s in STAGES}
+            for r in range(rounds):
+                mb.gradient_rows(w.data_ptr(), m)
+                rows_ms = mb.stage_ms()
+                scalar_ms = dict.fromkeys(STAGES, 0.0)
+                for j in range(m):
+                    mb.gradient(w_cols.data_ptr() + 8 * ndict * j)
+                    ms = mb.stage_ms()
+                    for s in STAGES:
+                        scalar_ms[s] += ms[s]
+                if r >= a.warmup:
+                    for s in STAGES:
+                        t[s][0].append(rows_ms[s])
+                        t[s][1].append(scalar_ms[s])
+            mb.profile(False)
+            for s, (rows_ms, scalar_ms) in t.items():
+                wres[s] = compare(rows_ms, scalar_ms)
+            # -- the whole step, host clock -----------------------------------------
+            rows_ms, scalar_ms = [], []
+            for r in range(rounds):
+                t0 = time.perf_counter()
+                worker.step(*batch)
+                t1 = time.perf_counter()
+                for _ in range(m):
+                    sworker.step(*batch)
+                t2 = time.perf_counter()
+                if r >= a.warmup:
+                    rows_ms.append((t1 - t0) * 1e3)
+                    scalar_ms.append((t2 - t1) * 1e3)
+            wres["step"] = compare(rows_ms, scalar_ms)
+            if order is orders[0]:
+                res.update(wres)
+            if len(orders) > 1:
+                res.setdefault("rounds", []).append(wres)
         res["ndict"] = int(ndict)
         worker.close()
         wmulti.close()

@@ -60,6 +60,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--sum-order", default="reference",
+                    help="reference, blocked, or a comma list of rounds measured one after the "
+                         "other in this process (an A/B: reference,blocked,reference,blocked)")
+    ap.add_argument("--out", default=None, help="also write the result line to this file")
     ap.add_argument("--ceiling-from", default=os.path.join(ROOT, "profiles", "r06_bench.json"))
     a = ap.parse_args()
 
@@ -86,22 +90,33 @@ def main():
     for i in range(a.warmup):  # untimed: every shape, the model's growth, code objects
         worker.step(*batches[i % a.batches])
     worker.mb.profile(True)
-    stages = {s: [] for s in _lib.MB_STAGES}
-    step_ms, load_ms, objv = [], [], 0.0
-    for i in range(a.steps):
-        off, idx, val, y = batches[i % a.batches]
-        t0 = time.perf_counter()
-        worker.mb.load(off, idx, val, y)
-        t1 = time.perf_counter()
-        load_ms.append((t1 - t0) * 1e3)
-        t0 = time.perf_counter()
-        objv, _ = worker.step(off, idx, val, y)
-        ms = worker.mb.stage_ms()  # waits for the push as well
-        step_ms.append((time.perf_counter() - t0) * 1e3)
-        for s, v in ms.items():
-            stages[s].append(v)
-    med = {s: float(np.median(v)) for s, v in stages.items()}
-    lo = {s: float(np.min(v)) for s, v in stages.items()}
+
+    def measure(order):
+        worker.mb.set_sum_order(order)
+        stages = {s: [] for s in _lib.MB_STAGES}
+        step_ms, load_ms, objv = [], [], 0.0
+        for i in range(a.steps):
+            off, idx, val, y = batches[i % a.batches]
+            t0 = time.perf_counter()
+            worker.mb.load(off, idx, val, y)
+            t1 = time.perf_counter()
+            load_ms.append((t1 - t0) * 1e3)
+            t0 = time.perf_counter()
+            objv, _ = worker.step(off, idx, val, y)
+            ms = worker.mb.stage_ms()  # waits for the push as well
+            step_ms.append((time.perf_counter() - t0) * 1e3)
+            for s, v in ms.items():
+                stages[s].append(v)
+        med = {s: float(np.median(v)) for s, v in stages.items()}
+        return {"sum_order": order, "stage_ms_median": med,
+                "stage_ms_min": {s: float(np.min(v)) for s, v in stages.items()},
+                "device_ms_sum_of_stages": float(sum(med.values())),
+                "load_ms_median": float(np.median(load_ms)),
+                "step_ms_median": float(np.median(step_ms)),
+                "step_ms_min": float(np.min(step_ms)), "last_objv": objv}
+
+    rounds = [measure(o) for o in a.sum_order.split(",")]
+    med = rounds[0]["stage_ms_median"]
     sort_bytes = passes * 32 * nnz - (4 * nnz if passes else 0)
     ceiling = None
     try:
@@ -126,18 +141,27 @@ def main():
                  "fraction_of_copy_ceiling": (sort_gbps / ceiling
                                               if sort_gbps and ceiling else None),
                  "pairs_per_s": nnz / (med["sort"] * 1e-3) if med["sort"] > 0 else None},
-        "stage_ms_median": med,
-        "stage_ms_min": lo,
-        "device_ms_sum_of_stages": float(sum(med.values())),
-        "load_ms_median": float(np.median(load_ms)),
-        "step_ms_median": float(np.median(step_ms)),
-        "step_ms_min": float(np.min(step_ms)),
-        "last_objv": objv,
+        **rounds[0],
         "lib": os.path.basename(_lib.LIB_PATH),
     }
+    if len(rounds) > 1:  # an A/B: every round, and blocked over reference by the rounds' medians
+        out["rounds"] = rounds
+        pick = {"trans_times_ms": lambda r: r["stage_ms_median"]["trans_times"],
+                "device_ms": lambda r: r["device_ms_sum_of_stages"],
+                "step_ms": lambda r: r["step_ms_median"]}
+        by = {o: {k: [f(r) for r in rounds if r["sum_order"] == o] for k, f in pick.items()}
+              for o in ("reference", "blocked")}
+        out["ab"] = {o: {k: {"median": float(np.median(v)), "min": min(v), "max": max(v)}
+                         for k, v in by[o].items()} for o in by}
+        out["blocked_over_reference"] = {k: out["ab"]["blocked"][k]["median"] /
+                                         out["ab"]["reference"][k]["median"] for k in pick}
     worker.close()
     model.close()
-    print(json.dumps(out))
+    line = json.dumps(out)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
 
 
 if __name__ == "__main__":
