@@ -1475,6 +1475,86 @@ int psg_mb_darling_set_state(psg_minibatch* mb, const double* dual, const double
 int psg_mb_darling_share_dual(psg_minibatch* mb, psg_minibatch* owner);
 
 /* ------------------------------------------------------------------ */
+/* The batch worker step for m models at once: a regularisation path   */
+/* over one resident minibatch (darling.cc:196-250 per model)          */
+/* ------------------------------------------------------------------ */
+/* 1 <= m <= PSG_DARLING_MAX_MODELS models (settings) over one localized
+ * minibatch.  The column runs, the rows' lists and the values do not depend
+ * on the model and are shared; dual[rows][m], cur_w / delta / delta_w
+ * [ndict][m] are row-major with model j at [i * m + j], and the active set is
+ * one uint32 per key whose bit j is model j's.  Column j of every output is
+ * bit for bit what psg_mb_darling_* gives for model j alone from the same
+ * state: every operator of darling.cc:338-350, 364-378, 432, 506 is one
+ * rounded operation in the order written, on one accumulator per (key, model)
+ * or (row, model), with the exp / log the scalar kernels call.  tau = 1 / (1 +
+ * dual) (:342), y tau and tau (1 - tau) are computed once per (row, model) and
+ * call, not once per entry: the same operations on the same operands.
+ * The rows state and the scalar state of one minibatch are independent (each
+ * has its own arrays; both read the rows' lists, which either init builds).
+ * Validity as the scalar block: every call needs psg_mb_darling_rows_init
+ * after psg_mb_localize, psg_mb_load and psg_mb_localize invalidate the state,
+ * m outside 1 .. PSG_DARLING_MAX_MODELS, cb > ce or ce > ndict is PSG_ERR_ARG.
+ * Defined deviations: the scalar block's (the device's exp / log, the
+ * fixed-order objv, absent keys, empty rows), and the active set as a mask
+ * word per key where the scalar block keeps a byte and the reference a
+ * Bitmap.  A shared dual across feature groups is not built for this state. */
+#define PSG_DARLING_MAX_MODELS 32
+/* preprocessData (:110-117) per model: w_dev is [ndict][m] (NULL: zero, every
+ * dual exactly 1.0), dual = exp(y .* (Z * w)) by psg_mb_times_rows, delta =
+ * delta_init, every bit below m set.  Builds the rows' lists and reads the
+ * columns' ranges like psg_mb_darling_init: synchronises. */
+int psg_mb_darling_rows_init(psg_minibatch* mb, int m, double delta_init, const double* w_dev,
+                             void* stream);
+/* kkt_filter_reset (:167-169) for every model.  Enqueues only. */
+int psg_mb_darling_rows_reset_active(psg_minibatch* mb, void* stream);
+/* computeGradients (:306-356) over columns [cb, ce): g_dev / u_dev are
+ * [ce - cb][m].  An inactive (key, model) gets the all-ones NaN in both
+ * (:334).  Scratch: 16 m (hi - lo) bytes for the terms of the block's sorted
+ * pairs [lo, hi), 16 m rows for the per-row table.  Enqueues only. */
+int psg_mb_darling_rows_gradients(psg_minibatch* mb, size_t cb, size_t ce, double* g_dev,
+                                  double* u_dev, void* stream);
+/* updateDual (:358-435): new_w_dev is [ce - cb][m], delta_max a host array of
+ * m (newDelta, darling.h:31-33).  A NaN weight clears (key, model)'s bit and
+ * zeroes its cur_w (:366-371); a row that no live factor of model j touches
+ * keeps dual[row][j]'s bits.  Enqueues only. */
+int psg_mb_darling_rows_update_dual(psg_minibatch* mb, size_t cb, size_t ce,
+                                    const double* new_w_dev, const double* delta_max,
+                                    void* stream);
+/* evaluateProgress (:506) per model: objv[m] on the host; synchronises. */
+int psg_mb_darling_rows_objv(psg_minibatch* mb, double* objv, void* stream);
+/* Tests and checkpoints: host arrays dual[rows][m], cur_w[ndict][m],
+ * delta[ndict][m], mask[ndict]; any may be NULL.  m must be the init's and no
+ * mask bit at or above m may be set (PSG_ERR_ARG).  Waits first. */
+int psg_mb_darling_rows_set_state(psg_minibatch* mb, int m, const double* dual,
+                                  const double* cur_w, const double* delta, const uint32_t* mask);
+/* psg_mb_rows_read ids of this state (PSG_ERR_ARG before the init) */
+#define PSG_MB_ROWS_DARLING_DUAL 8     /* double[rows * m] */
+#define PSG_MB_ROWS_DARLING_CUR_W 9    /* double[ndict * m] */
+#define PSG_MB_ROWS_DARLING_DELTA 10   /* double[ndict * m] */
+#define PSG_MB_ROWS_DARLING_DELTA_W 11 /* double[(ce - cb) * m] of the last update_dual */
+#define PSG_MB_ROWS_DARLING_MASK 12    /* uint32[ndict]: bit j = model j active */
+
+/* Darling::updateWeight (darling.cc:437-477) for m models on plain device
+ * arrays the caller owns: G, U, w, delta are [n][m] row-major, active one
+ * uint32 per position (bit j: model j), params a host array of m settings,
+ * vio_dev a device double[m] that the call max-accumulates (:466; zero it to
+ * start).  Column j is bit for bit psg_darling_update_dev's result for
+ * setting j.  The context gives the device and the default stream; its
+ * channels do not carry rows.  Calls on one context must be given one stream.
+ * Enqueues only. */
+int psg_darling_rows_update_dev(psg_ctx* ctx, const double* G_dev, const double* U_dev,
+                                double* w_dev, double* delta_dev, uint32_t* active_dev, size_t n,
+                                int m, const psg_darling_param* params, double* vio_dev,
+                                void* stream);
+/* The server branch of evaluateProgress (:538-555) per model: nnz_w[m],
+ * sum_abs[m] = sum |w| by psg_darling_progress's fixed-order reduction (the
+ * caller multiplies by its lambda), nnz_active[m].  Host outputs, any may be
+ * NULL; synchronises. */
+int psg_darling_rows_progress(psg_ctx* ctx, const double* w_dev, const uint32_t* active_dev,
+                              size_t n, int m, size_t* nnz_w, double* sum_abs, size_t* nnz_active,
+                              void* stream);
+
+/* ------------------------------------------------------------------ */
 /* Model evaluation: the distributed AUC (src/base/auc.h:8-103) and    */
 /* the exact rank AUC (src/base/evaluation.h:17-44)                    */
 /* ------------------------------------------------------------------ */

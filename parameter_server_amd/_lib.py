@@ -81,6 +81,10 @@ PSG_AUC_BY_KEY, PSG_AUC_AS_WRITTEN = 0, 1
 (PSG_MB_DARLING_DUAL, PSG_MB_DARLING_CUR_W, PSG_MB_DARLING_DELTA, PSG_MB_DARLING_ACTIVE,
  PSG_MB_DARLING_DELTA_W) = range(32, 37)
 PSG_MB_DARLING_TERMS = 37
+# ... and the multi-model Darling state (psg_mb_darling_rows_*), read by psg_mb_rows_read
+PSG_DARLING_MAX_MODELS = 32
+(PSG_MB_ROWS_DARLING_DUAL, PSG_MB_ROWS_DARLING_CUR_W, PSG_MB_ROWS_DARLING_DELTA,
+ PSG_MB_ROWS_DARLING_DELTA_W, PSG_MB_ROWS_DARLING_MASK) = range(8, 13)
 # ... and the loaded CSR
 PSG_MB_OFFSET, PSG_MB_INDEX, PSG_MB_VALUE, PSG_MB_Y = range(24, 28)
 # psg_mb_load_text's formats (DataConfig's values)
@@ -370,6 +374,14 @@ SIGNATURES = {
                                     C.POINTER(CacheResult)]),
     "psg_cache_scan_tile": (_sz, []),
     "psg_mb_darling_share_dual": (C.c_int, [_p, _p]),
+    "psg_mb_darling_rows_init": (C.c_int, [_p, C.c_int, C.c_double, _p, _p]),
+    "psg_mb_darling_rows_reset_active": (C.c_int, [_p, _p]),
+    "psg_mb_darling_rows_gradients": (C.c_int, [_p, _sz, _sz, _p, _p, _p]),
+    "psg_mb_darling_rows_update_dual": (C.c_int, [_p, _sz, _sz, _p, _p, _p]),
+    "psg_mb_darling_rows_objv": (C.c_int, [_p, _p, _p]),
+    "psg_mb_darling_rows_set_state": (C.c_int, [_p, C.c_int, _p, _p, _p, _p]),
+    "psg_darling_rows_update_dev": (C.c_int, [_p, _p, _p, _p, _p, _p, _sz, C.c_int, _p, _p, _p]),
+    "psg_darling_rows_progress": (C.c_int, [_p, _p, _p, _sz, C.c_int, _p, _p, _p, _p]),
     "psg_auc_create": (C.c_int, [_p, C.c_int64, C.POINTER(_p)]),
     "psg_auc_destroy": (None, [_p]),
     "psg_auc_clear": (C.c_int, [_p]),

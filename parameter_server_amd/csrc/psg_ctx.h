@@ -325,6 +325,8 @@ struct psg_ctx {
   JobTable table;
   unsigned long long* d_small = nullptr;  // 32 device words: counters, crc args
   unsigned long long* d_vio_slots = nullptr;  // psg::kVioSlots x 64 B, zero between updates
+  // psg_darling_rows_update_dev's slot rows (psg_darling_rows.hip), made at its first call
+  unsigned long long* d_vio_rows = nullptr;
   unsigned long long* h_small = nullptr;  // 32 pinned host words
   // signature-check counters, pooled: slabs of kCtrSlab device
   // words and as many pinned host words their results are copied back into;

@@ -35,6 +35,11 @@ enum BufId {
   // psg_colsum.hip: the control word, the huge runs' keys and first units, the
   // units' runs at level 1 and 2, the units' partials at level 1 and 2
   B_CS_CTL, B_CS_HKEY, B_CS_HBASE, B_CS_UNIT1, B_CS_UNIT2, B_CS_Q1, B_CS_Q2,
+  // psg_darling_rows.hip: dual [rows][m]; cur_w, delta, delta_w, exp(delta)
+  // [ndict][m]; the mask word per key; y tau and tau (1 - tau) [rows][m]; the
+  // block's terms or factors [(hi - lo)][m]; the objv partials and objv [m]
+  B_DR_DUAL, B_DR_CUR_W, B_DR_DELTA, B_DR_DELTA_W, B_DR_EXPD, B_DR_MASK, B_DR_YTAU, B_DR_Q,
+  B_DR_TERM, B_DR_PARTIAL, B_DR_OBJV,
   B_COUNT
 };
 
@@ -69,6 +74,10 @@ struct psg_minibatch : psg::DeviceBlocks<B_COUNT> {
   std::vector<uint32_t> pair_lo, pair_hi;
   size_t n_long = 0;  // the length of the long-run list, read at psg_mb_darling_init
   size_t last_cb = 0, last_ce = 0;  // the columns of the last psg_mb_darling_update_dual
+  // psg_darling_rows.hip: the m of psg_mb_darling_rows_init since the load and
+  // the localize (0: none), and the columns of its last update_dual
+  int drows_m = 0;
+  size_t dr_last_cb = 0, dr_last_ce = 0;
   size_t scratch_len[4] = {0, 0, 0, 0};
   // psg_mb_profile: a pair of timing events around each stage's launches;
   // the last pair is psg_mb_load_text's
@@ -117,6 +126,8 @@ int mb_load_finish(psg_minibatch* mb, size_t rows, size_t nnz, bool valued);
 // mb's dual block is about to go (a load, its destruction): its sharers lose
 // their Darling state, and mb stops sharing another's
 void mb_drop_sharing(psg_minibatch* mb);
+// psg_darling_rows.hip: psg_mb_rows_read's ids from PSG_MB_ROWS_DARLING_DUAL on
+int darling_rows_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t* n_out);
 // psg_terafea.hip, enqueued on `s` by psg_mb_load_terafea.  raw[n]: the keys in
 // line order; offset[rows + 1]: the tokeniser's.
 // *bad = min(*bad, the first row holding a key of group 0)

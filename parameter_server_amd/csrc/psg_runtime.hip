@@ -122,6 +122,7 @@ int psg_destroy(psg_ctx* c) {
   if (c->ring) (void)hipHostFree(c->ring);
   (void)hipFree(c->d_small);
   (void)hipFree(c->d_vio_slots);
+  if (c->d_vio_rows) (void)hipFree(c->d_vio_rows);
   if (c->h_small) (void)hipHostFree(c->h_small);
   (void)hipFree(c->scratch);
   if (c->copy_ev) (void)hipEventDestroy(c->copy_ev);

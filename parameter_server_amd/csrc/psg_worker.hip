@@ -764,6 +764,7 @@ int mb_load_begin(psg_minibatch* mb, size_t rows, size_t n, bool valued) {
   mb->xw_own = false;
   mb->xw_scored = false;
   mb->rows_m = 0;
+  mb->drows_m = 0;
   mb->has_slots = mb->groups_ok = false;
   mb_drop_sharing(mb);
   const size_t ntiles = blocks_of(n, kSortTile);
@@ -919,6 +920,7 @@ int psg_mb_localize(psg_minibatch* mb, const uint64_t* dict_dev, size_t ndict,
   mb->darling = false;
   mb->xw_own = false;
   mb->rows_m = 0;
+  mb->drows_m = 0;
   const uint32_t n = (uint32_t)mb->nnz, nu = (uint32_t)mb->n_uniq, nd = (uint32_t)ndict;
   const uint32_t rows = (uint32_t)mb->rows;
   uint32_t* before = mb->at<uint32_t>(B_BEFORE);

@@ -403,6 +403,8 @@ int psg_mb_rows_labels(psg_minibatch* mb, const double** y_dev, const double** x
 int psg_mb_rows_read(psg_minibatch* mb, int what, void* out, size_t cap_bytes, size_t* n_out) {
   if (!mb || !n_out) return fail(PSG_ERR_ARG, "null argument");
   *n_out = 0;
+  if (what >= PSG_MB_ROWS_DARLING_DUAL)  // the multi-model Darling state (psg_darling_rows.hip)
+    return psg::darling_rows_read(mb, what, out, cap_bytes, n_out);
   if (mb->state < S_LOCAL || mb->rows_m == 0)
     return fail(PSG_ERR_ARG, "psg_mb_rows_read before psg_mb_gradient_rows");
   int id;

@@ -22,6 +22,14 @@ into ``psg_mb_darling_update_dual`` without leaving HBM, all enqueued on the
 minibatch's stream, with no host wait.  ``darling_pass`` drives a whole pass
 over the key blocks for W workers that way, and ``server_progress`` is the
 server branch of ``evaluateProgress`` (:538-555), the one place that waits.
+
+``DarlingMultiWorker`` / ``DarlingMultiServer`` / ``darling_pass_rows`` are the
+same solver for m settings (a regularisation path) over one resident
+minibatch per worker: ``psg_mb_darling_rows_*`` and ``psg_darling_rows_*``
+(include/psg.h), with a row of m values per key or example and one mask word
+per key.  Column j of everything is bit for bit the scalar classes' result
+for setting j.  The server's arrays are plain device arrays: the context's
+channels do not carry rows.
 """
 from __future__ import annotations
 
@@ -31,7 +39,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .kv_vector import KVVector, Message, _ptr
+from .kv_vector import KVVector, Message, RowMergePlan, _ptr, gather_rows_dev
 from .worker import Minibatch
 
 # psg_mb_read's arrays of the Darling state: name -> (id, dtype)
@@ -340,3 +348,274 @@ def server_progress(server: KVVector, chl: int, lambda_: float,
                                               C.byref(objv), C.byref(vio), C.byref(nnz_as)))
     return {"nnz_w": nnz_w.value, "objv": objv.value, "violation": vio.value,
             "nnz_active": nnz_as.value}
+
+
+# ------------------------------------------------ m settings in one pass --
+# psg_mb_rows_read's arrays of the multi-model state: name -> (id, dtype)
+STATE_ROWS = {
+    "dual": (_lib.PSG_MB_ROWS_DARLING_DUAL, np.float64),
+    "cur_w": (_lib.PSG_MB_ROWS_DARLING_CUR_W, np.float64),
+    "delta": (_lib.PSG_MB_ROWS_DARLING_DELTA, np.float64),
+    "delta_w": (_lib.PSG_MB_ROWS_DARLING_DELTA_W, np.float64),
+    "mask": (_lib.PSG_MB_ROWS_DARLING_MASK, np.uint32),
+}
+
+
+def _per_model(x, m: int) -> np.ndarray:
+    a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float64), (m,)))
+    return a.copy()
+
+
+class DarlingMultiWorker:
+    """``DarlingWorker`` for m models over one minibatch (psg_mb_darling_rows_*):
+    dual[rows, m], cur_w / delta[ndict, m], a uint32 mask per key with bit j
+    for model j.  ``delta_max``: one value or one per model."""
+
+    _DICT, _W = 0, 1
+    _GU, _PULL = 0, 1  # scratch slots of the minibatch
+
+    def __init__(self, ctx, m: int, delta_init: float, delta_max, device: int = 0):
+        self._L = _lib.lib()
+        if not 1 <= m <= _lib.PSG_DARLING_MAX_MODELS:
+            raise _lib.PSGError(_lib.PSG_ERR_ARG, f"{m} models: 1 .. {_lib.PSG_DARLING_MAX_MODELS}")
+        self._ctx, self.device, self.m = ctx, device, int(m)
+        self.delta_init = float(delta_init)
+        self.delta_max = _per_model(delta_max, self.m)
+        self.mb = Minibatch(ctx)
+        self._dev = {}
+        self.dict_keys = np.zeros(0, np.uint64)
+        self.ndict = 0
+
+    def close(self):
+        self.mb.close()
+        self._dev = {}
+
+    _upload = DarlingWorker._upload
+
+    def _init(self, dict_keys, w) -> None:
+        w_dev = None
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (dict_keys.size, self.m):
+                raise _lib.PSGError(_lib.PSG_ERR_SIZE,
+                                    f"weights {w.shape}, ({dict_keys.size}, {self.m}) expected")
+            w_dev = self._upload(self._W, w)
+        _lib.check(self._L.psg_mb_darling_rows_init(self.mb._h, self.m, self.delta_init, w_dev,
+                                                    None))
+        self.dict_keys, self.ndict = dict_keys, dict_keys.size
+
+    def load(self, offset, index, value, y, dict_keys, w=None) -> None:
+        """As ``DarlingWorker.load``; ``w`` is [ndict, m]."""
+        dict_keys = np.ascontiguousarray(dict_keys, dtype=np.uint64)
+        mb = self.mb
+        mb.load(offset, index, value, y)
+        mb.uniq()
+        mb.localize(self._upload(self._DICT, dict_keys), dict_keys.size)
+        self._init(dict_keys, w)
+
+    def load_group(self, reader, slot_id: int, dict_keys, w=None) -> None:
+        """As ``DarlingWorker.load_group``, without a shared dual."""
+        dict_keys = np.ascontiguousarray(dict_keys, dtype=np.uint64)
+        mb = self.mb
+        reader.extract(slot_id, mb)
+        mb.uniq()
+        mb.localize(self._upload(self._DICT, dict_keys), dict_keys.size)
+        self._init(dict_keys, w)
+
+    def reset_active(self) -> None:
+        _lib.check(self._L.psg_mb_darling_rows_reset_active(self.mb._h, None))
+
+    def gradients_dev(self, cb: int, ce: int, stream=None) -> Tuple[int, int]:
+        """computeGradients over columns [cb, ce) into scratch: the device
+        addresses of G and U, [ce - cb, m] each.  Enqueues only."""
+        nb = 8 * max(ce - cb, 0) * self.m
+        p = self.mb.scratch(self._GU, max(2 * nb, 8))
+        _lib.check(self._L.psg_mb_darling_rows_gradients(self.mb._h, cb, ce, p, p + nb, stream))
+        return p, p + nb
+
+    def gradients(self, cb: int, ce: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Host copies of (G, U), [ce - cb, m] each."""
+        n = max(ce - cb, 0) * self.m
+        self.gradients_dev(cb, ce)
+        gu = self.mb.read_scratch(self._GU, np.float64, 2 * n)
+        return gu[:n].reshape(-1, self.m).copy(), gu[n:].reshape(-1, self.m).copy()
+
+    def update_dual_dev(self, cb: int, ce: int, new_w_dev: int, stream=None) -> None:
+        _lib.check(self._L.psg_mb_darling_rows_update_dual(
+            self.mb._h, cb, ce, new_w_dev, _ptr(self.delta_max), stream))
+
+    def update_dual(self, cb: int, ce: int, new_w) -> None:
+        """updateDual with the pulled weights [ce - cb, m] of columns [cb, ce)."""
+        new_w = np.ascontiguousarray(new_w, dtype=np.float64)
+        if new_w.shape != (max(ce - cb, 0), self.m):
+            raise _lib.PSGError(_lib.PSG_ERR_SIZE, f"weights {new_w.shape} for [{cb}, {ce})")
+        self.update_dual_dev(cb, ce, self._upload(self._W, new_w))
+
+    def objv(self) -> np.ndarray:
+        v = np.zeros(self.m)
+        _lib.check(self._L.psg_mb_darling_rows_objv(self.mb._h, _ptr(v), None))
+        return v
+
+    def _read(self, what: int, dtype) -> np.ndarray:
+        n = C.c_size_t()
+        rc = self._L.psg_mb_rows_read(self.mb._h, what, None, 0, C.byref(n))
+        if rc not in (_lib.PSG_OK, _lib.PSG_ERR_SIZE):
+            _lib.check(rc)
+        out = np.empty(n.value, dtype)
+        if n.value:
+            _lib.check(self._L.psg_mb_rows_read(self.mb._h, what, _ptr(out), out.nbytes,
+                                                C.byref(n)))
+        return out
+
+    def state(self) -> dict:
+        """Host copies: dual, cur_w, delta, delta_w as [., m]; mask as uint32[ndict]."""
+        st = {name: self._read(what, dtype) for name, (what, dtype) in STATE_ROWS.items()}
+        return {k: v if k == "mask" else v.reshape(-1, self.m) for k, v in st.items()}
+
+    def set_state(self, dual=None, cur_w=None, delta=None, mask=None, m: Optional[int] = None):
+        def arr(a, dtype):
+            return None if a is None else np.ascontiguousarray(a, dtype=dtype)
+        a = [arr(dual, np.float64), arr(cur_w, np.float64), arr(delta, np.float64),
+             arr(mask, np.uint32)]
+        _lib.check(self._L.psg_mb_darling_rows_set_state(
+            self.mb._h, self.m if m is None else m,
+            *[_ptr(x) if x is not None and x.size else None for x in a]))
+
+
+class DarlingMultiServer:
+    """The server of m settings: w, delta [n, m] and the mask word per key on
+    the device of ``ctx``; ``settings`` is a list of m dicts {eta, lambda_,
+    kkt_filter_threshold, delta_max}.  ``update`` is Darling::updateWeight
+    (darling.cc:437-477) per model by psg_darling_rows_update_dev."""
+
+    def __init__(self, ctx, keys, settings: Sequence[dict], delta_init: float = 1.0,
+                 device: int = 0):
+        import torch
+        self._L, self._ctx, self.device = _lib.lib(), ctx, device
+        self.m = len(settings)
+        if not 1 <= self.m <= _lib.PSG_DARLING_MAX_MODELS:
+            raise _lib.PSGError(_lib.PSG_ERR_ARG, f"{self.m} models")
+        self.keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        self.settings = [dict(s) for s in settings]
+        self._param = (_lib.DarlingParam * self.m)(*[
+            _lib.DarlingParam(s["eta"], s["lambda_"], s["kkt_filter_threshold"], s["delta_max"])
+            for s in settings])
+        n, dev = self.keys.size, "cuda:%d" % device
+        self.d_keys = torch.from_numpy(self.keys.view(np.int64).copy()).to(dev)
+        self.w = torch.zeros((n, self.m), dtype=torch.float64, device=dev)
+        self.delta = torch.full((n, self.m), float(delta_init), dtype=torch.float64, device=dev)
+        self.mask = torch.full((n,), self._all(), dtype=torch.int32, device=dev)
+        self.vio = torch.zeros(self.m, dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(device)
+        self._plans = {}
+
+    def _all(self) -> int:
+        return -1 if self.m == 32 else (1 << self.m) - 1
+
+    def close(self):
+        for p in self._plans.values():
+            p[0].close()
+        self._plans = {}
+
+    def reset_active(self) -> None:
+        import torch
+        torch.cuda.synchronize(self.device)
+        self.mask.fill_(self._all())
+        torch.cuda.synchronize(self.device)
+
+    def update(self, kb: int, ke: int, G: int, U: int, stream=None) -> None:
+        """The update of positions [kb, ke) from the device arrays G, U
+        [ke - kb, m]; the block's violation is max-accumulated.  Enqueues."""
+        if ke <= kb:
+            return
+        m = self.m
+        _lib.check(self._L.psg_darling_rows_update_dev(
+            self._ctx, G, U, self.w.data_ptr() + 8 * m * kb, self.delta.data_ptr() + 8 * m * kb,
+            self.mask.data_ptr() + 4 * kb, ke - kb, m, C.cast(self._param, C.c_void_p),
+            self.vio.data_ptr(), stream))
+
+    def violation(self, reset: bool = False) -> np.ndarray:
+        """The violation of every model since the last reset; waits."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        v = self.vio.cpu().numpy().copy()
+        if reset:
+            self.vio.zero_()
+            torch.cuda.synchronize(self.device)
+        return v
+
+    def progress(self) -> dict:
+        """evaluateProgress' server branch per model: nnz_w, objv = lambda *
+        sum |w|, violation, nnz_active; waits."""
+        nnz = (C.c_size_t * self.m)()
+        act = (C.c_size_t * self.m)()
+        sa = np.zeros(self.m)
+        _lib.check(self._L.psg_darling_rows_progress(
+            self._ctx, self.w.data_ptr(), self.mask.data_ptr(), self.keys.size, self.m,
+            C.cast(nnz, C.c_void_p), _ptr(sa), C.cast(act, C.c_void_p), None))
+        lam = np.array([s["lambda_"] for s in self.settings])
+        return {"nnz_w": np.array(nnz[:], np.int64), "objv": lam * sa,
+                "violation": self.violation(), "nnz_active": np.array(act[:], np.int64)}
+
+    def weights(self) -> np.ndarray:
+        import torch
+        torch.cuda.synchronize(self.device)
+        return self.w.cpu().numpy()
+
+    def active(self) -> np.ndarray:
+        import torch
+        torch.cuda.synchronize(self.device)
+        return self.mask.cpu().numpy().view(np.uint32)
+
+
+def darling_pass_rows(server: DarlingMultiServer, workers: Sequence[DarlingMultiWorker],
+                      key_blocks: Sequence[tuple]) -> None:
+    """``darling_pass`` for m settings: for each global key block [kb, ke), in
+    order, every worker holding a key of it computes its (G, U) rows, the
+    server updates the block once, every such worker runs updateDual from the
+    block's new weights.  A single worker whose columns are the server's
+    positions of the block hands its rows straight to the update and reads the
+    new weights in place.  Otherwise the workers' rows are folded in worker
+    order by a ``RowMergePlan`` (G and U as two jobs of rows of m) and each
+    worker's weights come back through ``gather_rows_dev``.  Everything is
+    enqueued on the workers' stream; nothing crosses the host inside a
+    block."""
+    import torch
+    m, skeys = server.m, server.keys
+    sched = pass_schedule([w.dict_keys for w in workers], key_blocks)
+    stream = workers[0].mb.stream if workers else None
+    for (kb, ke), row in zip(key_blocks, sched):
+        if not row:
+            continue
+        pb, pe = block_columns(skeys, kb, ke)  # the server's positions of the block
+        n = pe - pb
+        direct = len(row) == 1 and row[0][2] - row[0][1] == n and np.array_equal(
+            workers[row[0][0]].dict_keys[row[0][1]:row[0][2]], skeys[pb:pe])
+        if direct:
+            i, cb, ce = row[0]
+            G, U = workers[i].gradients_dev(cb, ce, stream)
+            server.update(pb, pe, G, U, stream)
+            workers[i].update_dual_dev(cb, ce, server.w.data_ptr() + 8 * m * pb, stream)
+            continue
+        for i, cb, ce in row:
+            workers[i].mb.scratch(workers[i]._PULL, 8 * m * (ce - cb))
+        gu = [workers[i].gradients_dev(cb, ce, stream) for i, cb, ce in row]
+        key = (pb, pe, tuple(row), tuple(gu))
+        if key not in server._plans:
+            agg = torch.empty((2, max(n, 1), m), dtype=torch.float64, device=server.w.device)
+            pk = [workers[i]._dev[workers[i]._DICT].data_ptr() + 8 * cb for i, cb, ce in row]
+            pn = [ce - cb for i, cb, ce in row]
+            jobs = [{"keys": server.d_keys.data_ptr() + 8 * pb, "nslots": n, "push_keys": pk,
+                     "push_rows": [p[a] for p in gu], "push_n": pn, "out": agg[a].data_ptr()}
+                    for a in (0, 1)]
+            server._plans[key] = (RowMergePlan(server.device, _lib.PSG_F64, m, jobs), agg)
+        plan, agg = server._plans[key]
+        plan.run(stream)
+        server.update(pb, pe, agg[0].data_ptr(), agg[1].data_ptr(), stream)
+        for i, cb, ce in row:
+            wk = workers[i]
+            p = wk.mb.scratch(wk._PULL, 8 * m * (ce - cb))
+            gather_rows_dev(_lib.PSG_F64, m, server.d_keys.data_ptr() + 8 * pb, n,
+                            server.w.data_ptr() + 8 * m * pb, wk._dev[wk._DICT].data_ptr() + 8 * cb,
+                            ce - cb, p, stream=stream)
+            wk.update_dual_dev(cb, ce, p, stream)
